@@ -4,7 +4,7 @@ IMG ?= ghcr.io/walkai/nos-mi355x:0.1.0
 CLIENT_IMG ?= ghcr.io/walkai/nos-mi355x-client:0.1.0
 NAMESPACE ?= nos-system
 
-.PHONY: all native test test-gpu lint sanitize helm-docs bench bench-8 smoke simulate devcluster kbench docker-build docker-push \
+.PHONY: all native test test-gpu lint sanitize helm-docs bench bench-full bench-8 smoke simulate devcluster kbench docker-build docker-push \
         deploy undeploy install-crds helm-install helm-uninstall kind-up clean
 
 all: native test
@@ -24,8 +24,11 @@ lint:
 sanitize:          ## host-code sanitizers (ASan+UBSan, TSan) over the HBM-limit shim's self-test
 	$(PYTHON) -m pytest tests/test_native_sanitizers.py -q
 
-bench: native      ## flagship benchmark, 1 GPU
+bench: native      ## flagship benchmark, 1 GPU: the headline window only
 	$(PYTHON) bench.py
+
+bench-full: native ## flagship benchmark with the density phase, the partitions window and the control-plane models
+	$(PYTHON) bench.py --full
 
 bench-8: native    ## flagship benchmark, 8 GPUs of one node (one rank per GPU over RCCL)
 	$(PYTHON) -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \

@@ -7,8 +7,13 @@ churning mix of 1/8, 1/2 and 1/1-GPU YOLOS-small inference pods through the nos 
 One step = one quantum of ``--cluster-s`` seconds of cluster time replayed in ``--quantum`` wall
 seconds of GPU serving (pod lifetimes, planner thresholds and flip outages compressed alike; the
 GPU serves at its real rate); every compute-partition flip darkens its GPU for the measured flip
-cost.  After the timed window a density phase saturates the node (8 CPX pods per GPU, then CU-mask
-slices beyond).  Rank 0 prints one JSON line.
+cost.  Rank 0 prints one JSON line.
+
+A plain run does what the headline needs and no more: set-up, warm-up, the timed steps, the result
+line.  ``--full`` adds everything measured beside it: the node commit barrier probe, a density phase
+that saturates the node (8 CPX pods per GPU, then CU-mask slices beyond), the same window on
+hardware partitions and the control-plane models (seeds, sensitivities, load 0.85).
+``--dump-outputs DIR`` writes the data plane's outputs after the timed steps as ``DIR/<name>.npy``.
 """
 from __future__ import annotations
 
@@ -55,7 +60,13 @@ def main() -> int:
     ap.add_argument("--lane-cus", type=int, default=0,
                     help="opt-in: a partition pod wider than this many CUs runs one batch-1 request loop per "
                          "disjoint run of this many CUs (0 = one loop per pod, as the reference demo)")
-    ap.add_argument("--no-density", action="store_true", help="skip the saturation/density phase")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the node commit barrier probe, the "
+                         "density phase, the same window on hardware partitions, the control-plane models")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write every partition slot's latest (logits, boxes) as "
+                         "DIR/<name>.npy (float32; inputs and weights are seeded, the same from run to run)")
+    ap.add_argument("--no-density", action="store_true", help="with --full: skip the saturation/density phase")
     ap.add_argument("--emulation", default=None, choices=("pinned", "spread", "landing"),
                     help="compute-partition emulation on the SPX device (default: spread; bench_core.EMULATION)")
     ap.add_argument("--erq", action="store_true",
@@ -93,7 +104,7 @@ def main() -> int:
                       flip_cost_s=args.flip_cost, policy=args.policy, depth=args.depth,
                       density=not args.no_density, pod_streams=args.pod_streams, lane_cus=args.lane_cus,
                       device_plugin=args.device_plugin, layout=args.layout, pod_start_s=args.pod_start,
-                      data_plane=not args.no_data_plane)
+                      data_plane=not args.no_data_plane, full=args.full, dump_outputs=args.dump_outputs)
     if args.emulation:
         cfg.emulation = args.emulation
     if args.erq:

@@ -1,7 +1,10 @@
 """pytest configuration: the ``gpu`` marker (tests that need an MI355X; the CPU suite runs
-``-m "not gpu"``) and the repository root on ``sys.path``."""
+``-m "not gpu"``), the repository root on ``sys.path`` and a temporary directory short enough for
+unix sockets."""
 import os
+import shutil
 import sys
+import tempfile
 
 import pytest
 
@@ -10,9 +13,46 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
+#: A unix socket's path holds at most 107 bytes (``sockaddr_un.sun_path``). The device-plugin and
+#: process tests bind theirs up to ~65 bytes below ``tempfile.gettempdir()`` (``tmpXXXXXXXX/node-1/
+#: device-plugins/nos-xcp-amd.com_spx_nps1.sock``; kubelet's own directory is short), so under a
+#: temporary directory longer than this the suite moves its temporary files to a shorter one.
+_TMP_MAX = 24
+_TMP_CANDIDATES = ("/tmp", "/var/tmp", "/dev/shm")
+_short_tmp = None
+_tmpdir_env = os.environ.get("TMPDIR")
+
+
+def _shorten_tempdir():
+    global _short_tmp
+    cur = tempfile.gettempdir()
+    if len(cur) <= _TMP_MAX:
+        return
+    for cand in _TMP_CANDIDATES:
+        if len(cand) < len(cur) and os.path.isdir(cand) and os.access(cand, os.W_OK | os.X_OK):
+            _short_tmp = tempfile.mkdtemp(prefix="nos-", dir=cand)
+            tempfile.tempdir = _short_tmp
+            os.environ["TMPDIR"] = _short_tmp   # the processes the tests start
+            return
+
+
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
     config.addinivalue_line("markers", "slow: long-running simulation test")
+    _shorten_tempdir()
+
+
+def pytest_unconfigure(config):
+    global _short_tmp
+    if _short_tmp is not None:
+        if tempfile.tempdir == _short_tmp:
+            tempfile.tempdir = None
+        if _tmpdir_env is None:
+            os.environ.pop("TMPDIR", None)
+        else:
+            os.environ["TMPDIR"] = _tmpdir_env
+        shutil.rmtree(_short_tmp, ignore_errors=True)
+        _short_tmp = None
 
 
 @pytest.fixture(autouse=True)

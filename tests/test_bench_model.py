@@ -53,3 +53,20 @@ def test_pod_start_sensitivity_rows():
     assert list(s) == ["0s", "3s", "6s", "12s"]
     v = [row["inf_per_s_model"] for row in s.values()]
     assert v == sorted(v, reverse=True) and len({row["util_pct"] for row in s.values()}) == 1
+
+
+def test_a_plain_run_leaves_out_what_full_adds(tmp_path):
+    """``run_bench`` without ``full`` (a plain ``bench.py`` run) stops at the headline window: the
+    driver's fields are there, ``ms_per_step`` is the wall time of one timed step (two quanta of
+    ``quantum_s``), and none of the fields measured beside the window is. A rehearsal has no data
+    plane, so ``dump_outputs`` writes nothing and says so."""
+    from walkai_nos_amd.bench_core import FULL_ONLY_KEYS, run_bench
+    c = _cfg(steps=2, warmup=1, preroll=5, quantum_s=0.05, dump_outputs=str(tmp_path / "dump"))
+    r = run_bench(c)
+    assert not c.full and r["full"] is False
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in r
+    assert r["steps"] == 2 and r["value"] > 0
+    assert r["ms_per_step"] == pytest.approx(1000.0 * c.quanta_per_step * c.quantum_s, rel=0.25)
+    assert not set(FULL_ONLY_KEYS) & set(r)
+    assert r["outputs"]["arrays"] == 0 and not (tmp_path / "dump").exists()

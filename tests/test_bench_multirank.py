@@ -126,7 +126,7 @@ def test_bench_py_eight_rank_rehearsal_prints_one_json_line():
     t0 = time.time()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8",
                         "--master-addr=127.0.0.1", f"--master-port={port}", "bench.py", "--gpus", "8",
-                        "--steps", "20", "--warmup", "5", "--no-data-plane", "--no-density"],
+                        "--steps", "20", "--warmup", "5", "--no-data-plane", "--full", "--no-density"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=900)
     wall = time.time() - t0
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

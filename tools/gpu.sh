@@ -8,9 +8,9 @@
 #   tests              pytest -m gpu (in one process)
 #   test_k             pytest -m gpu -k "$NOS_TEST_K"
 #   smoke              __graft_entry__.smoke()
-#   bench              bench.py as the driver runs it (--gpus 1 --steps 20 --warmup 5)
+#   bench              bench.py with the driver's flags (--gpus 1 --steps 20 --warmup 5) plus --full: the whole record
 #   bench_ranks        the driver's N > 1 launch rehearsed on the one GPU: NOS_RANKS ranks (default 2) over gloo
-#   bench_torch        bench.py on the PyTorch (hipBLASLt) backend, for comparison
+#   bench_torch        bench.py --full on the PyTorch (hipBLASLt) backend, for comparison
 #   seeds              the bench window over churn seeds 1-5 and 1234 (NOS_SEEDS overrides)
 #   operator           tools/operator_gpu_report.py: device map, commit barrier, probes
 #   pod_start          tools/pod_start_probe.py: a pod process's boot phase by phase (1/8-GPU slice)
@@ -21,8 +21,8 @@
 #   pmc_op             PMC passes over one op (NOS_OP, NOS_SLICE), counters in their own runs
 #   pmc_modes          L2 counters of a partition mode with all partitions busy (NOS_MODE, NOS_PARTS)
 #   kbench             tools/kbench.py per-op / per-mode microbenchmarks (NOS_KBENCH_ARGS)
-#   bench_runs         bench.py once per NOS_BENCH_RUNS entry ("<tag>:<arg>,<arg> ..."), e.g. layouts / seeds
-#   bench_long         bench.py over NOS_STEPS quanta (default 100) for a longer window
+#   bench_runs         bench.py --full once per NOS_BENCH_RUNS entry ("<tag>:<arg>,<arg> ..."), e.g. layouts / seeds
+#   bench_long         bench.py --full over NOS_STEPS quanta (default 100) for a longer window
 #   fair               tools/gpu_fair.sh: memory-only fairness as processes (NOS_FAIR_ONLY, NOS_FAIR_VARIANTS)
 #   fair_probe         tools/fair_probe.py: per-pod rates, amd-smi CU occupancy, KFD queues (NOS_FAIR_PODS)
 #   replay             tools/model_replay.py + replay_stats kernel traces per slice (NOS_SLICES, default "dpx cpx")
@@ -66,11 +66,11 @@ for s in "$@"; do
     test_k) step "test_${NOS_TEST_K:-x}" 600 python -u -m pytest tests -m gpu -x -v -rfP --timeout 300 \
               --timeout-method thread -k "${NOS_TEST_K:-x}" ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 600 python bench.py --gpus 1 --steps 20 --warmup 5 --out "$OUT/bench.json" ;;
+    bench) step bench 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full --out "$OUT/bench.json" ;;
     bench_ranks) step "bench_${NOS_RANKS:-2}rank" 900 env NOS_BENCH_DIST_BACKEND=gloo python -m torch.distributed.run \
                    --nnodes=1 --nproc-per-node "${NOS_RANKS:-2}" --master-addr 127.0.0.1 --master-port 29517 bench.py \
                    --gpus "${NOS_RANKS:-2}" --steps 20 --warmup 5 --no-density ;;
-    bench_torch) step bench_torch 600 python bench.py --steps 20 --warmup 5 --backend torch --out "$OUT/bench_torch.json" ;;
+    bench_torch) step bench_torch 600 python bench.py --steps 20 --warmup 5 --backend torch --full --out "$OUT/bench_torch.json" ;;
     seeds)
       mkdir -p "$OUT/seeds"
       for seed in ${NOS_SEEDS:-1 2 3 4 5 1234}; do
@@ -118,9 +118,9 @@ for s in "$@"; do
     bench_runs)
       for spec in ${NOS_BENCH_RUNS:-slices_1234:--layout=slices partitions_1234:--layout=partitions}; do
         tag=${spec%%:*}; args=${spec#*:}
-        step "bench_$tag" 400 python -u bench.py ${args//,/ } --out "$OUT/bench_$tag.json"
+        step "bench_$tag" 400 python -u bench.py --full ${args//,/ } --out "$OUT/bench_$tag.json"
       done ;;
-    bench_long) step "bench_${NOS_STEPS:-100}q" 900 python -u bench.py --steps "${NOS_STEPS:-100}" --warmup 5 \
+    bench_long) step "bench_${NOS_STEPS:-100}q" 900 python -u bench.py --full --steps "${NOS_STEPS:-100}" --warmup 5 \
                   --out "$OUT/bench_${NOS_STEPS:-100}q.json" ;;
     fair) step fair 1100 bash tools/gpu_fair.sh ;;
     fair_probe) step fair_probe 900 python -u tools/fair_probe.py --pods "${NOS_FAIR_PODS:-5,7,8}" \

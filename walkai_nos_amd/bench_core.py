@@ -41,9 +41,11 @@ XCDs couple the partitions (see EMULATION). Mode changes go through the fake amd
 (whose device map re-enumerates like the real one); everything else — kernels, streams,
 collectives — is real.
 
-After the timed window a **density** phase saturates the node through the same control plane and
-data plane: 8 CPX pods per GPU (the reference's MIG maximum is 7 per A100), then a CU-mask node
-with dedicated-CU and memory-only slices beyond 8 per GPU.  It is reported, never timed.
+With ``full`` (``bench.py --full``), after the timed window a **density** phase saturates the node
+through the same control plane and data plane: 8 CPX pods per GPU (the reference's MIG maximum is
+7 per A100), then a CU-mask node with dedicated-CU and memory-only slices beyond 8 per GPU.  It is
+reported, never timed; so are the node barrier probe, the partitions window and the control-plane
+models, which a plain run leaves out as well (:data:`FULL_ONLY_KEYS`).
 """
 from __future__ import annotations
 
@@ -181,6 +183,10 @@ class BenchConfig:
                                          # (<0: POD_START_S; bench.py measures it on the box before the window)
     declared_bound_quanta: float = 0.0   # >0: every pod declares spec.activeDeadlineSeconds = this many quanta
                                          # (plus its start-up), no tighter than the churn's longest lifetime
+    full: bool = False                   # also run what the headline does not need (bench.py --full): the node
+                                         # barrier probe, the density phase, the partitions window and the
+                                         # control-plane models after the window
+    dump_outputs: str = ""               # directory the data plane's outputs are written to after the window
 
     def __post_init__(self) -> None:
         #: the flip cost is the components' sum (so a measured commit barrier replaces its constant)
@@ -592,6 +598,33 @@ class DataPlane:
         for t in threads:
             t.join()
         return {k: sum(v) for k, v in counts.items()}
+
+    def outputs(self) -> Dict[str, Any]:
+        """What a caller of the serving path receives, per pre-warmed partition slot and lane: the
+        (logits, boxes) of the lane's latest inference as float32 arrays, keyed
+        ``<profile>_<partition>_lane<i>_<logits|boxes>``. A lane's input and the weights are seeded
+        and never change, so the set of names and (for a deterministic build) every value is the
+        same from run to run, whichever pods the churn put on the slot last. A slot no pod was put on
+        since its latencies were cleared (the start of the window) serves one inference first — a
+        captured graph's output buffer holds nothing of its own until the first replay. Slots added for
+        unaligned slices or the density phase are not listed: whether they exist depends on the run."""
+        import torch
+        self.drain_all()
+        torch.cuda.synchronize()
+        out: Dict[str, Any] = {}
+        for key, slot in self.slots.items():
+            if len(key) != 2 or key[0] == "slice" or not isinstance(key[1], int):
+                continue
+            if not slot.latency_ms:
+                for _ in slot.lanes:
+                    slot.submit()
+                slot.drain()
+            for i, lane in enumerate(slot.lanes):
+                if lane.out is None:
+                    continue
+                for name, t in zip(("logits", "boxes"), lane.out):
+                    out[f"{key[0]}_{key[1]}_lane{i}_{name}"] = t.detach().to("cpu", torch.float32).numpy().copy()
+        return out
 
     def close(self) -> None:
         """Release graphs, model replicas and CU-masked streams before interpreter teardown (a
@@ -1268,6 +1301,10 @@ def dist_report(cfg: BenchConfig, barrier_node: Optional[Dict[str, Any]]) -> Dic
             "commit_barrier_node_devices": (barrier_node or {}).get("devices")}
 
 
+#: result fields only a ``--full`` run fills (everything measured beside the headline window)
+FULL_ONLY_KEYS = ("flip_cost_sensitivity", "pod_start_sensitivity", "seed_model", "load_0.85", "commit_barrier_node",
+                  "partitions_window", "post_window", "pods_per_gpu_saturation", "density")
+
 #: wall seconds rank 0 may spend on the control-plane models after the windows (the other ranks
 #: wait): models past the budget are skipped and named in ``post_window.skipped``
 POST_WINDOW_BUDGET_S = {1: 120.0, 2: 120.0, 4: 90.0, 8: 60.0}
@@ -1323,15 +1360,17 @@ def run_bench(cfg: BenchConfig) -> Dict[str, Any]:
     commits_main = commits[0]
     latency = inference_latency(nb.data)
     per_profile = nb.profile_report(elapsed)
-    barrier_8dev = node_barrier_probe(cfg) if cfg.rank == 0 and gpu else None
-    density = density_phase(cfg, nb.data) if cfg.density else {}
+    dumped = dump_outputs(cfg, nb.data) if cfg.dump_outputs else None
+    barrier_8dev = node_barrier_probe(cfg) if cfg.full and cfg.rank == 0 and gpu else None
+    density = density_phase(cfg, nb.data) if cfg.full and cfg.density else {}
     nb.close()
     value = total_inf / elapsed
     util = _mean(nb.util_samples)
     raw = _mean(nb.raw_util_samples)
     pods = _mean(nb.pods_samples)
     # BASELINE config 4 beside the headline (the sliced default): the same window on hardware partitions
-    part = partitions_window(cfg, gpu, distributed) if cfg.layout != "partitions" and cfg.partitions_window else None
+    part = (partitions_window(cfg, gpu, distributed)
+            if cfg.full and cfg.layout != "partitions" and cfg.partitions_window else None)
     dist_block = dist_report(cfg, barrier_8dev)
     from .models.workload.yolos import YolosSmall
     from .ops import kernels as K
@@ -1342,7 +1381,7 @@ def run_bench(cfg: BenchConfig) -> Dict[str, Any]:
     skipped: List[str] = []
 
     def within(name: str, fn):
-        if cfg.rank != 0:
+        if cfg.rank != 0 or not cfg.full:
             return {}
         if time.perf_counter() - t_post > budget:
             skipped.append(name)
@@ -1358,7 +1397,7 @@ def run_bench(cfg: BenchConfig) -> Dict[str, Any]:
     sustainable = within("load_0.85", lambda: sustainable_load_row(cfg))
     post = {"budget_s": budget, "spent_s": round(time.perf_counter() - t_post, 1), "skipped": skipped}
     life_s = cfg.mean_lifetime_quanta * cfg.cluster_s
-    return {
+    res = {
         "metric": "aggregate GPU utilization % + schedulable pods/node, mixed fractional-GPU load",
         "value": round(value, 3),
         "unit": "inferences/s (aggregate over all GPUs; YOLOS-small fp32 batch-1 pods)",
@@ -1434,7 +1473,31 @@ def run_bench(cfg: BenchConfig) -> Dict[str, Any]:
                    "pod_streams": cfg.pod_streams, "lane_cus": cfg.lane_cus,
                    "partition_emulation": cfg.emulation,
                    "fp32_matmul": (K.get_fp32_matmul() if cfg.backend == "hip" else "hipblaslt-f32")},
+        "full": cfg.full,
     }
+    if not cfg.full:
+        for k in FULL_ONLY_KEYS:
+            res.pop(k, None)
+    if dumped is not None:
+        res["outputs"] = dumped
+    return res
+
+
+def dump_outputs(cfg: BenchConfig, data: Optional[DataPlane]) -> Dict[str, Any]:
+    """Write this rank's :meth:`DataPlane.outputs` to ``cfg.dump_outputs`` as ``<name>.npy`` (float32;
+    under torchrun every name starts with ``rank<r>_``) and say what was written."""
+    import numpy as np
+    if data is None:
+        return {"dir": cfg.dump_outputs, "arrays": 0, "note": "no data plane (rehearsal): nothing to write"}
+    os.makedirs(cfg.dump_outputs, exist_ok=True)
+    prefix = f"rank{cfg.rank}_" if cfg.world > 1 else ""
+    idle = [f"{k[0]}_{k[1]}" for k, s in data.slots.items() if len(k) == 2 and not s.latency_ms]
+    arrays = data.outputs()
+    for name, a in arrays.items():
+        np.save(os.path.join(cfg.dump_outputs, prefix + name + ".npy"), a)
+    return {"dir": cfg.dump_outputs, "arrays": len(arrays), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "dtype": "float32", "what": "every pre-warmed partition slot's latest (logits, boxes), per lane",
+            "idle_in_window_served_once_for_the_dump": idle}
 
 
 def measure_commit_barrier() -> Optional[float]:
