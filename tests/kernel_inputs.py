@@ -206,3 +206,27 @@ def split3_points() -> torch.Tensor:
     while len(bits) % 4:
         bits.append(0x3F800000)
     return torch.from_numpy(np.array(bits, dtype=np.uint32).view(np.float32).copy())
+
+
+# ---- the collector of the GPU tests' figures --------------------------------------------------------
+class Worst:
+    """Collects ``err`` against ``max(factor * err_ref, floor)``, prints the worst ratio, then asserts:
+    the figures reach the log whether or not the bound holds."""
+
+    def __init__(self, name, factor=4.0, label="edges"):
+        self.label = label
+        self.name, self.factor, self.ratio, self.at, self.n, self.fail = name, factor, 0.0, None, 0, []
+
+    def check(self, err, err_ref, floor, tag):
+        self.n += 1
+        ratio = err / err_ref if err_ref > 0 else (0.0 if err == 0 else math.inf)
+        if not ratio <= self.ratio:  # NaN counts
+            self.ratio, self.at = ratio, (tag, err, err_ref)
+        if not err <= max(self.factor * err_ref, floor):
+            self.fail.append((tag, err, err_ref, floor))
+
+    def done(self):
+        print(f"[{self.label}] {self.name}: {self.n} checks, worst err/err_ref {self.ratio:.3g} at {self.at}, "
+              f"{len(self.fail)} over the bound")
+        assert self.n > 0
+        assert not self.fail, (self.name, len(self.fail), self.fail[:6])

@@ -18,6 +18,7 @@ import torch
 import torch.nn.functional as F
 
 import kernel_inputs as KI
+from kernel_inputs import Worst
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import erf_fit  # noqa: E402  (the CPU replay of the packed GELU)
@@ -38,28 +39,6 @@ def K():
     assert kernels.hip_available(), "libnos_kernels.so must be built on a GPU box"
     kernels.set_backend("hip")
     return kernels
-
-
-class Worst:
-    """Collects ``err`` against ``max(factor * err_ref, floor)``, prints the worst ratio, then asserts:
-    the figures reach the log whether or not the bound holds."""
-
-    def __init__(self, name, factor=4.0):
-        self.name, self.factor, self.ratio, self.at, self.n, self.fail = name, factor, 0.0, None, 0, []
-
-    def check(self, err, err_ref, floor, tag):
-        self.n += 1
-        ratio = err / err_ref if err_ref > 0 else (0.0 if err == 0 else math.inf)
-        if not ratio <= self.ratio:  # NaN counts
-            self.ratio, self.at = ratio, (tag, err, err_ref)
-        if not err <= max(self.factor * err_ref, floor):
-            self.fail.append((tag, err, err_ref, floor))
-
-    def done(self):
-        print(f"[edges] {self.name}: {self.n} checks, worst err/err_ref {self.ratio:.3g} at {self.at}, "
-              f"{len(self.fail)} over the bound")
-        assert self.n > 0
-        assert not self.fail, (self.name, len(self.fail), self.fail[:6])
 
 
 # ---- attention ----------------------------------------------------------------------------------

@@ -206,6 +206,11 @@ class YolosSmall(nn.Module):
 
     # -- forward -------------------------------------------------------------------------
     def forward(self, pixels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        return self.detect(self.encode(pixels))
+
+    def encode(self, pixels: torch.Tensor) -> torch.Tensor:
+        """Tokens after the last block, ``[B, T, D]`` (before ``ln_f``): every row, not only the
+        detection rows the heads read."""
         B, _, Hh, Ww = pixels.shape
         pe, mid = self.position_embeddings((Hh, Ww))
         nd = self.c.num_detection_tokens
@@ -228,6 +233,12 @@ class YolosSmall(nn.Module):
         else:
             for i, blk in enumerate(self.blocks):
                 x = blk(x, mid[i] if mid is not None and i < self.c.num_layers - 1 else None)
+        return x
+
+    def detect(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(logits, boxes)`` from :meth:`encode`'s tokens: ``ln_f`` and the two MLP heads on the
+        detection rows."""
+        hip = x.shape[0] == 1 and x.is_cuda and K.get_backend() == "hip"
         det = x[:, -self.c.num_detection_tokens:, :]
         if hip and x.is_contiguous() and self.heads_fusable():
             # final LayerNorm + both MLP heads in three launches (csrc/head.hip)
