@@ -26,6 +26,7 @@
 #include "epilogue.h"
 #include "pin.h"
 #include "streamk.h"
+#include "x3_schedule.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -38,36 +39,6 @@ enum : int { EPI_NONE = 0, EPI_BIAS = 1, EPI_GELU = 2, EPI_RES = 4, EPI_RES2 = 8
 constexpr int BK = 32, LSTR = 40;
 
 __device__ __forceinline__ int acc_row(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
-
-// Logical tile order: xcd_major_n (pin.h) deals workgroups round-robin over the XCDs (phys % nx =
-// XCD, observed placement — speed only, never correctness), so XCD x gets a contiguous logical range:
-// a band of whole tile rows whose A rows stay in that XCD's L2 while it sweeps the weight columns.
-
-// Persistent grids: workgroup w's tiles are base + i*stride, i < count — the XCD's band again, dealt
-// over the XCD's P/nx workgroups (nx XCDs: 8, or the pinned partition's; P % nx == 0, otherwise a
-// plain w + i*P sweep).
-__device__ __forceinline__ void xcd_band(int w, int P, int nx, int tiles, int& base, int& stride, int& count) {
-  if (P % nx) {
-    base = w, stride = P, count = w < tiles ? (tiles - w + P - 1) / P : 0;
-    return;
-  }
-  const int x = w % nx, li = w / nx, px = P / nx, q = tiles / nx, r = tiles % nx;
-  const int n = q + (x < r ? 1 : 0);
-  base = x * q + min(x, r) + li, stride = px, count = li < n ? (n - li + px - 1) / px : 0;
-}
-
-// Grouped tile order: logical tile t walks GROUP tile rows down a column before moving right, so
-// the tiles an XCD runs at once cover GROUP rows x (its workgroups / GROUP) columns — A and W
-// slices that fit its 4 MB L2 together — instead of one row of tiles sweeping all of W. GROUP
-// rides in bits 8-15 of the epilogue word (1 = plain row-major order).
-__device__ __forceinline__ void tile_rc(int t, int tiles_m, int tiles_n, int group, int& mt, int& nt) {
-  if (group <= 1) {
-    mt = t / tiles_n, nt = t % tiles_n;
-    return;
-  }
-  const int per = group * tiles_n, g = t / per, r0 = g * group, gs = min(tiles_m - r0, group), o = t - g * per;
-  mt = r0 + o % gs, nt = o / gs;
-}
 
 __device__ __forceinline__ f32x16 mfma_x3(const bf16x8& a0, const bf16x8& a1, const bf16x8& a2, const bf16x8& b0,
                                           const bf16x8& b1, const bf16x8& b2, f32x16 d) {
@@ -237,10 +208,8 @@ __global__ __launch_bounds__(256, 2) void gemm_x3(const __bf16* __restrict__ A, 
   epi &= 0xff;
   if (pb.id < 0) return;
   const int tiles_n = N / BN, tiles_m = (M + BM - 1) / BM;
-  const int tiles = tiles_m * tiles_n;
-  const int t = xcd_major_n(pb.id, pb.n, pb.nx);
-  if (t >= tiles) return;
-  int mt, nt;
+  int t, sp, mt, nt;
+  if (!x3_unit(pb.id, pb.n, pb.nx, tiles_m * tiles_n, 1, t, sp)) return;
   tile_rc(t, tiles_m, tiles_n, group, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
 
@@ -562,15 +531,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void gemm_x3d(const __bf16* __re
   epi &= 0xff;
   if (pb.id < 0) return;
   const int tiles_n = N / BN, tiles_m = (M + BM - 1) / BM;
-  const int tiles = tiles_m * tiles_n;
   // split-K partials (splits > 1): unit = (tile, split), a tile's splits adjacent (one XCD's L2);
   // split sp sums K stages [sp*nk/splits, (sp+1)*nk/splits) into fp32 plane sp of C [splits][M][N]
   // with no epilogue — the consumer (splitk_layernorm) adds the planes, bias and residuals
-  const int u = xcd_major_n(pb.id, pb.n, pb.nx);
-  if (u >= tiles * splits) return;
-  const int t = u / splits, sp = u - t * splits;
+  int t, sp, mt, nt;
+  if (!x3_unit(pb.id, pb.n, pb.nx, tiles_m * tiles_n, splits, t, sp)) return;
   if (splits > 1) C += size_t(sp) * M * N;
-  int mt, nt;
   tile_rc(t, tiles_m, tiles_n, group, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
 
@@ -804,7 +770,7 @@ int launch_s(const __bf16* A, size_t ap, const __bf16* W, size_t wp, const float
     return -1;
   }
   const int tiles = ((M + BM - 1) / BM) * (N / BN);
-  const int g = std::max(1, std::min(grid, tiles));
+  const int g = x3s_grid(grid, tiles);
   hipLaunchKernelGGL((gemm_x3s<BM, BN, WGM, WGN, S, BKS>), dim3(pinned_grid(g, unsigned(epi >> 20) & 0xffu)),
                      dim3(64 * WGM * WGN), 0, s, A, ap, W, wp, bias, R, R2,
                      r2_rows, C, Cp, cp, M, N, K, epi);
@@ -871,12 +837,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void gemm_x3t(const __bf16* __re
   epi &= 0xff;
   if (pb.id < 0) return;
   const int tiles_n = N / BN, tiles_m = (M + BM - 1) / BM;
-  const int tiles = tiles_m * tiles_n;
-  const int u = xcd_major_n(pb.id, pb.n, pb.nx);
-  if (u >= tiles * splits) return;
-  const int t = u / splits, sp = u - t * splits;
+  int t, sp, mt, nt;
+  if (!x3_unit(pb.id, pb.n, pb.nx, tiles_m * tiles_n, splits, t, sp)) return;
   if (splits > 1) C += size_t(sp) * M * N;
-  int mt, nt;
   tile_rc(t, tiles_m, tiles_n, group, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
 
@@ -1005,12 +968,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void gemm_x3a(const float* __res
   epi &= 0xff;
   if (pb.id < 0) return;
   const int tiles_n = N / BN, tiles_m = (M + BM - 1) / BM;
-  const int tiles = tiles_m * tiles_n;
-  const int u = xcd_major_n(pb.id, pb.n, pb.nx);
-  if (u >= tiles * splits) return;
-  const int t = u / splits, sp = u - t * splits;
+  int t, sp, mt, nt;
+  if (!x3_unit(pb.id, pb.n, pb.nx, tiles_m * tiles_n, splits, t, sp)) return;
   if (splits > 1) C += size_t(sp) * M * N;
-  int mt, nt;
   tile_rc(t, tiles_m, tiles_n, group, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
 
@@ -1260,6 +1220,51 @@ int nos_gemm_x3_set_group(int g) {
     return -1;
   }
   g_group_m = g;
+  return 0;
+}
+
+// The tile schedule of a launch over tiles_m x tiles_n tiles, walked on the host with the kernels'
+// own functions (x3_schedule.h, pin.h). persistent != 0: gemm_x3s asked for `grid` workgroups
+// (clamped as launch_s clamps it); otherwise one unit = (tile, split) per workgroup and `grid` is
+// not used. hdr = {P logical workgroups, nx XCDs they are dealt over, units the launch must cover,
+// physical grid, units the schedule runs}; wg[3w..] = {count, base, stride} of logical workgroup w
+// (w < P <= wg_cap); units[4i..] = {logical tile, mt, nt, split} in workgroup order, each
+// workgroup's in stream order (the first unit_cap of them).
+int nos_gemm_x3_schedule(int tiles_m, int tiles_n, int group, int grid, unsigned pin, int persistent, int splits,
+                         int* hdr, int* wg, int wg_cap, int* units, int unit_cap) {
+  if (tiles_m < 1 || tiles_n < 1 || tiles_m > (1 << 20) / tiles_n || group < 1 || group > 255 || pin > 0xffu ||
+      splits < 1 || splits > 8 || (persistent && splits != 1) || !hdr || !wg || !units) {
+    g_err = "gemm_x3 schedule: tiles >= 1 (at most 2^20), group 1..255, an 8-bit pin, splits 1..8 (1 if persistent)";
+    return -1;
+  }
+  const int tiles = tiles_m * tiles_n, want = tiles * splits;
+  const unsigned phys = pinned_grid(unsigned(persistent ? x3s_grid(grid, tiles) : want), pin);
+  const int nx = pin ? __builtin_popcount(pin) : 8, P = pin ? pinned_n(phys, nx) : int(phys);
+  if (P > wg_cap) {
+    g_err = "gemm_x3 schedule: " + std::to_string(P) + " workgroups do not fit wg_cap";
+    return -1;
+  }
+  int n = 0;
+  auto put = [&](int t, int mt, int nt, int sp) {
+    if (n < unit_cap) units[4 * n] = t, units[4 * n + 1] = mt, units[4 * n + 2] = nt, units[4 * n + 3] = sp;
+    ++n;
+  };
+  for (int w = 0; w < P; ++w) {
+    int base = 0, stride = 0, count = 0, mt = 0, nt = 0, sp = 0;
+    if (persistent) {
+      xcd_band(w, P, nx, tiles, base, stride, count);
+      for (int i = 0; i < count; ++i) {
+        tile_rc(base + i * stride, tiles_m, tiles_n, group, mt, nt);
+        put(base + i * stride, mt, nt, 0);
+      }
+    } else if (int t = 0; x3_unit(w, P, nx, tiles, splits, t, sp)) {
+      tile_rc(t, tiles_m, tiles_n, group, mt, nt);
+      base = xcd_major_n(w, P, nx), count = 1;
+      put(t, mt, nt, sp);
+    }
+    wg[3 * w] = count, wg[3 * w + 1] = base, wg[3 * w + 2] = stride;
+  }
+  hdr[0] = P, hdr[1] = nx, hdr[2] = want, hdr[3] = int(phys), hdr[4] = n;
   return 0;
 }
 

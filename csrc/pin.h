@@ -22,6 +22,9 @@ struct PinnedBlock {
   int nx;  // XCDs the logical blocks are dealt over (8 unpinned)
 };
 
+// logical blocks of a pinned launch of `phys` physical ones over nx XCDs
+__host__ __device__ __forceinline__ int pinned_n(unsigned phys, int nx) { return int(phys / 8) * nx; }
+
 __device__ __forceinline__ int xcc_id() { return int(__builtin_amdgcn_s_getreg(20 | (31 << 11)) & 15); }
 
 __device__ __forceinline__ PinnedBlock pinned_block(unsigned pin) {
@@ -29,12 +32,12 @@ __device__ __forceinline__ PinnedBlock pinned_block(unsigned pin) {
   const unsigned x = unsigned(xcc_id());
   const int nx = __builtin_popcount(pin);
   if (!((pin >> x) & 1u)) return {-1, 0, nx};
-  return {int(blockIdx.x / 8) * nx + __builtin_popcount(pin & ((1u << x) - 1u)), int(gridDim.x / 8) * nx, nx};
+  return {int(blockIdx.x / 8) * nx + __builtin_popcount(pin & ((1u << x) - 1u)), pinned_n(gridDim.x, nx), nx};
 }
 
 // Logical block `phys` of n dealt round-robin over nx XCDs (phys % nx = XCD): XCD x gets the
 // contiguous logical range starting at x*(n/nx) + min(x, n%nx). A bijection on [0, n) for every n.
-__device__ __forceinline__ int xcd_major_n(int phys, int n, int nx) {
+__host__ __device__ __forceinline__ int xcd_major_n(int phys, int n, int nx) {
   const int x = phys % nx, q = n / nx, r = n % nx;
   return x * q + min(x, r) + phys / nx;
 }

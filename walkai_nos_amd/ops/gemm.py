@@ -281,6 +281,35 @@ def set_group_m(g: int) -> None:
         raise ValueError(L.nos_gemm_x3_last_error().decode())
 
 
+def x3_schedule(tiles_m: int, tiles_n: int, group: int = 1, grid: int = 0, pin: int = 0, persistent: bool = True,
+                splits: int = 1, lib: Optional[ctypes.CDLL] = None) -> dict:
+    """The tile schedule a launch over ``tiles_m x tiles_n`` tiles would use, walked on the host by
+    the library with the kernels' own functions (``nos_gemm_x3_schedule``, ``csrc/x3_schedule.h``).
+    ``persistent``: the stream-of-stages kernel asked for ``grid`` workgroups; otherwise one
+    (tile, split) unit per workgroup. Returns ``P`` (logical workgroups), ``nx`` (XCDs they are dealt
+    over), ``want`` (units to cover), ``phys`` (physical grid), ``wg`` (per logical workgroup
+    ``(count, base, stride)``) and ``units`` (per workgroup the ordered ``(tile, mt, nt, split)``)."""
+    L = lib if lib is not None else _lib_x3()
+    i32, vp = ctypes.c_int, ctypes.c_void_p
+    L.nos_gemm_x3_schedule.argtypes = [i32, i32, i32, i32, ctypes.c_uint, i32, i32, vp, vp, i32, vp, i32]
+    L.nos_gemm_x3_last_error.restype = ctypes.c_char_p
+    want = tiles_m * tiles_n * splits
+    wg_cap, unit_cap = max(int(grid), want, 1) + 8, 2 * want + 16
+    hdr, wg, units = (i32 * 5)(), (i32 * (3 * wg_cap))(), (i32 * (4 * unit_cap))()
+    if L.nos_gemm_x3_schedule(tiles_m, tiles_n, group, grid, pin, int(bool(persistent)), splits, hdr, wg, wg_cap,
+                              units, unit_cap) != 0:
+        raise ValueError(L.nos_gemm_x3_last_error().decode())
+    P, nx, want, phys, ran = hdr
+    if ran > unit_cap:
+        raise ValueError(f"x3 schedule: {ran} units for {want} (more than twice over)")
+    per_wg, flat, at = [], list(units[:4 * ran]), 0
+    wgs = [tuple(wg[3 * w:3 * w + 3]) for w in range(P)]
+    for count, _, _ in wgs:
+        per_wg.append([tuple(flat[4 * i:4 * i + 4]) for i in range(at, at + max(count, 0))])
+        at += max(count, 0)
+    return {"P": P, "nx": nx, "want": want, "phys": phys, "ran": ran, "wg": wgs, "units": per_wg}
+
+
 def weight_planes(w: torch.Tensor) -> torch.Tensor:
     """x3 planes of a weight, split once and cached ON the weight tensor (its view base, for a view
     such as the patch embedding's reshaped kernel) and re-split when the weight is modified in
