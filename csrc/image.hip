@@ -1,0 +1,286 @@
+// The image half of the workload (YOLOS-small): the pixels in front of the model and the detections
+// behind it, each as one launch with no host synchronisation.
+//
+//  * image_patch_planes_u8 — a uint8 RGB image [B][h][w][3] straight to the patch-embedding GEMM's
+//    operand: separable antialiased triangle resample to H x W (tap tables built on the host in fp64
+//    and read as constants), the per-channel affine v * a_c + b_c, and the exact x3 split into the
+//    three bf16 planes [3][B*gh*gw][3*p*p] of the patch matrix (row (b, i, j), column (c, u, v), as
+//    patch_planes_f32 in head.hip); optionally the fp32 pixels [B][3][H][W] as well. One 256-thread
+//    workgroup per p x p patch: the patch's source footprint is staged in LDS with aligned 4-byte
+//    loads, resampled horizontally into an fp32 LDS tile, then vertically by thread (u, v).
+//  * detections_f32 — softmax over the class logits, the best of the first L classes, the box in
+//    corner format scaled to the original image, and a stable compaction of the rows above the
+//    threshold; one workgroup per image, one wave per row.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+namespace {
+thread_local std::string g_err;
+
+// TAPS: weights per output row / column (scale <= 4: 2 * 4 + 1); PMAX: patch side; FMAX: rows and
+// columns of a patch's source footprint, at most scale * (p + 1) + 1 = 69 at scale 4 and p = 16
+// (the host passes the largest footprint of the tables and it is checked against FMAX).
+constexpr int TAPS = 9, PMAX = 16, FMAX = 72;
+// a footprint row in LDS: the global row's bytes at its own alignment (0-3 bytes of lead-in), whole dwords
+constexpr int NDW = (FMAX * 3 + 3 + 3) / 4, RS = NDW * 4;
+constexpr int MMAX = 1024, CMAX = 128;
+// the detections workgroup: 16 waves, so the 100 rows of YOLOS are 7 dependent row passes, not 25
+constexpr int DT = 1024, DW = DT / 64;
+
+struct ImgArgs {
+  const uint8_t* img;   // [B][h][w][3]
+  __bf16* planes;       // [3][B*gh*gw][3*p*p]
+  float* pixels;        // [B][3][H][W] or null
+  const int* yidx;      // [2][H]: first source row, tap count
+  const float* ywt;     // [H][TAPS]
+  const int* xidx;      // [2][W]
+  const float* xwt;     // [W][TAPS]
+  float a[3], b[3];
+  int B, h, w, H, W, p, gh, gw, GH, GW;  // GH x GW: the tiles that cover H x W (>= gh x gw)
+};
+
+__global__ __launch_bounds__(256) void image_patch_planes_u8(ImgArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t src[FMAX * RS];
+  __shared__ float hz[FMAX * PMAX * 3];  // [footprint row][v][c]: the horizontally resampled rows
+  __shared__ float wxs[PMAX * TAPS], wys[PMAX * TAPS];
+  __shared__ int xf[PMAX], xc[PMAX], yf[PMAX], yc[PMAX];
+  const int tid = threadIdx.x, p = a.p, H = a.H, W = a.W;
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(a.img), hi = lo + size_t(a.B) * a.h * a.w * 3;
+  const int tiles = a.B * a.GH * a.GW;
+  const size_t ck = size_t(3) * p * p, plane = size_t(a.B) * a.gh * a.gw * ck;
+  for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int b = t / (a.GH * a.GW), ij = t % (a.GH * a.GW), i = ij / a.GW, j = ij % a.GW;
+    const int y0 = i * p, x0 = j * p, ny = min(p, H - y0), nx = min(p, W - x0);
+    // the footprint: first source row / column of the first output, one past the last of the last
+    // (both ends grow with the output index)
+    const int fy0 = a.yidx[y0], fy1 = a.yidx[y0 + ny - 1] + a.yidx[H + y0 + ny - 1];
+    const int fx0 = a.xidx[x0], fx1 = a.xidx[x0 + nx - 1] + a.xidx[W + x0 + nx - 1];
+    const int fh = fy1 - fy0, fw = fx1 - fx0;
+    // the host checked the tables against these limits; a table that breaks them reads nothing
+    if (fy0 < 0 || fx0 < 0 || fy1 > a.h || fx1 > a.w || fh <= 0 || fw <= 0 || fh > FMAX || fw > FMAX) continue;
+    __syncthreads();  // the previous tile's readers are done with the LDS
+    if (tid < ny * TAPS) wys[tid] = a.ywt[size_t(y0) * TAPS + tid];
+    if (tid < nx * TAPS) wxs[tid] = a.xwt[size_t(x0) * TAPS + tid];
+    if (tid < ny) {
+      yf[tid] = min(max(a.yidx[y0 + tid] - fy0, 0), fh - 1);
+      yc[tid] = min(min(a.yidx[H + y0 + tid], TAPS), fh - yf[tid]);
+    }
+    if (tid < nx) {
+      xf[tid] = min(max(a.xidx[x0 + tid] - fx0, 0), fw - 1);
+      xc[tid] = min(min(a.xidx[W + x0 + tid], TAPS), fw - xf[tid]);
+    }
+    // stage the footprint: aligned dwords of each global row (the row's own alignment kept in LDS)
+    const int rowbytes = fw * 3;
+    for (int e = tid; e < fh * NDW; e += 256) {
+      const int r = e / NDW, d = e % NDW;
+      const uintptr_t addr = lo + ((size_t(b) * a.h + fy0 + r) * a.w + fx0) * 3;
+      const int sh = int(addr & 3);
+      if (d * 4 >= sh + rowbytes) continue;
+      const uintptr_t q = addr - sh + size_t(d) * 4;
+      uint32_t v = 0;
+      if (q >= lo && q + 4 <= hi) {
+        v = *reinterpret_cast<const uint32_t*>(q);
+      } else {  // the dword that straddles an end of the image: its bytes inside, one by one
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (q + k >= lo && q + k < hi) v |= uint32_t(*reinterpret_cast<const uint8_t*>(q + k)) << (8 * k);
+      }
+      *reinterpret_cast<uint32_t*>(src + r * RS + d * 4) = v;
+    }
+    __syncthreads();
+    // horizontal pass: (footprint row r, output column v, channel c), taps in ascending order
+    for (int e = tid; e < fh * PMAX * 3; e += 256) {
+      const int c = e % 3, v = (e / 3) % PMAX, r = e / (3 * PMAX);
+      if (v >= nx) continue;
+      const uintptr_t addr = lo + ((size_t(b) * a.h + fy0 + r) * a.w + fx0) * 3;
+      const uint8_t* s = src + r * RS + int(addr & 3) + xf[v] * 3 + c;
+      const float* wt = wxs + v * TAPS;
+      float acc = 0.f;
+      for (int k = 0; k < xc[v]; ++k) acc = fmaf(wt[k], float(s[k * 3]), acc);
+      hz[e] = acc;
+    }
+    __syncthreads();
+    // vertical pass, affine, split and store: thread (u, v), three channels
+    const bool in_grid = i < a.gh && j < a.gw;
+    const size_t row = (size_t(b) * a.gh + i) * a.gw + j;
+    for (int e = tid; e < p * p; e += 256) {
+      const int u = e / p, v = e % p;
+      if (u >= ny || v >= nx) continue;
+      const float* wt = wys + u * TAPS;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float* hcol = hz + (yf[u] * PMAX + v) * 3 + c;
+        float acc = 0.f;
+        for (int k = 0; k < yc[u]; ++k) acc = fmaf(wt[k], hcol[k * PMAX * 3], acc);
+        const float val = fmaf(acc, a.a[c], a.b[c]);
+        if (a.pixels != nullptr) a.pixels[((size_t(b) * 3 + c) * H + y0 + u) * W + x0 + v] = val;
+        if (in_grid) {
+          const __bf16 h0 = (__bf16)val;
+          const float r1 = val - (float)h0;
+          const __bf16 h1 = (__bf16)r1;
+          const __bf16 h2 = (__bf16)(r1 - (float)h1);
+          const size_t o = row * ck + size_t(c) * p * p + e;
+          a.planes[o] = h0;
+          a.planes[plane + o] = h1;
+          a.planes[2 * plane + o] = h2;
+        }
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+
+// logits [B][M][C] (C = L + 1, the last class "no object"), boxes [B][M][4] (cx, cy, w, h in 0..1),
+// target [B][2] (height, width) -> the rows with score > thr, in row order, at the front of
+// scores / labels / out_boxes [B][M](x4), zeros behind them, and their number in count [B]
+__global__ __launch_bounds__(DT) void detections_f32(const float* __restrict__ logits, const float* __restrict__ boxes,
+                                                      const float* __restrict__ target, float thr, int M, int C,
+                                                      float* __restrict__ scores, int* __restrict__ labels,
+                                                      float* __restrict__ out_boxes, int* __restrict__ count) {
+  __shared__ float s_score[MMAX];
+  __shared__ int s_label[MMAX];
+  __shared__ int s_wave[DW];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, L = C - 1;
+  for (int row = wave; row < M; row += DW) {
+    const float* x = logits + (size_t(b) * M + row) * C;
+    const float x0 = lane < C ? x[lane] : -INFINITY, x1 = lane + 64 < C ? x[lane + 64] : -INFINITY;
+    const float m = wave_max(fmaxf(x0, x1));
+    const float e0 = lane < C ? expf(x0 - m) : 0.f, e1 = lane + 64 < C ? expf(x1 - m) : 0.f;
+    const float sum = wave_sum(e0 + e1);
+    // the largest probability of the first L classes, the lowest index on ties
+    float best = lane < L ? e0 / sum : -1.f;
+    int idx = lane;
+    const float p1 = lane + 64 < L ? e1 / sum : -1.f;
+    if (p1 > best) best = p1, idx = lane + 64;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ob = __shfl_xor(best, o);
+      const int oi = __shfl_xor(idx, o);
+      if (ob > best || (ob == best && oi < idx)) best = ob, idx = oi;
+    }
+    if (lane == 0) {
+      s_score[row] = best;
+      s_label[row] = idx;
+    }
+  }
+  __syncthreads();
+  const float th = target[2 * b], tw = target[2 * b + 1];
+  int base = 0;  // kept rows so far: the same in every thread
+  for (int r0 = 0; r0 < M; r0 += DT) {
+    const int row = r0 + tid;
+    const bool keep = row < M && s_score[row] > thr;
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) s_wave[wave] = __popcll(mask);
+    __syncthreads();
+    int off = base;
+    for (int k = 0; k < wave; ++k) off += s_wave[k];
+    if (keep) {
+      const size_t slot = size_t(b) * M + off + __popcll(mask & ((1ull << lane) - 1ull));
+      const float* bx = boxes + (size_t(b) * M + row) * 4;
+      const float cx = bx[0], cy = bx[1], hw = 0.5f * bx[2], hh = 0.5f * bx[3];
+      scores[slot] = s_score[row];
+      labels[slot] = s_label[row];
+      out_boxes[slot * 4 + 0] = (cx - hw) * tw;
+      out_boxes[slot * 4 + 1] = (cy - hh) * th;
+      out_boxes[slot * 4 + 2] = (cx + hw) * tw;
+      out_boxes[slot * 4 + 3] = (cy + hh) * th;
+    }
+    for (int k = 0; k < DW; ++k) base += s_wave[k];
+    __syncthreads();  // s_wave is rewritten by the next chunk
+  }
+  for (int k = base + tid; k < M; k += DT) {
+    const size_t slot = size_t(b) * M + k;
+    scores[slot] = 0.f;
+    labels[slot] = 0;
+    out_boxes[slot * 4 + 0] = 0.f;
+    out_boxes[slot * 4 + 1] = 0.f;
+    out_boxes[slot * 4 + 2] = 0.f;
+    out_boxes[slot * 4 + 3] = 0.f;
+  }
+  if (tid == 0) count[b] = base;
+}
+
+int check(const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    g_err = std::string(what) + ": " + hipGetErrorString(e);
+    return int(e);
+  }
+  return 0;
+}
+
+int fail(const char* msg) {
+  g_err = msg;
+  return -1;
+}
+}  // namespace
+
+extern "C" {
+
+const char* nos_image_last_error() { return g_err.c_str(); }
+
+int nos_image_taps() { return TAPS; }
+int nos_image_max_footprint() { return FMAX; }
+int nos_image_max_patch() { return PMAX; }
+
+// img [B][h][w][3] uint8 -> planes [3][B*gh*gw][3*p*p] bf16 (and pixels [B][3][H][W] fp32 when
+// non-null). yidx [2][H] / xidx [2][W] (first source index, tap count) and ywt [H][taps] / xwt
+// [W][taps] are device tables; ytab / xtab are their row counts, max_fh / max_fw the largest source
+// footprint of one patch row / column of those tables (the host built them, so it knows). a, b:
+// host arrays of the three per-channel affine constants. wgs: workgroups (0 = one per tile).
+int nos_image_patch_planes_u8(const void* img, void* planes, float* pixels, const int* yidx, const float* ywt,
+                              const int* xidx, const float* xwt, int ytab, int xtab, int taps, int max_fh, int max_fw,
+                              const float* a, const float* b, int B, int h, int w, int H, int W, int p, int gh, int gw,
+                              int wgs, void* stream) {
+  if (!img || !planes || !yidx || !ywt || !xidx || !xwt || !a || !b) return fail("image_patch_planes: null operand");
+  if (B <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return fail("image_patch_planes: B, h, w, H, W must be positive");
+  if (p < 2 || p % 2 || p > PMAX) return fail("image_patch_planes: patch side must be even and at most 16");
+  if (gh <= 0 || gw <= 0 || size_t(gh) * p > size_t(H) || size_t(gw) * p > size_t(W))
+    return fail("image_patch_planes: whole patches inside the resized image (gh * p <= H, gw * p <= W)");
+  if (taps != TAPS || ytab != H || xtab != W) return fail("image_patch_planes: tap tables must be [H][9] and [W][9]");
+  if (max_fh <= 0 || max_fw <= 0 || max_fh > FMAX || max_fw > FMAX || max_fh > h || max_fw > w)
+    return fail("image_patch_planes: a patch's source footprint exceeds 72 rows or columns (scale above 4)");
+  ImgArgs k{};
+  k.img = static_cast<const uint8_t*>(img);
+  k.planes = static_cast<__bf16*>(planes);
+  k.pixels = pixels;
+  k.yidx = yidx, k.ywt = ywt, k.xidx = xidx, k.xwt = xwt;
+  for (int c = 0; c < 3; ++c) k.a[c] = a[c], k.b[c] = b[c];
+  k.B = B, k.h = h, k.w = w, k.H = H, k.W = W, k.p = p, k.gh = gh, k.gw = gw;
+  // with pixels every tile that covers H x W is computed; without, only the patch grid
+  k.GH = pixels ? (H + p - 1) / p : gh;
+  k.GW = pixels ? (W + p - 1) / p : gw;
+  const size_t tiles = size_t(B) * k.GH * k.GW;
+  if (tiles > size_t(1) << 30) return fail("image_patch_planes: too many patches");
+  const int grid = int(wgs > 0 && size_t(wgs) < tiles ? size_t(wgs) : tiles);
+  hipLaunchKernelGGL(image_patch_planes_u8, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k);
+  return check("image_patch_planes_u8");
+}
+
+// logits [B][M][C] fp32, boxes [B][M][4] fp32, target [B][2] fp32 (height, width), all on the device ->
+// count [B] int32, scores [B][M] fp32, labels [B][M] int32, out_boxes [B][M][4] fp32
+int nos_detections_f32(const float* logits, const float* boxes, const float* target, float threshold, int B, int M,
+                       int C, int* count, float* scores, int* labels, float* out_boxes, void* stream) {
+  if (!logits || !boxes || !target || !count || !scores || !labels || !out_boxes)
+    return fail("detections: null operand");
+  if (B <= 0 || M <= 0 || M > MMAX || C < 2 || C > CMAX)
+    return fail("detections: B > 0, 0 < M <= 1024, 2 <= classes (with \"no object\") <= 128");
+  hipLaunchKernelGGL(detections_f32, dim3(B), dim3(DT), 0, reinterpret_cast<hipStream_t>(stream), logits, boxes,
+                     target, threshold, M, C, scores, labels, out_boxes, count);
+  return check("detections_f32");
+}
+
+}  // extern "C"

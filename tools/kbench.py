@@ -7,6 +7,12 @@ Reports microseconds per call and achieved TFLOP/s for: attention (unsplit one-w
 baseline, stream-K LDS-shared workgroup kernel, stream-K one-wave kernel with 2 and 3
 resident waves/SIMD, PyTorch SDPA), and the four fp32 GEMMs of a
 layer (hipBLASLt via torch).
+
+``--only image`` times the image pipeline instead (``csrc/image.hip``) on SPX- and CPX-sized slices:
+the fused uint8 -> patch-planes kernel against the torch composition on the same GPU (``.float()``,
+antialiased ``F.interpolate``, the affine, ``K.patch_planes``), the detections kernel against the
+torch composition of the post-process, and ``detect_image`` against ``forward`` alone; the two sides
+of each pair alternate within the run and the median of the rounds is reported.
 """
 from __future__ import annotations
 
@@ -53,7 +59,7 @@ def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default="gpurun_out/kbench.json")
-    ap.add_argument("--only", choices=("all", "attn", "gemm", "model", "modes"), default="all")
+    ap.add_argument("--only", choices=("all", "attn", "gemm", "model", "modes", "image"), default="all")
     ap.add_argument("--slices", default="spx,dpx,qpx,cpx")
     ap.add_argument("--partitions", type=int, default=0, help="modes: run only this many partitions of each mode")
     ap.add_argument("--free-s", type=float, default=0.0,
@@ -67,6 +73,8 @@ def main() -> int:
     torch.manual_seed(0)
     if a.only == "modes":
         return modes_bench(a)
+    if a.only == "image":
+        return image_bench(a)
     qkv = torch.randn(1, T, 3 * D, device="cuda")
     out = torch.empty(1, T, D, device="cuda")
     x = torch.randn(T, D, device="cuda")
@@ -191,6 +199,75 @@ def modes_bench(a) -> int:
         for sl in slots:
             sl.close()
         torch.cuda.synchronize()
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(results, f, indent=1)
+    return 0
+
+
+def image_bench(a) -> int:
+    """The image pipeline per slice: microseconds per call, fused kernel and torch composition
+    interleaved (``rounds`` alternations, the median of each)."""
+    import statistics
+
+    import torch.nn.functional as F
+
+    from walkai_nos_amd.models.workload.processor import IMAGENET_MEAN, IMAGENET_STD
+    from walkai_nos_amd.models.workload.yolos import YolosSmall
+    from walkai_nos_amd.ops import image as I
+    out_hw, rounds = (800, 1056), 3
+    ca, cb = I.affine(IMAGENET_MEAN, IMAGENET_STD)
+    ca, cb = torch.tensor(ca, device="cuda").view(1, 3, 1, 1), torch.tensor(cb, device="cuda").view(1, 3, 1, 1)
+    g = torch.Generator().manual_seed(0)
+    imgs = {f"{h}x{w}": torch.randint(0, 256, (1, h, w, 3), generator=g, dtype=torch.uint8).cuda()
+            for h, w in ((480, 640), (3024, 4032))}
+    logits, boxes = 3.0 * torch.randn(1, 100, 92, device="cuda"), 0.2 + 0.6 * torch.rand(1, 100, 4, device="cuda")
+    target = torch.tensor([[480.0, 640.0]], device="cuda")
+
+    def torch_planes(img):
+        x = F.interpolate(img.permute(0, 3, 1, 2).float(), size=out_hw, mode="bilinear", antialias=True,
+                          align_corners=False)
+        return K.patch_planes(x * ca + cb, 16)
+
+    def pair(r, name, fused, composed, s, iters):
+        t = {"hip": [], "torch": []}
+        for _ in range(rounds):
+            t["hip"].append(timeit(fused, s, iters))
+            t["torch"].append(timeit(composed, s, iters))
+        r[f"{name}_hip_us"] = round(statistics.median(t["hip"]), 1)
+        r[f"{name}_torch_us"] = round(statistics.median(t["torch"]), 1)
+        r[f"{name}_rounds_us"] = {k: [round(v, 1) for v in vs] for k, vs in t.items()}
+
+    results = []
+    for prof, label in (("spx_nps1", "spx"), ("cpx_nps1", "cpx")):
+        if label not in a.slices.split(","):
+            continue
+        cus = slice_cus(prof, 0)
+        n = 256 if cus is None else len(cus)
+        with Stream(0, cus) as hs:
+            s = hs.torch_stream()
+            K.set_slice_cus(n)
+            r = {"slice": label, "cus": n, "target_hw": list(out_hw), "iters": a.iters, "rounds": rounds}
+            for name, img in imgs.items():
+                pair(r, f"preprocess_{name}", lambda: I.image_patch_planes(img, out_hw, 16, IMAGENET_MEAN, IMAGENET_STD),
+                     lambda: torch_planes(img), s, a.iters)
+            pair(r, "detections", lambda: I.detections(logits, boxes, target, 0.5),
+                 lambda: I.detections_reference(logits, boxes, target, 0.5), s, a.iters)
+            with torch.cuda.stream(s), torch.no_grad():
+                m = YolosSmall().cuda().eval()
+                img = imgs["480x640"][0]
+                px = m.processor.preprocess(img)
+                it = max(3, a.iters // 4)
+                t = {"detect_image": [], "forward": []}
+                for _ in range(rounds):
+                    t["detect_image"].append(timeit(lambda: m.detect_image(img), s, it))
+                    t["forward"].append(timeit(lambda: m(px), s, it))
+            r["detect_image_ms"] = round(statistics.median(t["detect_image"]) / 1000.0, 3)
+            r["forward_ms"] = round(statistics.median(t["forward"]) / 1000.0, 3)
+            r["model_rounds_ms"] = {k: [round(v / 1000.0, 3) for v in vs] for k, vs in t.items()}
+            print(json.dumps(r), flush=True)
+            results.append(r)
+    K.set_slice_cus(None)
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(results, f, indent=1)

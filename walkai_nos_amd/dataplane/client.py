@@ -11,6 +11,11 @@ the reference's loop — until ``epoch + seconds``.  A workgroup census (which p
 process's kernels run on) is taken while every pod is busy.  It prints one JSON line and exits.
 
     python -m walkai_nos_amd.dataplane.client --seconds 10 [--no-graph] [--census]
+
+``--end-to-end`` makes one inference what a pod that is handed a photo does: a uint8 image (seeded,
+synthetic, ``--image-hw``) through the fused preprocess, the model and the detections kernel
+(``YolosSmall.detect_image``), all inside the warm-up and the captured graph; the JSON line then
+carries ``"end_to_end": true`` and ``"detections"``, the number of boxes above ``--threshold``.
 """
 from __future__ import annotations
 
@@ -60,6 +65,11 @@ def main(argv=None) -> int:
     ap.add_argument("--hw", default="800,1066")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("NOS_POD_STREAMS", "1")),
                     help="HIP streams the inference loop rotates over (one inference at a time)")
+    ap.add_argument("--end-to-end", action="store_true",
+                    help="time image in, detections out (uint8 image -> preprocess -> model -> post-process)")
+    ap.add_argument("--image-hw", default="480,640", help="--end-to-end: the synthetic source image's height,width")
+    ap.add_argument("--size", default="800,1333", help="--end-to-end: the processor's shortest,longest edge")
+    ap.add_argument("--threshold", type=float, default=0.5, help="--end-to-end: detection score threshold")
     args = ap.parse_args(argv)
     t_boot = time.perf_counter()
     import torch
@@ -70,7 +80,23 @@ def main(argv=None) -> int:
     hw = tuple(int(x) for x in args.hw.split(","))
     dev = "cuda:0"
     model = YolosSmall().to(dev).eval()
-    x = demo_input(1, hw, dev, seed=int(os.environ.get("NOS_POD_SEED", "0")))
+    seed = int(os.environ.get("NOS_POD_SEED", "0"))
+    if args.end_to_end:
+        from ..models.workload.processor import YolosProcessor
+        ih, iw = (int(v) for v in args.image_hw.split(","))
+        shortest, longest = (int(v) for v in args.size.split(","))
+        model.processor = YolosProcessor(shortest, longest, patch=model.c.patch_size)
+        img = torch.randint(0, 256, (ih, iw, 3), generator=torch.Generator().manual_seed(seed),
+                            dtype=torch.uint8).to(dev)
+        hw = model.processor.size((ih, iw))
+
+        def infer():
+            return model.detect_image(img, args.threshold)
+    else:
+        x = demo_input(1, hw, dev, seed=seed)
+
+        def infer():
+            return model(x)
     streams = [torch.cuda.Stream() for _ in range(max(1, args.streams))]
     if os.environ.get("NOS_POD_EAGER_QUEUES", "0") == "1":
         # touch every stream back to back before anything else: HIP creates the process's hardware
@@ -82,13 +108,13 @@ def main(argv=None) -> int:
     stream = streams[0]
     with torch.no_grad(), torch.cuda.stream(stream):
         for _ in range(2):
-            model(x)
+            res = infer()
     stream.synchronize()
     graph = None
     if not args.no_graph:
         graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(graph, stream=stream):
-            model(x)
+            res = infer()
         stream.synchronize()
     out: Dict[str, Any] = {"pid": os.getpid(), "slice_ids": os.environ.get("NOS_SLICE_IDS", ""),
                            "hsa_cu_mask": os.environ.get("HSA_CU_MASK", ""), "slice_cus": K.slice_cus(),
@@ -121,12 +147,16 @@ def main(argv=None) -> int:
                 if graph is not None:
                     graph.replay()
                 else:
-                    model(x)
+                    res = infer()
             s.synchronize()
             lat.append(1e3 * (time.perf_counter() - t0))
     out["window_s"] = round(time.time() - start, 3)
     out["inferences"] = len(lat)
     out["latency_ms"] = _stats(lat)
+    if args.end_to_end:
+        out["end_to_end"] = True
+        out["input_hw"] = list(hw)
+        out["detections"] = int(res["count"].sum().item())   # of the last inference
     if census is not None:
         out["census"] = census
     out["hbm"] = _shim()

@@ -16,6 +16,9 @@ DETR-style MLP heads) built for the MI355X inference path:
   LayerNorm that emits x3 planes, x3 GEMMs with bias / exact GELU / residuals fused into the store
   (the QKV projection leaves as fp32, which the x3 flash attention splits in-kernel), and the
   stream-K x3 flash attention; the detection heads (100 tokens) stay on ``torch`` / hipBLASLt;
+* ``encode_image`` / ``detect_image`` take a uint8 photo instead of ready pixels: the processor's
+  resize and normalisation fused with the patch GEMM's x3 split, and the post-process, one HIP
+  launch each (:mod:`walkai_nos_amd.ops.image`, :mod:`.processor`);
 * ``load_hf_state_dict`` maps a ``transformers`` ``YolosForObjectDetection`` state dict onto this
   module, which is how numerical parity is tested
   (``tests/test_infra.py::test_yolos_matches_transformers_reference``) — there is no network, so
@@ -36,7 +39,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ...ops import image as I
 from ...ops import kernels as K
+from .processor import YolosProcessor
 
 
 @dataclass
@@ -163,6 +168,8 @@ class YolosSmall(nn.Module):
         self.cls_head = _MLPHead(d, d, c.num_labels + 1)
         self.box_head = _MLPHead(d, d, 4)
         self._pos_cache: Dict[Tuple[int, int, str, int], torch.Tensor] = {}
+        #: the image processor of :meth:`encode_image` / :meth:`detect_image` (replace it for another size rule)
+        self.processor = YolosProcessor(patch=c.patch_size)
         self.reset_parameters()
 
     def reset_parameters(self, seed: int = 0) -> None:
@@ -225,6 +232,9 @@ class YolosSmall(nn.Module):
         else:
             xp = K.patch_embed(pixels, self.patch.weight, self.patch.bias, self.c.patch_size)   # [B, P, D]
             x = torch.cat((self.cls_token.expand(B, -1, -1), xp, self.det_tokens.expand(B, -1, -1)), dim=1) + pe
+        return self._run_blocks(x, mid)
+
+    def _run_blocks(self, x: torch.Tensor, mid: Optional[torch.Tensor]) -> torch.Tensor:
         if K.x3_active(x):
             h3 = None
             for i, blk in enumerate(self.blocks):
@@ -234,6 +244,53 @@ class YolosSmall(nn.Module):
             for i, blk in enumerate(self.blocks):
                 x = blk(x, mid[i] if mid is not None and i < self.c.num_layers - 1 else None)
         return x
+
+    # -- image in, detections out ----------------------------------------------------------
+    def _image_fused(self, img: torch.Tensor, hw: Tuple[int, int]) -> bool:
+        """The uint8 image can go straight to the patch GEMM's planes: batch 1 on the GPU in x3 mode,
+        and a resize the kernel takes (``ops.image.fusable``)."""
+        p = self.c.patch_size
+        return (img.shape[0] == 1 and img.is_cuda and K.x3_active(self.pos_embed) and self.c.num_channels == 3
+                and (3 * p * p) % 32 == 0 and I.fusable(tuple(img.shape[1:3]), hw, p))
+
+    def encode_image(self, image_u8) -> torch.Tensor:
+        """:meth:`encode` from a uint8 HWC image (tensor, ndarray or PIL): resized by
+        ``self.processor``'s rule, normalised and split into the patch GEMM's x3 planes by one kernel
+        (``ops.image.image_patch_planes``) — no fp32 image is materialised. In ``f32`` mode, off the GPU
+        or for a batch it is ``encode(processor.preprocess(image))``."""
+        img = self.processor.as_batch(image_u8, self.pos_embed.device)
+        hw = self.processor.size(tuple(img.shape[1:3]))
+        if not self._image_fused(img, hw):
+            return self.encode(self.processor.preprocess(img))
+        from ...ops.gemm import gemm_x3
+        pe, mid = self.position_embeddings(hw)
+        p = self.c.patch_size
+        P = (hw[0] // p) * (hw[1] // p)
+        x = self.token_template(hw).clone()
+        planes, _ = I.image_patch_planes(img, hw, p, self.processor.mean, self.processor.std)
+        gemm_x3(planes, self.patch.weight.reshape(self.patch.weight.shape[0], -1), self.patch.bias,
+                residual2=pe[0, 1:1 + P], out=x[0, 1:1 + P])
+        return self._run_blocks(x, mid)
+
+    def detect_image(self, image_u8, threshold: float = 0.5) -> Dict[str, torch.Tensor]:
+        """Image in, detections out, with no host synchronisation (so it can be captured in a graph):
+        ``{"logits", "pred_boxes"}`` of the model and ``{"count", "scores", "labels", "boxes"}`` of
+        ``ops.image.detections`` — survivors first, in token order, boxes in pixels of the original
+        image. ``self.processor.results(count, scores, labels, boxes)`` gives the per-image lists."""
+        img = self.processor.as_batch(image_u8, self.pos_embed.device)
+        logits, boxes = self.detect(self.encode_image(img))
+        count, scores, labels, xyxy = I.detections(logits, boxes, self._target_sizes(img), threshold)
+        return {"logits": logits, "pred_boxes": boxes, "count": count, "scores": scores, "labels": labels,
+                "boxes": xyxy}
+
+    def _target_sizes(self, img: torch.Tensor) -> torch.Tensor:
+        """``[B, 2]`` fp32 (height, width) of the original images on their device, cached: a captured
+        graph must not copy from the host."""
+        key = (img.shape[0], img.shape[1], img.shape[2], str(img.device))
+        if getattr(self, "_ts_key", None) != key:
+            self._ts = torch.tensor([[img.shape[1], img.shape[2]]] * img.shape[0], dtype=torch.float32).to(img.device)
+            self._ts_key = key
+        return self._ts
 
     def detect(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(logits, boxes)`` from :meth:`encode`'s tokens: ``ln_f`` and the two MLP heads on the

@@ -116,6 +116,8 @@ TARGETS: Sequence[Target] = (
            libs=["rccl", "amdhip64"]),
     Target("libnos_kernels.so", ["kernels.hip", "gemm.hip", "gemm_x3.hip", "head.hip", "attn_proj.hip", "attn_wide.hip"],
            "hipcc", source_flags={"attn_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}),
+    # the image half of the workload (uint8 image -> patch planes, logits -> detections): a library of its own
+    Target("libnos_image.so", ["image.hip"], "hipcc"),
     # the agent's commit-barrier helper as a native program: no interpreter start-up on the flip path
     Target("nos-gpuhelper", ["gpuhelper.cpp", "rccl_barrier.cpp", "p2p_barrier.hip"], "hipcc",
            libs=["rccl", "amdhip64"], executable=True),

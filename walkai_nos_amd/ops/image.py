@@ -1,0 +1,302 @@
+"""The image half of the workload: a uint8 image to the patch-embedding GEMM's operand, and
+``(logits, boxes)`` to detections — HIP kernels on the GPU (``csrc/image.hip``, ``libnos_image.so``),
+PyTorch reference math on the CPU and with the ``torch`` backend, the conventions of
+:mod:`walkai_nos_amd.ops.kernels`.
+
+* :func:`resize_size` — the YOLOS processor's size rule (shortest edge, longest-edge clamp, both
+  sides cropped to a multiple of 16).
+* :func:`image_patch_planes` — antialiased triangle ("bilinear") resample at half-pixel centres,
+  the per-channel affine ``v / (255 std) - mean / std``, and the x3 split of the im2col, in one
+  launch. The tap tables are built on the host in fp64, rounded to fp32 and cached on the device per
+  ``(h, w, H, W)``, so the kernel reads constants and a captured graph stays valid. Per-axis scales up
+  to 4 (9 taps) run in the kernel; anything larger takes the torch composition.
+* :func:`detections` — ``post_process_object_detection`` as one launch without a host
+  synchronisation: softmax, best of the first ``L`` classes, corner boxes in pixels of the original
+  image, and the rows above the threshold compacted in token order, ``count`` written on the device.
+
+The resample is what ``F.interpolate(..., mode="bilinear", antialias=True, align_corners=False)``
+computes, which is PIL's ``BILINEAR`` resize in float. Unlike the ``transformers`` processor nothing
+is rounded to uint8 between the two passes, so pixels differ from it by less than one uint8 step.
+"""
+from __future__ import annotations
+
+import ctypes
+import threading
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import kernels as K
+from .native import NativeUnavailable, available, load
+
+LIB = "libnos_image.so"
+#: weights per output row / column, and the per-axis scale they cover (``csrc/image.hip``)
+TAPS = 9
+MAX_SCALE = 4.0
+MAX_PATCH = 16
+MAX_FOOTPRINT = 72
+#: detections kernel limits: rows per image, classes with "no object"
+MAX_ROWS, MAX_CLASSES = 1024, 128
+
+_lib: Optional[ctypes.CDLL] = None
+_lock = threading.Lock()
+
+
+def hip_available() -> bool:
+    return available(LIB)
+
+
+def _L() -> ctypes.CDLL:
+    global _lib
+    with _lock:
+        if _lib is None:
+            L = load(LIB)
+            vp, i32, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+            fp = ctypes.POINTER(ctypes.c_float)
+            L.nos_image_patch_planes_u8.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, fp, fp,
+                                                    i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+            L.nos_detections_f32.argtypes = [vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, vp, vp]
+            L.nos_image_last_error.restype = ctypes.c_char_p
+            if (L.nos_image_taps(), L.nos_image_max_footprint(), L.nos_image_max_patch()) != \
+                    (TAPS, MAX_FOOTPRINT, MAX_PATCH):
+                raise NativeUnavailable(f"{LIB} was built with other limits than ops/image.py expects")
+            _lib = L
+        return _lib
+
+
+def _use_hip(t: torch.Tensor) -> bool:
+    if not t.is_cuda or K.get_backend() == "torch":
+        return False
+    if not hip_available():
+        raise NativeUnavailable(f"{LIB} is not built but a GPU tensor reached the HIP op path")
+    return True
+
+
+def _check(rc: int, what: str) -> None:
+    if rc != 0:
+        raise RuntimeError(f"nos {what} failed: {_L().nos_image_last_error().decode()} (rc={rc})")
+
+
+def image_wgs() -> int:
+    """Workgroups of the preprocess kernel (grid-stride over patches): one per patch on the whole
+    GPU; on a slice that shares the GPU, 4 per CU of the slice (as ``kernels.layernorm_wgs``)."""
+    cus = K.slice_cus()
+    return 0 if cus >= K.total_cus() else 4 * cus
+
+
+# ---- the size rule ------------------------------------------------------------------------------
+def resize_size(hw: Tuple[int, int], shortest: int = 800, longest: Optional[int] = 1333,
+                mod: Optional[int] = 16) -> Tuple[int, int]:
+    """``(H, W)`` the YOLOS processor resizes an ``(h, w)`` image to: the shortest edge to
+    ``shortest`` unless the longest would pass ``longest``, the other edge truncated, then both
+    cropped to a multiple of ``mod``."""
+    h, w = int(hw[0]), int(hw[1])
+    size, raw = int(shortest), None
+    if longest is not None:
+        lo, hi = float(min(h, w)), float(max(h, w))
+        if hi / lo * size > longest:
+            raw = longest * lo / hi
+            size = int(round(raw))
+    if w < h:
+        ow = size
+        oh = int((raw if raw is not None else size) * h / w)
+    elif (h <= w and h == size) or (w <= h and w == size):
+        oh, ow = h, w
+    else:
+        oh = size
+        ow = int((raw if raw is not None else size) * w / h)
+    if mod is not None:
+        ow -= ow % mod
+        oh -= oh % mod
+    return oh, ow
+
+
+# ---- the resample -------------------------------------------------------------------------------
+def tap_table(n_in: int, n_out: int, taps: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The antialiased triangle filter of one axis in fp64: ``(first [n_out], count [n_out],
+    weights [n_out, taps])``. Output ``i`` is ``sum_k weights[i, k] * src[first[i] + k]`` over
+    ``k < count[i]``: centre ``(i + 0.5) * n_in / n_out``, support ``max(scale, 1)``, weights
+    normalised to sum 1 (so the edges renormalise instead of clamping)."""
+    scale = n_in / n_out
+    support = scale if scale >= 1.0 else 1.0
+    inv = 1.0 / scale if scale >= 1.0 else 1.0
+    centre = scale * (np.arange(n_out, dtype=np.float64) + 0.5)
+    first = np.maximum((centre - support + 0.5).astype(np.int64), 0)
+    count = np.minimum((centre + support + 0.5).astype(np.int64), n_in) - first
+    width = int(count.max()) if taps is None else taps
+    if count.max() > width:
+        raise ValueError(f"tap_table: {int(count.max())} taps at scale {scale:.3f}, room for {width}")
+    k = np.arange(width, dtype=np.float64)
+    x = (k[None, :] + first[:, None] - centre[:, None] + 0.5) * inv
+    wt = np.clip(1.0 - np.abs(x), 0.0, None) * (k[None, :] < count[:, None])
+    wt /= wt.sum(axis=1, keepdims=True)
+    return first, count, wt
+
+
+def resample_matrix(n_in: int, n_out: int) -> torch.Tensor:
+    """The tap table of one axis as a dense fp64 ``[n_out, n_in]`` matrix."""
+    first, count, wt = tap_table(n_in, n_out)
+    m = np.zeros((n_out, n_in), dtype=np.float64)
+    for k in range(wt.shape[1]):
+        rows = np.nonzero(k < count)[0]
+        m[rows, first[rows] + k] = wt[rows, k]
+    return torch.from_numpy(m)
+
+
+def resample_reference(img: torch.Tensor, out_hw: Tuple[int, int]) -> torch.Tensor:
+    """The fp64 definition of the resample, from the tap tables: ``img`` ``[..., h, w]`` (any real
+    dtype) -> ``[..., H, W]`` float64."""
+    h, w = img.shape[-2:]
+    return resample_matrix(h, out_hw[0]) @ img.double().cpu() @ resample_matrix(w, out_hw[1]).t()
+
+
+_tables: Dict[tuple, tuple] = {}
+
+
+def _device_tables(h: int, w: int, H: int, W: int, p: int, device: torch.device) -> Optional[tuple]:
+    """``(yidx, ywt, xidx, xwt, max_fh, max_fw)`` on ``device``, cached; None when an axis needs more
+    than ``TAPS`` weights or a patch's source footprint does not fit the kernel's LDS tile."""
+    key = (h, w, H, W, p, str(device))
+    if key not in _tables:
+        entry = None
+        if h / H <= MAX_SCALE and w / W <= MAX_SCALE:
+            out = []
+            for n_in, n_out in ((h, H), (w, W)):
+                first, count, wt = tap_table(n_in, n_out, TAPS)
+                starts = np.arange(0, n_out, p)
+                lasts = np.minimum(starts + p, n_out) - 1
+                out.append((first, count, wt, int((first[lasts] + count[lasts] - first[starts]).max())))
+            if all(o[3] <= MAX_FOOTPRINT for o in out):
+                dev = []
+                for first, count, wt, _ in out:
+                    dev.append(torch.from_numpy(np.stack((first, count)).astype(np.int32)).to(device))
+                    dev.append(torch.from_numpy(wt.astype(np.float32)).to(device))
+                entry = (dev[0], dev[1], dev[2], dev[3], out[0][3], out[1][3])
+        with _lock:
+            if len(_tables) >= 16:
+                _tables.clear()
+            _tables[key] = entry
+    return _tables[key]
+
+
+def affine(mean: Sequence[float], std: Sequence[float]) -> Tuple[Tuple[float, ...], Tuple[float, ...]]:
+    """``(a, b)`` with ``pixel = u8 * a_c + b_c``: ``a_c = 1 / (255 std_c)``, ``b_c = -mean_c / std_c``."""
+    return tuple(1.0 / (255.0 * s) for s in std), tuple(-m / s for m, s in zip(mean, std))
+
+
+def im2col(pixels: torch.Tensor, patch: int) -> torch.Tensor:
+    """``[B, C, H, W]`` -> ``[B*gh*gw, C*p*p]``: row ``(b, i, j)``, column ``(c, u, v)``."""
+    B, C, H, W = pixels.shape
+    gh, gw = H // patch, W // patch
+    return pixels[:, :, :gh * patch, :gw * patch].reshape(B, C, gh, patch, gw, patch) \
+        .permute(0, 2, 4, 1, 3, 5).reshape(B * gh * gw, C * patch * patch)
+
+
+def pixels_reference(img_u8: torch.Tensor, out_hw: Tuple[int, int], mean: Sequence[float], std: Sequence[float],
+                     dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The torch composition: ``[B, h, w, 3]`` uint8 -> ``[B, 3, H, W]`` in ``dtype``."""
+    a, b = affine(mean, std)
+    x = F.interpolate(img_u8.permute(0, 3, 1, 2).to(dtype), size=tuple(out_hw), mode="bilinear", antialias=True,
+                      align_corners=False)
+    # (the permuted view makes interpolate answer channels-last: the model takes plain NCHW)
+    return (x * torch.tensor(a, dtype=dtype, device=x.device).view(1, 3, 1, 1)
+            + torch.tensor(b, dtype=dtype, device=x.device).view(1, 3, 1, 1)).contiguous()
+
+
+def fusable(hw: Tuple[int, int], out_hw: Tuple[int, int], patch: int) -> bool:
+    """True when the kernel can take this resize: even patch side up to 16, at least one whole patch,
+    and per-axis scales up to 4."""
+    return (patch % 2 == 0 and 2 <= patch <= MAX_PATCH and out_hw[0] >= patch and out_hw[1] >= patch
+            and hw[0] / out_hw[0] <= MAX_SCALE and hw[1] / out_hw[1] <= MAX_SCALE)
+
+
+def image_patch_planes(img_u8: torch.Tensor, out_hw: Tuple[int, int], patch: int, mean: Sequence[float],
+                       std: Sequence[float], want_pixels: bool = False) \
+        -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """``[B, h, w, 3]`` uint8 (interleaved RGB) -> ``(planes [3, B*gh*gw, 3*p*p] bf16, pixels
+    [B, 3, H, W] fp32 or None)``: resized to ``out_hw``, normalised, and split into the x3 planes of
+    the patch matrix (``kernels.patch_planes``' layout). One HIP launch on the GPU; on a CPU tensor,
+    with the ``torch`` backend, or past the kernel's limits (:func:`fusable`), the fp32 torch
+    composition and ``split3`` of its im2col."""
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[-1] != 3:
+        raise ValueError("image_patch_planes: a uint8 [B, h, w, 3] image")
+    B, h, w, _ = img_u8.shape
+    H, W = int(out_hw[0]), int(out_hw[1])
+    tabs = None
+    if _use_hip(img_u8) and fusable((h, w), (H, W), patch):
+        tabs = _device_tables(h, w, H, W, patch, img_u8.device)
+    if tabs is None:
+        px = pixels_reference(img_u8, (H, W), mean, std)
+        return K.split3(im2col(px, patch)), (px if want_pixels else None)
+    img = img_u8.contiguous()
+    gh, gw = H // patch, W // patch
+    planes = torch.empty(3, B * gh * gw, 3 * patch * patch, dtype=torch.bfloat16, device=img.device)
+    pixels = torch.empty(B, 3, H, W, dtype=torch.float32, device=img.device) if want_pixels else None
+    yidx, ywt, xidx, xwt, max_fh, max_fw = tabs
+    a, b = affine(mean, std)
+    F3 = ctypes.c_float * 3
+    rc = _L().nos_image_patch_planes_u8(img.data_ptr(), planes.data_ptr(), pixels.data_ptr() if want_pixels else None,
+                                        yidx.data_ptr(), ywt.data_ptr(), xidx.data_ptr(), xwt.data_ptr(),
+                                        ywt.shape[0], xwt.shape[0], ywt.shape[1], max_fh, max_fw, F3(*a), F3(*b),
+                                        B, h, w, H, W, patch, gh, gw, image_wgs(),
+                                        torch.cuda.current_stream().cuda_stream)
+    _check(rc, "image_patch_planes")
+    return planes, pixels
+
+
+# ---- detections ---------------------------------------------------------------------------------
+def target_tensor(target_sizes, batch: int, device: torch.device) -> torch.Tensor:
+    """``[B, 2]`` fp32 (height, width) on ``device``; a tensor already there is used as it is (no
+    copy, so a captured graph can hold it); None means unscaled boxes."""
+    if target_sizes is None:
+        return torch.ones(batch, 2, dtype=torch.float32, device=device)
+    t = torch.as_tensor(target_sizes)
+    t = t.to(device=device, dtype=torch.float32).reshape(-1, 2).contiguous()
+    if t.shape[0] != batch:
+        raise ValueError("detections: as many target sizes as images")
+    return t
+
+
+def detections_reference(logits: torch.Tensor, boxes: torch.Tensor, target: torch.Tensor, threshold: float) \
+        -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The torch composition of :func:`detections` in the inputs' precision, without a host sync."""
+    prob = torch.softmax(logits, -1)
+    scores, labels = prob[..., :-1].max(-1)
+    cx, cy, bw, bh = boxes.unbind(-1)
+    xyxy = torch.stack((cx - 0.5 * bw, cy - 0.5 * bh, cx + 0.5 * bw, cy + 0.5 * bh), dim=-1)
+    th, tw = target.to(boxes.dtype).unbind(1)
+    xyxy = xyxy * torch.stack((tw, th, tw, th), dim=1)[:, None, :]
+    keep = scores > threshold
+    count = keep.sum(-1).to(torch.int32)
+    order = torch.sort((~keep).to(torch.int8), dim=-1, stable=True).indices     # kept rows first, in order
+    live = torch.arange(keep.shape[1], device=keep.device)[None, :] < count[:, None]
+    scores = torch.gather(scores, 1, order) * live
+    labels = (torch.gather(labels, 1, order) * live).to(torch.int32)
+    xyxy = torch.gather(xyxy, 1, order[..., None].expand(-1, -1, 4)) * live[..., None]
+    return count, scores, labels, xyxy
+
+
+def detections(logits: torch.Tensor, boxes: torch.Tensor, target_sizes, threshold: float) \
+        -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``logits [B, M, L+1]``, ``boxes [B, M, 4]`` (centre format, 0..1), ``target_sizes [B, 2]``
+    (height, width of each original image) -> ``(count [B] int32, scores [B, M], labels [B, M] int32,
+    boxes_xyxy [B, M, 4])``: row ``m`` survives when the largest softmax probability of its first
+    ``L`` classes exceeds ``threshold``; survivors stand first, in token order, zeros behind them."""
+    B, M, C = logits.shape
+    target = target_tensor(target_sizes, B, logits.device)
+    if not _use_hip(logits) or logits.dtype != torch.float32 or boxes.dtype != torch.float32 \
+            or M > MAX_ROWS or C > MAX_CLASSES or C < 2:
+        return detections_reference(logits, boxes, target, threshold)
+    logits, boxes = logits.contiguous(), boxes.contiguous()
+    dev = logits.device
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, M, dtype=torch.float32, device=dev)
+    labels = torch.empty(B, M, dtype=torch.int32, device=dev)
+    xyxy = torch.empty(B, M, 4, dtype=torch.float32, device=dev)
+    rc = _L().nos_detections_f32(logits.data_ptr(), boxes.data_ptr(), target.data_ptr(), float(threshold), B, M, C,
+                                 count.data_ptr(), scores.data_ptr(), labels.data_ptr(), xyxy.data_ptr(),
+                                 torch.cuda.current_stream().cuda_stream)
+    _check(rc, "detections")
+    return count, scores, labels, xyxy
