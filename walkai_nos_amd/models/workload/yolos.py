@@ -41,6 +41,7 @@ import torch.nn.functional as F
 
 from ...ops import image as I
 from ...ops import kernels as K
+from ...ops.graph_cache import GraphCache
 from .processor import YolosProcessor
 
 
@@ -62,6 +63,12 @@ class YolosConfig:
     def head_dim(self) -> int:
         return self.hidden_size // self.num_heads
 
+
+#: eagerly used input sizes whose position embeddings, token template and target sizes stay cached
+#: (sizes used under graph capture are kept besides): with mid position embeddings one size is 12
+#: tensors of T x 384 fp32, 63 MB at the demo's 3401 tokens, so 4 bound a server that sees every size
+#: eagerly to about 250 MB, while a handful of sizes in rotation never re-interpolates
+CACHED_SIZES = 4
 
 #: the demo's input after YolosImageProcessor (640x480 COCO image -> shortest edge 800)
 DEMO_INPUT_HW = (800, 1066)
@@ -167,7 +174,12 @@ class YolosSmall(nn.Module):
         self.ln_f = nn.LayerNorm(d, eps=c.layer_norm_eps)
         self.cls_head = _MLPHead(d, d, c.num_labels + 1)
         self.box_head = _MLPHead(d, d, 4)
-        self._pos_cache: Dict[Tuple[int, int, str, int], torch.Tensor] = {}
+        # per-size device tensors that a captured graph reads by address (ops/graph_cache.py): what is
+        # handed out under capture stays until invalidate_cache() or a parameter-version change; of the
+        # sizes only run eagerly the CACHED_SIZES most recently used are kept
+        self._pos_cache = GraphCache(CACHED_SIZES)
+        self._tok_cache = GraphCache(CACHED_SIZES)
+        self._ts_cache = GraphCache(CACHED_SIZES)
         #: the image processor of :meth:`encode_image` / :meth:`detect_image` (replace it for another size rule)
         self.processor = YolosProcessor(patch=c.patch_size)
         self.reset_parameters()
@@ -199,17 +211,21 @@ class YolosSmall(nn.Module):
 
     def position_embeddings(self, hw: Tuple[int, int]) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         key = (hw[0], hw[1], str(self.pos_embed.device), self.pos_embed._version)
-        if key not in self._pos_cache:
+
+        def make():
             with torch.no_grad():
                 pe = self._interp(self.pos_embed, hw).contiguous()
                 mid = self._interp(self.mid_pos_embed, hw).contiguous() if self.mid_pos_embed is not None else None
-            self._pos_cache.clear()
-            self._pos_cache[key] = (pe, mid)
-        return self._pos_cache[key]
+            return pe, mid
+        # entries of another device or parameter version are stale: they leave, pinned or not
+        return self._pos_cache.get(key, make, lambda k: k[2:] != key[2:])
 
     def invalidate_cache(self) -> None:
+        """Drop every cached per-size tensor (after the parameters changed in place in a way their
+        version counters miss, e.g. through ``.data``). Graphs captured before must be captured again."""
         self._pos_cache.clear()
-        self._tok_key = None
+        self._tok_cache.clear()
+        self._ts_cache.clear()
 
     # -- forward -------------------------------------------------------------------------
     def forward(self, pixels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -286,11 +302,9 @@ class YolosSmall(nn.Module):
     def _target_sizes(self, img: torch.Tensor) -> torch.Tensor:
         """``[B, 2]`` fp32 (height, width) of the original images on their device, cached: a captured
         graph must not copy from the host."""
-        key = (img.shape[0], img.shape[1], img.shape[2], str(img.device))
-        if getattr(self, "_ts_key", None) != key:
-            self._ts = torch.tensor([[img.shape[1], img.shape[2]]] * img.shape[0], dtype=torch.float32).to(img.device)
-            self._ts_key = key
-        return self._ts
+        B, h, w = img.shape[:3]
+        return self._ts_cache.get((B, h, w, str(img.device)),
+                                  lambda: torch.tensor([[h, w]] * B, dtype=torch.float32).to(img.device))
 
     def detect(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(logits, boxes)`` from :meth:`encode`'s tokens: ``ln_f`` and the two MLP heads on the
@@ -316,17 +330,18 @@ class YolosSmall(nn.Module):
     def token_template(self, hw: Tuple[int, int]) -> torch.Tensor:
         """[1, T, D]: the class-token row + its position embedding, zero patch rows, the detection-token
         rows + theirs — cached per parameter versions (every forward copies it once)."""
-        key = (hw, str(self.pos_embed.device), self.pos_embed._version, self.cls_token._version,
+        key = (tuple(hw), str(self.pos_embed.device), self.pos_embed._version, self.cls_token._version,
                self.det_tokens._version)
-        if getattr(self, "_tok_key", None) != key:
+
+        def make():
             pe, _ = self.position_embeddings(hw)
             nd = self.c.num_detection_tokens
             with torch.no_grad():
                 t = torch.zeros_like(pe)
                 t[:, :1] = self.cls_token + pe[:, :1]
                 t[:, -nd:] = self.det_tokens + pe[:, -nd:]
-            self._tok, self._tok_key = t, key
-        return self._tok
+            return t
+        return self._tok_cache.get(key, make, lambda k: k[1:] != key[1:])
 
     def flops_per_inference(self, hw: Tuple[int, int] = DEMO_INPUT_HW) -> float:
         c = self.c

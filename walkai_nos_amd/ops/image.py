@@ -8,7 +8,8 @@ PyTorch reference math on the CPU and with the ``torch`` backend, the convention
 * :func:`image_patch_planes` — antialiased triangle ("bilinear") resample at half-pixel centres,
   the per-channel affine ``v / (255 std) - mean / std``, and the x3 split of the im2col, in one
   launch. The tap tables are built on the host in fp64, rounded to fp32 and cached on the device per
-  ``(h, w, H, W)``, so the kernel reads constants and a captured graph stays valid. Per-axis scales up
+  ``(h, w, H, W)``, so the kernel reads constants and a captured graph stays valid: tables handed out
+  under capture are kept until :func:`invalidate_cache` (:mod:`.graph_cache`). Per-axis scales up
   to 4 (9 taps) run in the kernel; anything larger takes the torch composition.
 * :func:`detections` — ``post_process_object_detection`` as one launch without a host
   synchronisation: softmax, best of the first ``L`` classes, corner boxes in pixels of the original
@@ -22,13 +23,14 @@ from __future__ import annotations
 
 import ctypes
 import threading
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 from . import kernels as K
+from .graph_cache import GraphCache
 from .native import NativeUnavailable, available, load
 
 LIB = "libnos_image.so"
@@ -152,33 +154,41 @@ def resample_reference(img: torch.Tensor, out_hw: Tuple[int, int]) -> torch.Tens
     return resample_matrix(h, out_hw[0]) @ img.double().cpu() @ resample_matrix(w, out_hw[1]).t()
 
 
-_tables: Dict[tuple, tuple] = {}
+#: the tap tables per ``(h, w, H, W, p, device)``. A launch recorded in a graph reads them by address, so
+#: an entry handed out under capture stays until :func:`invalidate_cache`; of the sizes only seen
+#: eagerly the 16 most recently used are kept (about 44 bytes per output row and column each: 80 KB
+#: at 800 x 1056, so the bound is on the number of stale sizes, not on memory that matters)
+_tables = GraphCache(16)
+
+
+def invalidate_cache() -> None:
+    """Drop every cached tap table, also those a captured graph holds: capture such graphs again."""
+    _tables.clear()
+
+
+def _make_tables(h: int, w: int, H: int, W: int, p: int, device: torch.device) -> Optional[tuple]:
+    if h / H > MAX_SCALE or w / W > MAX_SCALE:
+        return None
+    out = []
+    for n_in, n_out in ((h, H), (w, W)):
+        first, count, wt = tap_table(n_in, n_out, TAPS)
+        starts = np.arange(0, n_out, p)
+        lasts = np.minimum(starts + p, n_out) - 1
+        out.append((first, count, wt, int((first[lasts] + count[lasts] - first[starts]).max())))
+    if any(o[3] > MAX_FOOTPRINT for o in out):
+        return None
+    dev = []
+    for first, count, wt, _ in out:
+        dev.append(torch.from_numpy(np.stack((first, count)).astype(np.int32)).to(device))
+        dev.append(torch.from_numpy(wt.astype(np.float32)).to(device))
+    return dev[0], dev[1], dev[2], dev[3], out[0][3], out[1][3]
 
 
 def _device_tables(h: int, w: int, H: int, W: int, p: int, device: torch.device) -> Optional[tuple]:
-    """``(yidx, ywt, xidx, xwt, max_fh, max_fw)`` on ``device``, cached; None when an axis needs more
-    than ``TAPS`` weights or a patch's source footprint does not fit the kernel's LDS tile."""
-    key = (h, w, H, W, p, str(device))
-    if key not in _tables:
-        entry = None
-        if h / H <= MAX_SCALE and w / W <= MAX_SCALE:
-            out = []
-            for n_in, n_out in ((h, H), (w, W)):
-                first, count, wt = tap_table(n_in, n_out, TAPS)
-                starts = np.arange(0, n_out, p)
-                lasts = np.minimum(starts + p, n_out) - 1
-                out.append((first, count, wt, int((first[lasts] + count[lasts] - first[starts]).max())))
-            if all(o[3] <= MAX_FOOTPRINT for o in out):
-                dev = []
-                for first, count, wt, _ in out:
-                    dev.append(torch.from_numpy(np.stack((first, count)).astype(np.int32)).to(device))
-                    dev.append(torch.from_numpy(wt.astype(np.float32)).to(device))
-                entry = (dev[0], dev[1], dev[2], dev[3], out[0][3], out[1][3])
-        with _lock:
-            if len(_tables) >= 16:
-                _tables.clear()
-            _tables[key] = entry
-    return _tables[key]
+    """``(yidx, ywt, xidx, xwt, max_fh, max_fw)`` on ``device``, cached (:data:`_tables`); None when an
+    axis needs more than ``TAPS`` weights or a patch's source footprint does not fit the kernel's LDS
+    tile."""
+    return _tables.get((h, w, H, W, p, str(device)), lambda: _make_tables(h, w, H, W, p, device))
 
 
 def affine(mean: Sequence[float], std: Sequence[float]) -> Tuple[Tuple[float, ...], Tuple[float, ...]]:
