@@ -8,12 +8,20 @@
 //    patch_planes_f32 in head.hip); optionally the fp32 pixels [B][3][H][W] as well. One 256-thread
 //    workgroup per p x p patch: the patch's source footprint is staged in LDS with aligned 4-byte
 //    loads, resampled horizontally into an fp32 LDS tile, then vertically by thread (u, v).
+//  * image_patch_planes_nv12 — the same kernel body with another staging loop: the source is a video
+//    decoder's NV12 surface (a Y plane [B][h][w] and an interleaved UV plane [B][(h+1)/2][(w+1)/2][2],
+//    each with its own row pitch and batch stride). The footprint's luma rows and the chroma rows under
+//    them are read, converted to RGB by an integer matrix the host passes (nearest chroma: luma (r, c)
+//    takes chroma (r >> 1, c >> 1)) and written as RGB bytes into the same LDS tile; everything behind
+//    the staging loop is shared, so the result is bit-equal to the RGB kernel on the converted frame.
 //  * detections_f32 — softmax over the class logits, the best of the first L classes, the box in
 //    corner format scaled to the original image, and a stable compaction of the rows above the
 //    threshold; one workgroup per image, one wave per row.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 
 namespace {
@@ -41,7 +49,44 @@ struct ImgArgs {
   int B, h, w, H, W, p, gh, gw, GH, GW;  // GH x GW: the tiles that cover H x W (>= gh x gw)
 };
 
-__global__ __launch_bounds__(256) void image_patch_planes_u8(ImgArgs a) {
+// The NV12 source of image_patch_planes_nv12. [ylo, yhi) and [uvlo, uvhi) are the storage the planes
+// live in: no byte outside them is read. tab: the colour matrix in 16.16 fixed point, row c = (Y, U, V)
+// coefficients of channel c, then the offsets taken from Y, U and V first (ops/image.py builds it).
+struct Nv12Args {
+  const uint8_t *y, *uv;
+  uintptr_t ylo, yhi, uvlo, uvhi;
+  long long ypitch, uvpitch, ybs, uvbs;
+  int tab[12];
+};
+
+// columns of an NV12 footprint are staged in groups of 4 (one dword of luma, one dword = two pairs of
+// chroma, three dwords of RGB): NG groups fit a row of the LDS tile, which covers any 69 columns
+constexpr int NG = RS / 12, NV12_FMAX_W = NG * 4 - 3;
+
+// four bytes at q, of which those inside [lo, hi) are read: one aligned dword where q allows it
+__device__ __forceinline__ uint32_t load4(uintptr_t q, uintptr_t lo, uintptr_t hi) {
+  if ((q & 3) == 0 && q >= lo && q + 4 <= hi) return *reinterpret_cast<const uint32_t*>(q);
+  uint32_t v = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (q + k >= lo && q + k < hi) v |= uint32_t(*reinterpret_cast<const uint8_t*>(q + k)) << (8 * k);
+  return v;
+}
+
+// one pixel's channel c as 8.16 fixed point clamped to [0, 256): exact in int32 (the largest term is below
+// 2^25, the sum below 2^27). The channel is bits 16-23, clip((sum + 2^15) >> 16, 0, 255) of ops/image.py:
+// clamping before the shift is the same number. It is also deliberate: from clamp(x >> 16) | clamp(y >> 16)
+// << 8 hipcc (ROCm 7) makes one v_ashr_pk_u8_i32 and takes that result's upper half for zero, which an
+// MI355X does not deliver: the bytes OR-ed in above it came out wrong.
+// The products are 24-bit multiplies (full rate; a 32-bit one is a quarter of it, and these 36 per thread
+// were what the staging loop waited on): the host checks that every coefficient fits.
+__device__ __forceinline__ uint32_t nv12_channel(const int* t, int c, int y, int u, int v) {
+  return uint32_t(min(max(__mul24(t[3 * c], y) + __mul24(t[3 * c + 1], u) + __mul24(t[3 * c + 2], v) + 32768, 0),
+                      0xffffff));
+}
+
+template <bool NV12>
+__device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const Nv12Args& n) {
   __shared__ __attribute__((aligned(16))) uint8_t src[FMAX * RS];
   __shared__ float hz[FMAX * PMAX * 3];  // [footprint row][v][c]: the horizontally resampled rows
   __shared__ float wxs[PMAX * TAPS], wys[PMAX * TAPS];
@@ -60,6 +105,9 @@ __global__ __launch_bounds__(256) void image_patch_planes_u8(ImgArgs a) {
     const int fh = fy1 - fy0, fw = fx1 - fx0;
     // the host checked the tables against these limits; a table that breaks them reads nothing
     if (fy0 < 0 || fx0 < 0 || fy1 > a.h || fx1 > a.w || fh <= 0 || fw <= 0 || fh > FMAX || fw > FMAX) continue;
+    // NV12: column groups of 4, the first one holding fx0; lead bytes of a row in LDS, groups per row
+    const int gx0 = fx0 >> 2, lead = (fx0 & 3) * 3, ng = ((fx1 - 1) >> 2) - gx0 + 1;
+    if (NV12 && ng > NG) continue;
     __syncthreads();  // the previous tile's readers are done with the LDS
     if (tid < ny * TAPS) wys[tid] = a.ywt[size_t(y0) * TAPS + tid];
     if (tid < nx * TAPS) wxs[tid] = a.xwt[size_t(x0) * TAPS + tid];
@@ -71,31 +119,59 @@ __global__ __launch_bounds__(256) void image_patch_planes_u8(ImgArgs a) {
       xf[tid] = min(max(a.xidx[x0 + tid] - fx0, 0), fw - 1);
       xc[tid] = min(min(a.xidx[W + x0 + tid], TAPS), fw - xf[tid]);
     }
-    // stage the footprint: aligned dwords of each global row (the row's own alignment kept in LDS)
-    const int rowbytes = fw * 3;
-    for (int e = tid; e < fh * NDW; e += 256) {
-      const int r = e / NDW, d = e % NDW;
-      const uintptr_t addr = lo + ((size_t(b) * a.h + fy0 + r) * a.w + fx0) * 3;
-      const int sh = int(addr & 3);
-      if (d * 4 >= sh + rowbytes) continue;
-      const uintptr_t q = addr - sh + size_t(d) * 4;
-      uint32_t v = 0;
-      if (q >= lo && q + 4 <= hi) {
-        v = *reinterpret_cast<const uint32_t*>(q);
-      } else {  // the dword that straddles an end of the image: its bytes inside, one by one
+    if constexpr (NV12) {
+      // stage the footprint as RGB bytes: thread (row r, group g) reads 4 luma bytes and the 2 chroma
+      // pairs under them, converts, and writes 12 bytes (columns outside the footprint, at the two
+      // ends of a row, get bytes no later pass reads; pitch padding can only land there)
+      for (int e = tid; e < fh * NG; e += 256) {
+        const int r = e / NG, g = e % NG;
+        if (g >= ng) continue;
+        const int sy = fy0 + r, sx = (gx0 + g) * 4;
+        const uintptr_t qy = reinterpret_cast<uintptr_t>(n.y) + b * n.ybs + sy * n.ypitch + sx;
+        const uintptr_t qc = reinterpret_cast<uintptr_t>(n.uv) + b * n.uvbs + (sy >> 1) * n.uvpitch + sx;
+        const uint32_t yy = load4(qy, n.ylo, n.yhi), cc = load4(qc, n.uvlo, n.uvhi);
+        uint32_t px[4];  // R | G << 8 | B << 16 of the group's four columns
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (q + k >= lo && q + k < hi) v |= uint32_t(*reinterpret_cast<const uint8_t*>(q + k)) << (8 * k);
+        for (int k = 0; k < 4; ++k) {
+          const int y = int((yy >> (8 * k)) & 255) - n.tab[9];
+          const int u = int((cc >> (16 * (k >> 1))) & 255) - n.tab[10];
+          const int v = int((cc >> (16 * (k >> 1) + 8)) & 255) - n.tab[11];
+          px[k] = nv12_channel(n.tab, 0, y, u, v) >> 16 | (nv12_channel(n.tab, 1, y, u, v) >> 8 & 0xff00) |
+                  (nv12_channel(n.tab, 2, y, u, v) & 0xff0000);
+        }
+        uint32_t* dst = reinterpret_cast<uint32_t*>(src + r * RS + g * 12);
+        dst[0] = px[0] | px[1] << 24;
+        dst[1] = px[1] >> 8 | px[2] << 16;
+        dst[2] = px[2] >> 16 | px[3] << 8;
       }
-      *reinterpret_cast<uint32_t*>(src + r * RS + d * 4) = v;
+    } else {
+      // stage the footprint: aligned dwords of each global row (the row's own alignment kept in LDS)
+      const int rowbytes = fw * 3;
+      for (int e = tid; e < fh * NDW; e += 256) {
+        const int r = e / NDW, d = e % NDW;
+        const uintptr_t addr = lo + ((size_t(b) * a.h + fy0 + r) * a.w + fx0) * 3;
+        const int sh = int(addr & 3);
+        if (d * 4 >= sh + rowbytes) continue;
+        const uintptr_t q = addr - sh + size_t(d) * 4;
+        uint32_t v = 0;
+        if (q >= lo && q + 4 <= hi) {
+          v = *reinterpret_cast<const uint32_t*>(q);
+        } else {  // the dword that straddles an end of the image: its bytes inside, one by one
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (q + k >= lo && q + k < hi) v |= uint32_t(*reinterpret_cast<const uint8_t*>(q + k)) << (8 * k);
+        }
+        *reinterpret_cast<uint32_t*>(src + r * RS + d * 4) = v;
+      }
     }
     __syncthreads();
     // horizontal pass: (footprint row r, output column v, channel c), taps in ascending order
     for (int e = tid; e < fh * PMAX * 3; e += 256) {
       const int c = e % 3, v = (e / 3) % PMAX, r = e / (3 * PMAX);
       if (v >= nx) continue;
-      const uintptr_t addr = lo + ((size_t(b) * a.h + fy0 + r) * a.w + fx0) * 3;
-      const uint8_t* s = src + r * RS + int(addr & 3) + xf[v] * 3 + c;
+      int sh = lead;
+      if constexpr (!NV12) sh = int((lo + ((size_t(b) * a.h + fy0 + r) * a.w + fx0) * 3) & 3);
+      const uint8_t* s = src + r * RS + sh + xf[v] * 3 + c;
       const float* wt = wxs + v * TAPS;
       float acc = 0.f;
       for (int k = 0; k < xc[v]; ++k) acc = fmaf(wt[k], float(s[k * 3]), acc);
@@ -129,6 +205,14 @@ __global__ __launch_bounds__(256) void image_patch_planes_u8(ImgArgs a) {
       }
     }
   }
+}
+
+__global__ __launch_bounds__(256) void image_patch_planes_u8(ImgArgs a) {
+  image_patch_planes_body<false>(a, Nv12Args{});
+}
+
+__global__ __launch_bounds__(256) void image_patch_planes_nv12(ImgArgs a, Nv12Args n) {
+  image_patch_planes_body<true>(a, n);
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -226,26 +310,11 @@ int fail(const char* msg) {
   g_err = msg;
   return -1;
 }
-}  // namespace
-
-extern "C" {
-
-const char* nos_image_last_error() { return g_err.c_str(); }
-
-int nos_image_taps() { return TAPS; }
-int nos_image_max_footprint() { return FMAX; }
-int nos_image_max_patch() { return PMAX; }
-
-// img [B][h][w][3] uint8 -> planes [3][B*gh*gw][3*p*p] bf16 (and pixels [B][3][H][W] fp32 when
-// non-null). yidx [2][H] / xidx [2][W] (first source index, tap count) and ywt [H][taps] / xwt
-// [W][taps] are device tables; ytab / xtab are their row counts, max_fh / max_fw the largest source
-// footprint of one patch row / column of those tables (the host built them, so it knows). a, b:
-// host arrays of the three per-channel affine constants. wgs: workgroups (0 = one per tile).
-int nos_image_patch_planes_u8(const void* img, void* planes, float* pixels, const int* yidx, const float* ywt,
-                              const int* xidx, const float* xwt, int ytab, int xtab, int taps, int max_fh, int max_fw,
-                              const float* a, const float* b, int B, int h, int w, int H, int W, int p, int gh, int gw,
-                              int wgs, void* stream) {
-  if (!img || !planes || !yidx || !ywt || !xidx || !xwt || !a || !b) return fail("image_patch_planes: null operand");
+// what both image entries check and fill (all but the source); grid: the workgroups to launch
+int image_args(ImgArgs& k, int& grid, void* planes, float* pixels, const int* yidx, const float* ywt, const int* xidx,
+               const float* xwt, int ytab, int xtab, int taps, int max_fh, int max_fw, const float* a, const float* b,
+               int B, int h, int w, int H, int W, int p, int gh, int gw, int wgs) {
+  if (!planes || !yidx || !ywt || !xidx || !xwt || !a || !b) return fail("image_patch_planes: null operand");
   if (B <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return fail("image_patch_planes: B, h, w, H, W must be positive");
   if (p < 2 || p % 2 || p > PMAX) return fail("image_patch_planes: patch side must be even and at most 16");
   if (gh <= 0 || gw <= 0 || size_t(gh) * p > size_t(H) || size_t(gw) * p > size_t(W))
@@ -253,8 +322,6 @@ int nos_image_patch_planes_u8(const void* img, void* planes, float* pixels, cons
   if (taps != TAPS || ytab != H || xtab != W) return fail("image_patch_planes: tap tables must be [H][9] and [W][9]");
   if (max_fh <= 0 || max_fw <= 0 || max_fh > FMAX || max_fw > FMAX || max_fh > h || max_fw > w)
     return fail("image_patch_planes: a patch's source footprint exceeds 72 rows or columns (scale above 4)");
-  ImgArgs k{};
-  k.img = static_cast<const uint8_t*>(img);
   k.planes = static_cast<__bf16*>(planes);
   k.pixels = pixels;
   k.yidx = yidx, k.ywt = ywt, k.xidx = xidx, k.xwt = xwt;
@@ -265,9 +332,86 @@ int nos_image_patch_planes_u8(const void* img, void* planes, float* pixels, cons
   k.GW = pixels ? (W + p - 1) / p : gw;
   const size_t tiles = size_t(B) * k.GH * k.GW;
   if (tiles > size_t(1) << 30) return fail("image_patch_planes: too many patches");
-  const int grid = int(wgs > 0 && size_t(wgs) < tiles ? size_t(wgs) : tiles);
+  grid = int(wgs > 0 && size_t(wgs) < tiles ? size_t(wgs) : tiles);
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+const char* nos_image_last_error() { return g_err.c_str(); }
+
+int nos_image_taps() { return TAPS; }
+int nos_image_max_footprint() { return FMAX; }
+int nos_image_max_patch() { return PMAX; }
+
+int nos_image_nv12_max_footprint() { return NV12_FMAX_W; }
+
+// img [B][h][w][3] uint8 -> planes [3][B*gh*gw][3*p*p] bf16 (and pixels [B][3][H][W] fp32 when
+// non-null). yidx [2][H] / xidx [2][W] (first source index, tap count) and ywt [H][taps] / xwt
+// [W][taps] are device tables; ytab / xtab are their row counts, max_fh / max_fw the largest source
+// footprint of one patch row / column of those tables (the host built them, so it knows). a, b:
+// host arrays of the three per-channel affine constants. wgs: workgroups (0 = one per tile).
+int nos_image_patch_planes_u8(const void* img, void* planes, float* pixels, const int* yidx, const float* ywt,
+                              const int* xidx, const float* xwt, int ytab, int xtab, int taps, int max_fh, int max_fw,
+                              const float* a, const float* b, int B, int h, int w, int H, int W, int p, int gh, int gw,
+                              int wgs, void* stream) {
+  if (!img) return fail("image_patch_planes: null operand");
+  ImgArgs k{};
+  int grid = 0;
+  if (const int rc = image_args(k, grid, planes, pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a, b,
+                                B, h, w, H, W, p, gh, gw, wgs))
+    return rc;
+  k.img = static_cast<const uint8_t*>(img);
   hipLaunchKernelGGL(image_patch_planes_u8, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k);
   return check("image_patch_planes_u8");
+}
+
+// The same from an NV12 frame: y [B][h][w] uint8 with row pitch y_pitch and batch stride y_bstride
+// (bytes), uv [B][(h+1)/2][(w+1)/2][2] uint8 (U, V) with uv_pitch and uv_bstride; [y_lo, y_hi) and
+// [uv_lo, uv_hi) are the first and one-past-last byte of the storage each plane lives in (the kernel
+// reads whole dwords where it can, and never outside them). table: 12 host integers, the 3 x 3 colour
+// matrix in 16.16 fixed point by rows (R, G, B) x (Y, U, V), each below 2^23 in size, then the offsets
+// of Y, U and V (0..255). The rest as nos_image_patch_planes_u8.
+int nos_image_patch_planes_nv12(const void* y, const void* y_lo, const void* y_hi, const void* uv, const void* uv_lo,
+                                const void* uv_hi, long long y_pitch, long long uv_pitch, long long y_bstride,
+                                long long uv_bstride, const int* table, void* planes, float* pixels, const int* yidx,
+                                const float* ywt, const int* xidx, const float* xwt, int ytab, int xtab, int taps,
+                                int max_fh, int max_fw, const float* a, const float* b, int B, int h, int w, int H, int W,
+                                int p, int gh, int gw, int wgs, void* stream) {
+  if (!y || !uv || !table) return fail("image_patch_planes: null operand");
+  ImgArgs k{};
+  int grid = 0;
+  if (const int rc = image_args(k, grid, planes, pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a, b,
+                                B, h, w, H, W, p, gh, gw, wgs))
+    return rc;
+  if (max_fw > NV12_FMAX_W) return fail("image_patch_planes_nv12: a patch's source footprint exceeds 69 columns");
+  const long long ch = (h + 1) / 2, cw2 = 2 * ((w + 1) / 2LL);
+  if (y_pitch < w) return fail("image_patch_planes_nv12: the Y pitch is smaller than the width");
+  if (uv_pitch < cw2) return fail("image_patch_planes_nv12: the UV pitch is smaller than 2 * ((w + 1) / 2)");
+  // the planes' first and one-past-last byte (a batch stride may be negative) inside the storage
+  const auto inside = [B](const void* ptr, const void* lo, const void* hi, long long bs, long long rows, long long pitch,
+                          long long rowbytes) {
+    const long long first = std::min(0LL, (B - 1) * bs), last = std::max(0LL, (B - 1) * bs) + (rows - 1) * pitch + rowbytes;
+    const intptr_t q = reinterpret_cast<intptr_t>(ptr);
+    return lo && hi && q + first >= reinterpret_cast<intptr_t>(lo) && q + last <= reinterpret_cast<intptr_t>(hi);
+  };
+  if (std::llabs(y_bstride) > (1LL << 40) || std::llabs(uv_bstride) > (1LL << 40) || y_pitch > (1LL << 30) ||
+      uv_pitch > (1LL << 30))
+    return fail("image_patch_planes_nv12: pitch or batch stride out of range");
+  if (!inside(y, y_lo, y_hi, y_bstride, h, y_pitch, w) || !inside(uv, uv_lo, uv_hi, uv_bstride, ch, uv_pitch, cw2))
+    return fail("image_patch_planes_nv12: a plane does not lie inside its storage bounds");
+  for (int i = 0; i < 12; ++i)
+    if (i < 9 ? std::abs(table[i]) >= (1 << 23) : (table[i] < 0 || table[i] > 255))
+      return fail("image_patch_planes_nv12: colour table: coefficients below 2^23 in size, offsets in 0..255");
+  Nv12Args n{};
+  n.y = static_cast<const uint8_t*>(y), n.uv = static_cast<const uint8_t*>(uv);
+  n.ylo = reinterpret_cast<uintptr_t>(y_lo), n.yhi = reinterpret_cast<uintptr_t>(y_hi);
+  n.uvlo = reinterpret_cast<uintptr_t>(uv_lo), n.uvhi = reinterpret_cast<uintptr_t>(uv_hi);
+  n.ypitch = y_pitch, n.uvpitch = uv_pitch, n.ybs = y_bstride, n.uvbs = uv_bstride;
+  for (int i = 0; i < 12; ++i) n.tab[i] = table[i];
+  hipLaunchKernelGGL(image_patch_planes_nv12, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, n);
+  return check("image_patch_planes_nv12");
 }
 
 // logits [B][M][C] fp32, boxes [B][M][4] fp32, target [B][2] fp32 (height, width), all on the device ->

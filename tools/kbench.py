@@ -12,7 +12,10 @@ layer (hipBLASLt via torch).
 the fused uint8 -> patch-planes kernel against the torch composition on the same GPU (``.float()``,
 antialiased ``F.interpolate``, the affine, ``K.patch_planes``), the detections kernel against the
 torch composition of the post-process, and ``detect_image`` against ``forward`` alone; the two sides
-of each pair alternate within the run and the median of the rounds is reported.
+of each pair alternate within the run and the median of the rounds is reported. NV12 rows (a decoder
+surface at a pitch of the width rounded up to 256, 480x640 and 1080x1920) time three ways to the same
+planes, alternating: (a) the fused NV12 launch, (b) the RGB kernel alone on the converted frame, (c)
+``nv12_to_rgb`` followed by the RGB kernel, which is what a pod without the fused path runs.
 """
 from __future__ import annotations
 
@@ -238,6 +241,24 @@ def image_bench(a) -> int:
         r[f"{name}_torch_us"] = round(statistics.median(t["torch"]), 1)
         r[f"{name}_rounds_us"] = {k: [round(v, 1) for v in vs] for k, vs in t.items()}
 
+    def triple(r, name, out, fused, rgb_only, convert_then_rgb, s, iters):
+        # five alternations: the spread of (b) within the run is what a difference (a) - (b) is read against
+        t = {"fused": [], "rgb_kernel": [], "convert_then_rgb": []}
+        for _ in range(5):
+            t["fused"].append(timeit(fused, s, iters))
+            t["rgb_kernel"].append(timeit(rgb_only, s, iters))
+            t["convert_then_rgb"].append(timeit(convert_then_rgb, s, iters))
+        r[f"{name}_target_hw"] = list(out)
+        for k, vs in t.items():
+            r[f"{name}_{k}_us"] = round(statistics.median(vs), 1)
+        r[f"{name}_rounds_us"] = {k: [round(v, 1) for v in vs] for k, vs in t.items()}
+
+    from walkai_nos_amd.models.workload.processor import Nv12
+    frames = {}
+    for h, w in ((480, 640), (1080, 1920)):
+        pitch = -(-w // 256) * 256
+        frames[f"{h}x{w}"] = Nv12.from_buffer(torch.randint(0, 256, (pitch * h * 3 // 2,), generator=g,
+                                                            dtype=torch.uint8).cuda(), h, w, pitch)
     results = []
     for prof, label in (("spx_nps1", "spx"), ("cpx_nps1", "cpx")):
         if label not in a.slices.split(","):
@@ -251,6 +272,14 @@ def image_bench(a) -> int:
             for name, img in imgs.items():
                 pair(r, f"preprocess_{name}", lambda: I.image_patch_planes(img, out_hw, 16, IMAGENET_MEAN, IMAGENET_STD),
                      lambda: torch_planes(img), s, a.iters)
+            for name, f in frames.items():
+                out = I.resize_size(tuple(f.y.shape), 800, 1333)
+                rgb = f.rgb()
+                triple(r, f"nv12_{name}", out,
+                       lambda: I.nv12_patch_planes(f.y, f.uv, out, 16, IMAGENET_MEAN, IMAGENET_STD),
+                       lambda: I.image_patch_planes(rgb, out, 16, IMAGENET_MEAN, IMAGENET_STD),
+                       lambda: I.image_patch_planes(I.nv12_to_rgb(f.y, f.uv), out, 16, IMAGENET_MEAN, IMAGENET_STD),
+                       s, a.iters)
             pair(r, "detections", lambda: I.detections(logits, boxes, target, 0.5),
                  lambda: I.detections_reference(logits, boxes, target, 0.5), s, a.iters)
             with torch.cuda.stream(s), torch.no_grad():

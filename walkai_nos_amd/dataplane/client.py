@@ -16,6 +16,8 @@ process's kernels run on) is taken while every pod is busy.  It prints one JSON 
 synthetic, ``--image-hw``) through the fused preprocess, the model and the detections kernel
 (``YolosSmall.detect_image``), all inside the warm-up and the captured graph; the JSON line then
 carries ``"end_to_end": true`` and ``"detections"``, the number of boxes above ``--threshold``.
+``--pixel-format nv12`` hands it what a video decoder does instead: one NV12 surface (Y rows, then UV
+rows, ``--pitch`` bytes apart), converted inside the same preprocess launch.
 """
 from __future__ import annotations
 
@@ -70,6 +72,10 @@ def main(argv=None) -> int:
     ap.add_argument("--image-hw", default="480,640", help="--end-to-end: the synthetic source image's height,width")
     ap.add_argument("--size", default="800,1333", help="--end-to-end: the processor's shortest,longest edge")
     ap.add_argument("--threshold", type=float, default=0.5, help="--end-to-end: detection score threshold")
+    ap.add_argument("--pixel-format", choices=("rgb", "nv12"), default="rgb",
+                    help="--end-to-end: interleaved RGB, or an NV12 decoder surface (even height)")
+    ap.add_argument("--pitch", type=int, default=0,
+                    help="--end-to-end, nv12: bytes between rows of the surface (default: the width rounded up to 256)")
     args = ap.parse_args(argv)
     t_boot = time.perf_counter()
     import torch
@@ -82,12 +88,17 @@ def main(argv=None) -> int:
     model = YolosSmall().to(dev).eval()
     seed = int(os.environ.get("NOS_POD_SEED", "0"))
     if args.end_to_end:
-        from ..models.workload.processor import YolosProcessor
+        from ..models.workload.processor import Nv12, YolosProcessor
         ih, iw = (int(v) for v in args.image_hw.split(","))
         shortest, longest = (int(v) for v in args.size.split(","))
         model.processor = YolosProcessor(shortest, longest, patch=model.c.patch_size)
-        img = torch.randint(0, 256, (ih, iw, 3), generator=torch.Generator().manual_seed(seed),
-                            dtype=torch.uint8).to(dev)
+        gen = torch.Generator().manual_seed(seed)
+        if args.pixel_format == "nv12":
+            pitch = args.pitch or -(-iw // 256) * 256
+            img = Nv12.from_buffer(torch.randint(0, 256, (pitch * (ih + ih // 2),), generator=gen,
+                                                 dtype=torch.uint8).to(dev), ih, iw, pitch)
+        else:
+            img = torch.randint(0, 256, (ih, iw, 3), generator=gen, dtype=torch.uint8).to(dev)
         hw = model.processor.size((ih, iw))
 
         def infer():
@@ -156,6 +167,7 @@ def main(argv=None) -> int:
     if args.end_to_end:
         out["end_to_end"] = True
         out["input_hw"] = list(hw)
+        out["pixel_format"] = args.pixel_format
         out["detections"] = int(res["count"].sum().item())   # of the last inference
     if census is not None:
         out["census"] = census

@@ -18,6 +18,14 @@ PyTorch reference math on the CPU and with the ``torch`` backend, the convention
 The resample is what ``F.interpolate(..., mode="bilinear", antialias=True, align_corners=False)``
 computes, which is PIL's ``BILINEAR`` resize in float. Unlike the ``transformers`` processor nothing
 is rounded to uint8 between the two passes, so pixels differ from it by less than one uint8 step.
+
+* :func:`nv12_to_rgb` / :func:`nv12_patch_planes` — the same from a video decoder's NV12 surface (a
+  full-resolution Y plane and a half-resolution interleaved UV plane, each with its own row pitch):
+  the colour conversion happens while the kernel stages a patch's source footprint, so no RGB frame
+  is materialised. The conversion is defined in integers (:func:`nv12_table`), so the fused result is
+  bit-equal to :func:`image_patch_planes` of :func:`nv12_to_rgb`. Chroma is taken nearest — luma
+  ``(r, c)`` uses chroma ``(r >> 1, c >> 1)``, what the usual one-call library conversions do;
+  bilinear chroma upsampling (and with it chroma siting) is not offered.
 """
 from __future__ import annotations
 
@@ -39,6 +47,8 @@ TAPS = 9
 MAX_SCALE = 4.0
 MAX_PATCH = 16
 MAX_FOOTPRINT = 72
+#: columns of a patch's footprint the NV12 staging loop takes (4-column groups in the same LDS row)
+NV12_MAX_FOOTPRINT = 69
 #: detections kernel limits: rows per image, classes with "no object"
 MAX_ROWS, MAX_CLASSES = 1024, 128
 
@@ -59,10 +69,14 @@ def _L() -> ctypes.CDLL:
             fp = ctypes.POINTER(ctypes.c_float)
             L.nos_image_patch_planes_u8.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, fp, fp,
                                                     i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+            i64 = ctypes.c_longlong
+            L.nos_image_patch_planes_nv12.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64,
+                                                      ctypes.POINTER(ctypes.c_int)] + \
+                L.nos_image_patch_planes_u8.argtypes[1:]
             L.nos_detections_f32.argtypes = [vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, vp, vp]
             L.nos_image_last_error.restype = ctypes.c_char_p
-            if (L.nos_image_taps(), L.nos_image_max_footprint(), L.nos_image_max_patch()) != \
-                    (TAPS, MAX_FOOTPRINT, MAX_PATCH):
+            if (L.nos_image_taps(), L.nos_image_max_footprint(), L.nos_image_max_patch(),
+                    L.nos_image_nv12_max_footprint()) != (TAPS, MAX_FOOTPRINT, MAX_PATCH, NV12_MAX_FOOTPRINT):
                 raise NativeUnavailable(f"{LIB} was built with other limits than ops/image.py expects")
             _lib = L
         return _lib
@@ -253,6 +267,110 @@ def image_patch_planes(img_u8: torch.Tensor, out_hw: Tuple[int, int], patch: int
                                         B, h, w, H, W, patch, gh, gw, image_wgs(),
                                         torch.cuda.current_stream().cuda_stream)
     _check(rc, "image_patch_planes")
+    return planes, pixels
+
+
+# ---- NV12 ---------------------------------------------------------------------------------------
+#: ``(Kr, Kb)`` of the luma equation ``Y = Kr R + Kg G + Kb B``
+NV12_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
+
+
+def nv12_real_matrix(matrix: str = "bt601", full_range: bool = False) -> Tuple[np.ndarray, Tuple[int, int, int]]:
+    """The conversion in real numbers, derived in fp64 from ``(Kr, Kb)``: ``(M [3, 3], offsets)`` with
+    ``rgb = M @ ((Y, U, V) - offsets)``. Limited range scales Y by 255/219 and chroma by 255/224 and
+    takes 16 from Y; both ranges take 128 from chroma."""
+    if matrix not in NV12_MATRICES:
+        raise ValueError(f"nv12: matrix {matrix!r} is none of {sorted(NV12_MATRICES)}")
+    kr, kb = NV12_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    sy, sc = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
+    m = np.array([[sy, 0.0, sc * 2.0 * (1.0 - kr)],
+                  [sy, -sc * 2.0 * kb * (1.0 - kb) / kg, -sc * 2.0 * kr * (1.0 - kr) / kg],
+                  [sy, sc * 2.0 * (1.0 - kb), 0.0]], dtype=np.float64)
+    return m, (0 if full_range else 16, 128, 128)
+
+
+def nv12_table(matrix: str = "bt601", full_range: bool = False) -> Tuple[int, ...]:
+    """The 12 integers both :func:`nv12_to_rgb` and the kernel compute with: the matrix of
+    :func:`nv12_real_matrix` as ``round(real * 2^16)`` by rows (R, G, B) x (Y, U, V), then the three
+    offsets. Channel ``c`` is ``clip((t[3c] (Y - t[9]) + t[3c+1] (U - t[10]) + t[3c+2] (V - t[11]) +
+    2^15) >> 16, 0, 255)``."""
+    m, off = nv12_real_matrix(matrix, full_range)
+    return tuple(int(v) for v in np.rint(m * 65536.0).astype(np.int64).reshape(-1)) + tuple(off)
+
+
+def nv12_planes(y: torch.Tensor, uv: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The two planes of an NV12 frame as ``[B, h, w]`` and ``[B, (h+1)//2, (w+1)//2, 2]`` views, checked:
+    uint8, one device, matching shapes, rows possibly pitched but contiguous inside."""
+    if not isinstance(y, torch.Tensor) or not isinstance(uv, torch.Tensor) or y.dtype != torch.uint8 \
+            or uv.dtype != torch.uint8:
+        raise ValueError("nv12: the Y and UV planes are uint8 tensors")
+    if y.dim() == 2 and uv.dim() == 3:
+        y, uv = y[None], uv[None]
+    if y.dim() != 3 or uv.dim() != 4 or 0 in y.shape:
+        raise ValueError("nv12: Y is [B, h, w] (or [h, w]) and UV [B, (h+1)//2, (w+1)//2, 2] (or without B)")
+    B, h, w = y.shape
+    if tuple(uv.shape) != (B, (h + 1) // 2, (w + 1) // 2, 2):
+        raise ValueError(f"nv12: a {h}x{w} Y plane takes a UV plane of shape "
+                         f"{(B, (h + 1) // 2, (w + 1) // 2, 2)}, not {tuple(uv.shape)}")
+    if y.device != uv.device:
+        raise ValueError(f"nv12: both planes on one device, not {y.device} and {uv.device}")
+    if (w > 1 and y.stride(2) != 1) or uv.stride(3) != 1 or (uv.shape[2] > 1 and uv.stride(2) != 2):
+        raise ValueError("nv12: rows may be pitched, but the bytes of a row are contiguous (U, V interleaved)")
+    return y, uv
+
+
+def nv12_to_rgb(y: torch.Tensor, uv: torch.Tensor, matrix: str = "bt601", full_range: bool = False) -> torch.Tensor:
+    """An NV12 frame as interleaved RGB, uint8 ``[B, h, w, 3]``: the definition of the conversion (and
+    what runs on the CPU, with the ``torch`` backend and past the kernel's limits). Nearest chroma,
+    exact int32 arithmetic on :func:`nv12_table`."""
+    y, uv = nv12_planes(y, uv)
+    t = nv12_table(matrix, full_range)
+    h, w = y.shape[1:]
+    rows, cols = torch.arange(h, device=y.device) >> 1, torch.arange(w, device=y.device) >> 1
+    # the largest term is below 2^25 (138 438 x 128, 76 309 x 255) and the sum below 2^27: int32 cannot overflow
+    yy = y.to(torch.int32) - t[9]
+    c = uv.to(torch.int32)[:, rows][:, :, cols]
+    u, v = c[..., 0] - t[10], c[..., 1] - t[11]
+    out = [(t[3 * k] * yy + t[3 * k + 1] * u + t[3 * k + 2] * v + 32768) >> 16 for k in range(3)]
+    return torch.stack(out, dim=-1).clamp_(0, 255).to(torch.uint8)
+
+
+def _storage_bounds(t: torch.Tensor) -> Tuple[int, int]:
+    s = t.untyped_storage()
+    return s.data_ptr(), s.data_ptr() + s.nbytes()
+
+
+def nv12_patch_planes(y: torch.Tensor, uv: torch.Tensor, out_hw: Tuple[int, int], patch: int, mean: Sequence[float],
+                      std: Sequence[float], matrix: str = "bt601", full_range: bool = False,
+                      want_pixels: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """:func:`image_patch_planes` of an NV12 frame (:func:`nv12_planes`' layout), bit-equal to
+    ``image_patch_planes(nv12_to_rgb(y, uv, matrix, full_range), ...)`` — which is what runs on a CPU
+    tensor, with the ``torch`` backend and past the kernel's limits. On the GPU one HIP launch reads
+    the two planes in place, by their strides: a pitched surface is not copied."""
+    y, uv = nv12_planes(y, uv)
+    table = nv12_table(matrix, full_range)
+    B, h, w = y.shape
+    H, W = int(out_hw[0]), int(out_hw[1])
+    tabs = None
+    if _use_hip(y) and fusable((h, w), (H, W), patch):
+        tabs = _device_tables(h, w, H, W, patch, y.device)
+    if tabs is None or tabs[5] > NV12_MAX_FOOTPRINT:
+        return image_patch_planes(nv12_to_rgb(y, uv, matrix, full_range), (H, W), patch, mean, std, want_pixels)
+    gh, gw = H // patch, W // patch
+    planes = torch.empty(3, B * gh * gw, 3 * patch * patch, dtype=torch.bfloat16, device=y.device)
+    pixels = torch.empty(B, 3, H, W, dtype=torch.float32, device=y.device) if want_pixels else None
+    yidx, ywt, xidx, xwt, max_fh, max_fw = tabs
+    a, b = affine(mean, std)
+    F3 = ctypes.c_float * 3
+    rc = _L().nos_image_patch_planes_nv12(y.data_ptr(), *_storage_bounds(y), uv.data_ptr(), *_storage_bounds(uv),
+                                          y.stride(1), uv.stride(1), y.stride(0), uv.stride(0),
+                                          (ctypes.c_int * 12)(*table), planes.data_ptr(),
+                                          pixels.data_ptr() if want_pixels else None, yidx.data_ptr(), ywt.data_ptr(),
+                                          xidx.data_ptr(), xwt.data_ptr(), ywt.shape[0], xwt.shape[0], ywt.shape[1],
+                                          max_fh, max_fw, F3(*a), F3(*b), B, h, w, H, W, patch, gh, gw, image_wgs(),
+                                          torch.cuda.current_stream().cuda_stream)
+    _check(rc, "nv12_patch_planes")
     return planes, pixels
 
 
