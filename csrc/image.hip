@@ -14,6 +14,12 @@
 //    them are read, converted to RGB by an integer matrix the host passes (nearest chroma: luma (r, c)
 //    takes chroma (r >> 1, c >> 1)) and written as RGB bytes into the same LDS tile; everything behind
 //    the staging loop is shared, so the result is bit-equal to the RGB kernel on the converted frame.
+//  * image_patch_planes_nv21 / _yuv420p / _packed3 / _packed4 — further staging loops of that body, one
+//    instantiation each (Src below): NV12 with V before U; planar 4:2:0 (I420 / YV12: three planes, each
+//    with its own pitch, batch stride and storage); and packed pixels of 3 or 4 bytes (RGB, BGR, RGBA,
+//    BGRA: the colour bytes at offsets the host passes, a fourth byte never read as colour) at any row
+//    pitch, batch stride and alignment, so a crop or a padded capture buffer is read in place. All of them
+//    write RGB bytes in column groups of 4 into the LDS tile, and share every pass behind it.
 //  * detections_f32 — softmax over the class logits, the best of the first L classes, the box in
 //    corner format scaled to the original image, and a stable compaction of the rows above the
 //    threshold; one workgroup per image, one wave per row.
@@ -59,9 +65,37 @@ struct Nv12Args {
   int tab[12];
 };
 
-// columns of an NV12 footprint are staged in groups of 4 (one dword of luma, one dword = two pairs of
-// chroma, three dwords of RGB): NG groups fit a row of the LDS tile, which covers any 69 columns
-constexpr int NG = RS / 12, NV12_FMAX_W = NG * 4 - 3;
+// One plane of a source that is read through pitches: p its first byte, [lo, hi) the storage it lives in
+// (no byte outside is read), pitch and bs the bytes between rows and between batch elements.
+struct PlaneArg {
+  const uint8_t* p;
+  uintptr_t lo, hi;
+  long long pitch, bs;
+};
+
+// Planar 4:2:0 (I420; YV12 is the same with u and v exchanged by the host): y [B][h][w], u and v
+// [B][(h+1)/2][(w+1)/2]; tab as in Nv12Args.
+struct PlanarArgs {
+  PlaneArg y, u, v;
+  int tab[12];
+};
+
+// Packed pixels [B][h][w][C], C = 3 or 4 by the instantiation: r, g, b are the byte offsets of red, green
+// and blue inside a pixel (0, 1, 2 for RGB and RGBA; 2, 1, 0 for BGR and BGRA).
+struct PackedArgs {
+  PlaneArg s;
+  int r, g, b;
+};
+
+// The source layouts, one instantiation of the body (and one __global__ entry) each. RGB: contiguous
+// [B][h][w][3], staged as whole rows of aligned dwords, footprints of up to FMAX = 72 columns. Every other
+// layout stages columns in groups of 4 (for 4:2:0 one dword of luma and the two chroma samples under it, for
+// packed pixels 12 or 16 source bytes; three dwords of RGB out): NG groups fit a row of the LDS tile, and
+// any GROUP_FMAX_W = 69 columns lie inside 18 consecutive groups wherever they start, so these layouts
+// cover footprints of up to 69 columns (scale 4 at patch 16); the host falls back past that.
+enum class Src { RGB, NV12, NV21, YUV420P, PACKED3, PACKED4 };
+constexpr int NG = RS / 12, GROUP_FMAX_W = NG * 4 - 3;
+constexpr int NV12_FMAX_W = GROUP_FMAX_W, YUV420P_FMAX_W = GROUP_FMAX_W, PACKED_FMAX_W = GROUP_FMAX_W;
 
 // four bytes at q, of which those inside [lo, hi) are read: one aligned dword where q allows it
 __device__ __forceinline__ uint32_t load4(uintptr_t q, uintptr_t lo, uintptr_t hi) {
@@ -71,6 +105,29 @@ __device__ __forceinline__ uint32_t load4(uintptr_t q, uintptr_t lo, uintptr_t h
   for (int k = 0; k < 4; ++k)
     if (q + k >= lo && q + k < hi) v |= uint32_t(*reinterpret_cast<const uint8_t*>(q + k)) << (8 * k);
   return v;
+}
+
+// NB bytes at any q into (NB + 3) / 4 dwords, lowest address first: load4 of the aligned dwords that hold
+// them (one more than the result when q's alignment makes the bytes straddle it), shifted into place. Only
+// bytes inside [lo, hi) are read; the others come out as zero.
+template <int NB>
+__device__ __forceinline__ void load_bytes(uint32_t* w, uintptr_t q, uintptr_t lo, uintptr_t hi) {
+  constexpr int N = (NB + 3) / 4;
+  const int sh = int(q & 3);
+  const uintptr_t q0 = q - sh;
+  uint32_t d[N + 1];
+#pragma unroll
+  for (int k = 0; k < N; ++k) d[k] = load4(q0 + 4 * k, lo, hi);
+  d[N] = sh + NB > 4 * N ? load4(q0 + 4 * N, lo, hi) : 0u;
+#pragma unroll
+  for (int k = 0; k < N; ++k) w[k] = uint32_t((uint64_t(d[k + 1]) << 32 | d[k]) >> (8 * sh));
+}
+
+// four pixels (R | G << 8 | B << 16 each) as the 12 RGB bytes of a column group in the LDS tile
+__device__ __forceinline__ void store_rgb4(uint32_t* dst, const uint32_t (&px)[4]) {
+  dst[0] = px[0] | px[1] << 24;
+  dst[1] = px[1] >> 8 | px[2] << 16;
+  dst[2] = px[2] >> 16 | px[3] << 8;
 }
 
 // one pixel's channel c as 8.16 fixed point clamped to [0, 256): exact in int32 (the largest term is below
@@ -85,8 +142,27 @@ __device__ __forceinline__ uint32_t nv12_channel(const int* t, int c, int y, int
                       0xffffff));
 }
 
-template <bool NV12>
-__device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const Nv12Args& n) {
+// Four columns of 4:2:0 as a column group of the LDS tile: yy their luma bytes, chroma(i, 0) and chroma(i, 1)
+// the U and V sample under columns 2i and 2i + 1 (nearest: luma (r, c) takes chroma (r >> 1, c >> 1)).
+template <class Chroma>
+__device__ __forceinline__ void yuv_to_rgb4(const int* tab, uint32_t yy, Chroma chroma, uint32_t* dst) {
+  uint32_t px[4];  // R | G << 8 | B << 16 of the group's four columns
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int y = int((yy >> (8 * k)) & 255) - tab[9];
+    const int u = int(chroma(k >> 1, 0)) - tab[10];
+    const int v = int(chroma(k >> 1, 1)) - tab[11];
+    px[k] = nv12_channel(tab, 0, y, u, v) >> 16 | (nv12_channel(tab, 1, y, u, v) >> 8 & 0xff00) |
+            (nv12_channel(tab, 2, y, u, v) & 0xff0000);
+  }
+  store_rgb4(dst, px);
+}
+
+// SrcArgs: what the layout's staging loop reads besides ImgArgs (Nv12Args, PlanarArgs, PackedArgs; the
+// contiguous RGB source is ImgArgs::img and takes an empty Nv12Args)
+template <Src S, class SrcArgs>
+__device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const SrcArgs& n) {
+  constexpr bool GROUPS = S != Src::RGB;
   __shared__ __attribute__((aligned(16))) uint8_t src[FMAX * RS];
   __shared__ float hz[FMAX * PMAX * 3];  // [footprint row][v][c]: the horizontally resampled rows
   __shared__ float wxs[PMAX * TAPS], wys[PMAX * TAPS];
@@ -105,9 +181,9 @@ __device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const 
     const int fh = fy1 - fy0, fw = fx1 - fx0;
     // the host checked the tables against these limits; a table that breaks them reads nothing
     if (fy0 < 0 || fx0 < 0 || fy1 > a.h || fx1 > a.w || fh <= 0 || fw <= 0 || fh > FMAX || fw > FMAX) continue;
-    // NV12: column groups of 4, the first one holding fx0; lead bytes of a row in LDS, groups per row
+    // all but RGB: column groups of 4, the first one holding fx0; lead bytes of a row in LDS, groups per row
     const int gx0 = fx0 >> 2, lead = (fx0 & 3) * 3, ng = ((fx1 - 1) >> 2) - gx0 + 1;
-    if (NV12 && ng > NG) continue;
+    if (GROUPS && ng > NG) continue;
     __syncthreads();  // the previous tile's readers are done with the LDS
     if (tid < ny * TAPS) wys[tid] = a.ywt[size_t(y0) * TAPS + tid];
     if (tid < nx * TAPS) wxs[tid] = a.xwt[size_t(x0) * TAPS + tid];
@@ -119,30 +195,48 @@ __device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const 
       xf[tid] = min(max(a.xidx[x0 + tid] - fx0, 0), fw - 1);
       xc[tid] = min(min(a.xidx[W + x0 + tid], TAPS), fw - xf[tid]);
     }
-    if constexpr (NV12) {
-      // stage the footprint as RGB bytes: thread (row r, group g) reads 4 luma bytes and the 2 chroma
-      // pairs under them, converts, and writes 12 bytes (columns outside the footprint, at the two
-      // ends of a row, get bytes no later pass reads; pitch padding can only land there)
+    if constexpr (GROUPS) {
+      // stage the footprint as RGB bytes: thread (row r, group g) reads the group's four columns, makes RGB
+      // of them and writes 12 bytes (columns outside the footprint, at the two ends of a row, get bytes no
+      // later pass reads; pitch padding, a neighbouring row's or another plane's bytes can only land there)
       for (int e = tid; e < fh * NG; e += 256) {
         const int r = e / NG, g = e % NG;
         if (g >= ng) continue;
         const int sy = fy0 + r, sx = (gx0 + g) * 4;
-        const uintptr_t qy = reinterpret_cast<uintptr_t>(n.y) + b * n.ybs + sy * n.ypitch + sx;
-        const uintptr_t qc = reinterpret_cast<uintptr_t>(n.uv) + b * n.uvbs + (sy >> 1) * n.uvpitch + sx;
-        const uint32_t yy = load4(qy, n.ylo, n.yhi), cc = load4(qc, n.uvlo, n.uvhi);
-        uint32_t px[4];  // R | G << 8 | B << 16 of the group's four columns
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int y = int((yy >> (8 * k)) & 255) - n.tab[9];
-          const int u = int((cc >> (16 * (k >> 1))) & 255) - n.tab[10];
-          const int v = int((cc >> (16 * (k >> 1) + 8)) & 255) - n.tab[11];
-          px[k] = nv12_channel(n.tab, 0, y, u, v) >> 16 | (nv12_channel(n.tab, 1, y, u, v) >> 8 & 0xff00) |
-                  (nv12_channel(n.tab, 2, y, u, v) & 0xff0000);
-        }
         uint32_t* dst = reinterpret_cast<uint32_t*>(src + r * RS + g * 12);
-        dst[0] = px[0] | px[1] << 24;
-        dst[1] = px[1] >> 8 | px[2] << 16;
-        dst[2] = px[2] >> 16 | px[3] << 8;
+        if constexpr (S == Src::NV12 || S == Src::NV21) {
+          // 4 luma bytes and the 2 chroma pairs under them; NV21 has V in a pair's first byte
+          constexpr int UB = S == Src::NV21 ? 8 : 0;
+          const uintptr_t qy = reinterpret_cast<uintptr_t>(n.y) + b * n.ybs + sy * n.ypitch + sx;
+          const uintptr_t qc = reinterpret_cast<uintptr_t>(n.uv) + b * n.uvbs + (sy >> 1) * n.uvpitch + sx;
+          const uint32_t yy = load4(qy, n.ylo, n.yhi), cc = load4(qc, n.uvlo, n.uvhi);
+          yuv_to_rgb4(n.tab, yy, [cc](int i, int v) { return (cc >> (16 * i + (v ? 8 - UB : UB))) & 255; }, dst);
+        } else if constexpr (S == Src::YUV420P) {
+          // 4 luma bytes, and 2 bytes of each chroma plane: every plane by its own pitch and batch stride
+          const uintptr_t qy = reinterpret_cast<uintptr_t>(n.y.p) + b * n.y.bs + sy * n.y.pitch + sx;
+          const uintptr_t qu = reinterpret_cast<uintptr_t>(n.u.p) + b * n.u.bs + (sy >> 1) * n.u.pitch + (sx >> 1);
+          const uintptr_t qv = reinterpret_cast<uintptr_t>(n.v.p) + b * n.v.bs + (sy >> 1) * n.v.pitch + (sx >> 1);
+          uint32_t uu, vv;
+          load_bytes<2>(&uu, qu, n.u.lo, n.u.hi);
+          load_bytes<2>(&vv, qv, n.v.lo, n.v.hi);
+          yuv_to_rgb4(n.tab, load4(qy, n.y.lo, n.y.hi),
+                      [uu, vv](int i, int v) { return ((v ? vv : uu) >> (8 * i)) & 255; }, dst);
+        } else {
+          // 4 pixels of C = 3 or 4 bytes: their 12 or 16 bytes from the row's aligned dwords, then the three
+          // colour bytes of each by their offsets in a pixel (a fourth byte is dropped here)
+          constexpr int C = S == Src::PACKED4 ? 4 : 3;
+          uint32_t w[C], px[4];
+          load_bytes<4 * C>(w, reinterpret_cast<uintptr_t>(n.s.p) + b * n.s.bs + sy * n.s.pitch + sx * C, n.s.lo,
+                            n.s.hi);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            uint32_t q;  // pixel k's bytes from bit 0
+            if constexpr (C == 4) q = w[k];
+            else q = k == 0 ? w[0] : k == 1 ? (w[0] >> 24 | w[1] << 8) : k == 2 ? (w[1] >> 16 | w[2] << 16) : w[2] >> 8;
+            px[k] = (q >> (8 * n.r) & 255) | (q >> (8 * n.g) & 255) << 8 | (q >> (8 * n.b) & 255) << 16;
+          }
+          store_rgb4(dst, px);
+        }
       }
     } else {
       // stage the footprint: aligned dwords of each global row (the row's own alignment kept in LDS)
@@ -170,7 +264,7 @@ __device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const 
       const int c = e % 3, v = (e / 3) % PMAX, r = e / (3 * PMAX);
       if (v >= nx) continue;
       int sh = lead;
-      if constexpr (!NV12) sh = int((lo + ((size_t(b) * a.h + fy0 + r) * a.w + fx0) * 3) & 3);
+      if constexpr (!GROUPS) sh = int((lo + ((size_t(b) * a.h + fy0 + r) * a.w + fx0) * 3) & 3);
       const uint8_t* s = src + r * RS + sh + xf[v] * 3 + c;
       const float* wt = wxs + v * TAPS;
       float acc = 0.f;
@@ -208,11 +302,27 @@ __device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const 
 }
 
 __global__ __launch_bounds__(256) void image_patch_planes_u8(ImgArgs a) {
-  image_patch_planes_body<false>(a, Nv12Args{});
+  image_patch_planes_body<Src::RGB>(a, Nv12Args{});
 }
 
 __global__ __launch_bounds__(256) void image_patch_planes_nv12(ImgArgs a, Nv12Args n) {
-  image_patch_planes_body<true>(a, n);
+  image_patch_planes_body<Src::NV12>(a, n);
+}
+
+__global__ __launch_bounds__(256) void image_patch_planes_nv21(ImgArgs a, Nv12Args n) {
+  image_patch_planes_body<Src::NV21>(a, n);
+}
+
+__global__ __launch_bounds__(256) void image_patch_planes_yuv420p(ImgArgs a, PlanarArgs n) {
+  image_patch_planes_body<Src::YUV420P>(a, n);
+}
+
+__global__ __launch_bounds__(256) void image_patch_planes_packed3(ImgArgs a, PackedArgs n) {
+  image_patch_planes_body<Src::PACKED3>(a, n);
+}
+
+__global__ __launch_bounds__(256) void image_patch_planes_packed4(ImgArgs a, PackedArgs n) {
+  image_patch_planes_body<Src::PACKED4>(a, n);
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -335,6 +445,63 @@ int image_args(ImgArgs& k, int& grid, void* planes, float* pixels, const int* yi
   grid = int(wgs > 0 && size_t(wgs) < tiles ? size_t(wgs) : tiles);
   return 0;
 }
+
+// a plane of B x rows x rowbytes at ptr (batch stride bs, possibly negative; row pitch) lies inside [lo, hi)
+bool inside(int B, const void* ptr, const void* lo, const void* hi, long long bs, long long rows, long long pitch,
+            long long rowbytes) {
+  const long long first = std::min(0LL, (B - 1) * bs), last = std::max(0LL, (B - 1) * bs) + (rows - 1) * pitch + rowbytes;
+  const intptr_t q = reinterpret_cast<intptr_t>(ptr);
+  return lo && hi && q + first >= reinterpret_cast<intptr_t>(lo) && q + last <= reinterpret_cast<intptr_t>(hi);
+}
+
+bool stride_range(long long pitch, long long bs) { return std::llabs(bs) <= (1LL << 40) && pitch <= (1LL << 30); }
+
+bool table_ok(const int* table) {
+  for (int i = 0; i < 12; ++i)
+    if (i < 9 ? std::abs(table[i]) >= (1 << 23) : (table[i] < 0 || table[i] > 255)) return false;
+  return true;
+}
+
+PlaneArg plane_arg(const void* p, const void* lo, const void* hi, long long pitch, long long bs) {
+  return PlaneArg{static_cast<const uint8_t*>(p), reinterpret_cast<uintptr_t>(lo), reinterpret_cast<uintptr_t>(hi), pitch,
+                  bs};
+}
+
+// both orders of the semi-planar entry: vu = 0 is NV12 (U, V), 1 is NV21 (V, U)
+int patch_planes_semiplanar(const void* y, const void* y_lo, const void* y_hi, const void* uv, const void* uv_lo,
+                            const void* uv_hi, long long y_pitch, long long uv_pitch, long long y_bstride,
+                            long long uv_bstride, const int* table, void* planes, float* pixels, const int* yidx,
+                            const float* ywt, const int* xidx, const float* xwt, int ytab, int xtab, int taps,
+                            int max_fh, int max_fw, const float* a, const float* b, int B, int h, int w, int H, int W,
+                            int p, int gh, int gw, int wgs, void* stream, int vu) {
+  if (!y || !uv || !table) return fail("image_patch_planes: null operand");
+  if (vu != 0 && vu != 1) return fail("image_patch_planes_nv12: the chroma order is 0 (U, V) or 1 (V, U)");
+  ImgArgs k{};
+  int grid = 0;
+  if (const int rc = image_args(k, grid, planes, pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a, b,
+                                B, h, w, H, W, p, gh, gw, wgs))
+    return rc;
+  if (max_fw > NV12_FMAX_W) return fail("image_patch_planes_nv12: a patch's source footprint exceeds 69 columns");
+  const long long ch = (h + 1) / 2, cw2 = 2 * ((w + 1) / 2LL);
+  if (y_pitch < w) return fail("image_patch_planes_nv12: the Y pitch is smaller than the width");
+  if (uv_pitch < cw2) return fail("image_patch_planes_nv12: the UV pitch is smaller than 2 * ((w + 1) / 2)");
+  if (!stride_range(y_pitch, y_bstride) || !stride_range(uv_pitch, uv_bstride))
+    return fail("image_patch_planes_nv12: pitch or batch stride out of range");
+  // the planes' first and one-past-last byte (a batch stride may be negative) inside the storage
+  if (!inside(B, y, y_lo, y_hi, y_bstride, h, y_pitch, w) || !inside(B, uv, uv_lo, uv_hi, uv_bstride, ch, uv_pitch, cw2))
+    return fail("image_patch_planes_nv12: a plane does not lie inside its storage bounds");
+  if (!table_ok(table))
+    return fail("image_patch_planes_nv12: colour table: coefficients below 2^23 in size, offsets in 0..255");
+  Nv12Args n{};
+  n.y = static_cast<const uint8_t*>(y), n.uv = static_cast<const uint8_t*>(uv);
+  n.ylo = reinterpret_cast<uintptr_t>(y_lo), n.yhi = reinterpret_cast<uintptr_t>(y_hi);
+  n.uvlo = reinterpret_cast<uintptr_t>(uv_lo), n.uvhi = reinterpret_cast<uintptr_t>(uv_hi);
+  n.ypitch = y_pitch, n.uvpitch = uv_pitch, n.ybs = y_bstride, n.uvbs = uv_bstride;
+  for (int i = 0; i < 12; ++i) n.tab[i] = table[i];
+  hipLaunchKernelGGL(vu ? image_patch_planes_nv21 : image_patch_planes_nv12, dim3(grid), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), k, n);
+  return check(vu ? "image_patch_planes_nv21" : "image_patch_planes_nv12");
+}
 }  // namespace
 
 extern "C" {
@@ -346,6 +513,8 @@ int nos_image_max_footprint() { return FMAX; }
 int nos_image_max_patch() { return PMAX; }
 
 int nos_image_nv12_max_footprint() { return NV12_FMAX_W; }
+int nos_image_yuv420p_max_footprint() { return YUV420P_FMAX_W; }
+int nos_image_packed_max_footprint() { return PACKED_FMAX_W; }
 
 // img [B][h][w][3] uint8 -> planes [3][B*gh*gw][3*p*p] bf16 (and pixels [B][3][H][W] fp32 when
 // non-null). yidx [2][H] / xidx [2][W] (first source index, tap count) and ywt [H][taps] / xwt
@@ -379,39 +548,94 @@ int nos_image_patch_planes_nv12(const void* y, const void* y_lo, const void* y_h
                                 const float* ywt, const int* xidx, const float* xwt, int ytab, int xtab, int taps,
                                 int max_fh, int max_fw, const float* a, const float* b, int B, int h, int w, int H, int W,
                                 int p, int gh, int gw, int wgs, void* stream) {
-  if (!y || !uv || !table) return fail("image_patch_planes: null operand");
+  return patch_planes_semiplanar(y, y_lo, y_hi, uv, uv_lo, uv_hi, y_pitch, uv_pitch, y_bstride, uv_bstride, table, planes,
+                                 pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a, b, B, h, w, H, W, p,
+                                 gh, gw, wgs, stream, 0);
+}
+
+// nos_image_patch_planes_nv12 with the order of a chroma pair as a trailing argument: vu = 0 for NV12 (U, V),
+// 1 for NV21 (V, U).
+int nos_image_patch_planes_nv12_order(const void* y, const void* y_lo, const void* y_hi, const void* uv,
+                                      const void* uv_lo, const void* uv_hi, long long y_pitch, long long uv_pitch,
+                                      long long y_bstride, long long uv_bstride, const int* table, void* planes,
+                                      float* pixels, const int* yidx, const float* ywt, const int* xidx,
+                                      const float* xwt, int ytab, int xtab, int taps, int max_fh, int max_fw,
+                                      const float* a, const float* b, int B, int h, int w, int H, int W, int p, int gh,
+                                      int gw, int wgs, void* stream, int vu) {
+  return patch_planes_semiplanar(y, y_lo, y_hi, uv, uv_lo, uv_hi, y_pitch, uv_pitch, y_bstride, uv_bstride, table, planes,
+                                 pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a, b, B, h, w, H, W, p,
+                                 gh, gw, wgs, stream, vu);
+}
+
+// The same from planar 4:2:0: y [B][h][w], u and v [B][(h+1)/2][(w+1)/2] uint8, each plane with its own row
+// pitch, batch stride (bytes) and storage bounds as in nos_image_patch_planes_nv12 (YV12: pass the planes by
+// what they hold, not by where they lie). table and the rest as there.
+int nos_image_patch_planes_yuv420p(const void* y, const void* y_lo, const void* y_hi, const void* u, const void* u_lo,
+                                   const void* u_hi, const void* v, const void* v_lo, const void* v_hi,
+                                   long long y_pitch, long long u_pitch, long long v_pitch, long long y_bstride,
+                                   long long u_bstride, long long v_bstride, const int* table, void* planes,
+                                   float* pixels, const int* yidx, const float* ywt, const int* xidx, const float* xwt,
+                                   int ytab, int xtab, int taps, int max_fh, int max_fw, const float* a, const float* b,
+                                   int B, int h, int w, int H, int W, int p, int gh, int gw, int wgs, void* stream) {
+  if (!y || !u || !v || !table) return fail("image_patch_planes: null operand");
   ImgArgs k{};
   int grid = 0;
   if (const int rc = image_args(k, grid, planes, pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a, b,
                                 B, h, w, H, W, p, gh, gw, wgs))
     return rc;
-  if (max_fw > NV12_FMAX_W) return fail("image_patch_planes_nv12: a patch's source footprint exceeds 69 columns");
-  const long long ch = (h + 1) / 2, cw2 = 2 * ((w + 1) / 2LL);
-  if (y_pitch < w) return fail("image_patch_planes_nv12: the Y pitch is smaller than the width");
-  if (uv_pitch < cw2) return fail("image_patch_planes_nv12: the UV pitch is smaller than 2 * ((w + 1) / 2)");
-  // the planes' first and one-past-last byte (a batch stride may be negative) inside the storage
-  const auto inside = [B](const void* ptr, const void* lo, const void* hi, long long bs, long long rows, long long pitch,
-                          long long rowbytes) {
-    const long long first = std::min(0LL, (B - 1) * bs), last = std::max(0LL, (B - 1) * bs) + (rows - 1) * pitch + rowbytes;
-    const intptr_t q = reinterpret_cast<intptr_t>(ptr);
-    return lo && hi && q + first >= reinterpret_cast<intptr_t>(lo) && q + last <= reinterpret_cast<intptr_t>(hi);
-  };
-  if (std::llabs(y_bstride) > (1LL << 40) || std::llabs(uv_bstride) > (1LL << 40) || y_pitch > (1LL << 30) ||
-      uv_pitch > (1LL << 30))
-    return fail("image_patch_planes_nv12: pitch or batch stride out of range");
-  if (!inside(y, y_lo, y_hi, y_bstride, h, y_pitch, w) || !inside(uv, uv_lo, uv_hi, uv_bstride, ch, uv_pitch, cw2))
-    return fail("image_patch_planes_nv12: a plane does not lie inside its storage bounds");
-  for (int i = 0; i < 12; ++i)
-    if (i < 9 ? std::abs(table[i]) >= (1 << 23) : (table[i] < 0 || table[i] > 255))
-      return fail("image_patch_planes_nv12: colour table: coefficients below 2^23 in size, offsets in 0..255");
-  Nv12Args n{};
-  n.y = static_cast<const uint8_t*>(y), n.uv = static_cast<const uint8_t*>(uv);
-  n.ylo = reinterpret_cast<uintptr_t>(y_lo), n.yhi = reinterpret_cast<uintptr_t>(y_hi);
-  n.uvlo = reinterpret_cast<uintptr_t>(uv_lo), n.uvhi = reinterpret_cast<uintptr_t>(uv_hi);
-  n.ypitch = y_pitch, n.uvpitch = uv_pitch, n.ybs = y_bstride, n.uvbs = uv_bstride;
+  if (max_fw > YUV420P_FMAX_W) return fail("image_patch_planes_yuv420p: a patch's source footprint exceeds 69 columns");
+  const long long ch = (h + 1) / 2, cw = (w + 1) / 2;
+  if (y_pitch < w) return fail("image_patch_planes_yuv420p: the Y pitch is smaller than the width");
+  if (u_pitch < cw) return fail("image_patch_planes_yuv420p: the U pitch is smaller than (w + 1) / 2");
+  if (v_pitch < cw) return fail("image_patch_planes_yuv420p: the V pitch is smaller than (w + 1) / 2");
+  if (!stride_range(y_pitch, y_bstride) || !stride_range(u_pitch, u_bstride) || !stride_range(v_pitch, v_bstride))
+    return fail("image_patch_planes_yuv420p: pitch or batch stride out of range");
+  if (!inside(B, y, y_lo, y_hi, y_bstride, h, y_pitch, w) || !inside(B, u, u_lo, u_hi, u_bstride, ch, u_pitch, cw) ||
+      !inside(B, v, v_lo, v_hi, v_bstride, ch, v_pitch, cw))
+    return fail("image_patch_planes_yuv420p: a plane does not lie inside its storage bounds");
+  if (!table_ok(table))
+    return fail("image_patch_planes_yuv420p: colour table: coefficients below 2^23 in size, offsets in 0..255");
+  PlanarArgs n{};
+  n.y = plane_arg(y, y_lo, y_hi, y_pitch, y_bstride);
+  n.u = plane_arg(u, u_lo, u_hi, u_pitch, u_bstride);
+  n.v = plane_arg(v, v_lo, v_hi, v_pitch, v_bstride);
   for (int i = 0; i < 12; ++i) n.tab[i] = table[i];
-  hipLaunchKernelGGL(image_patch_planes_nv12, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, n);
-  return check("image_patch_planes_nv12");
+  hipLaunchKernelGGL(image_patch_planes_yuv420p, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, n);
+  return check("image_patch_planes_yuv420p");
+}
+
+// The same from packed pixels: img [B][h][w][C] uint8 with row pitch and batch stride in bytes (any pitch >=
+// w * C, any alignment of the first byte, the batch stride possibly negative) inside the storage [lo, hi).
+// order: "rgb", "bgr" (C = 3), "rgba" or "bgra" (C = 4; the fourth byte is never read as colour). A crop or
+// a padded capture buffer is read in place. The rest as nos_image_patch_planes_u8.
+int nos_image_patch_planes_packed(const void* img, const void* lo, const void* hi, long long pitch, long long bstride,
+                                  const char* order, void* planes, float* pixels, const int* yidx, const float* ywt,
+                                  const int* xidx, const float* xwt, int ytab, int xtab, int taps, int max_fh,
+                                  int max_fw, const float* a, const float* b, int B, int h, int w, int H, int W, int p,
+                                  int gh, int gw, int wgs, void* stream) {
+  if (!img || !order) return fail("image_patch_planes: null operand");
+  const std::string o(order);
+  if (o != "rgb" && o != "bgr" && o != "rgba" && o != "bgra")
+    return fail("image_patch_planes_packed: unknown channel order (rgb, bgr, rgba or bgra)");
+  const int C = int(o.size());
+  ImgArgs k{};
+  int grid = 0;
+  if (const int rc = image_args(k, grid, planes, pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a, b,
+                                B, h, w, H, W, p, gh, gw, wgs))
+    return rc;
+  if (max_fw > PACKED_FMAX_W) return fail("image_patch_planes_packed: a patch's source footprint exceeds 69 columns");
+  if (pitch < (long long)w * C) return fail("image_patch_planes_packed: the row pitch is smaller than a row's bytes");
+  if (!stride_range(pitch, bstride)) return fail("image_patch_planes_packed: pitch or batch stride out of range");
+  if (!inside(B, img, lo, hi, bstride, h, pitch, (long long)w * C))
+    return fail("image_patch_planes_packed: the image does not lie inside its storage bounds");
+  PackedArgs n{};
+  n.s = plane_arg(img, lo, hi, pitch, bstride);
+  n.r = o[0] == 'r' ? 0 : 2, n.g = 1, n.b = 2 - n.r;
+  if (C == 4)
+    hipLaunchKernelGGL(image_patch_planes_packed4, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, n);
+  else
+    hipLaunchKernelGGL(image_patch_planes_packed3, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, n);
+  return check("image_patch_planes_packed");
 }
 
 // logits [B][M][C] fp32, boxes [B][M][4] fp32, target [B][2] fp32 (height, width), all on the device ->

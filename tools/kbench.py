@@ -15,7 +15,9 @@ torch composition of the post-process, and ``detect_image`` against ``forward`` 
 of each pair alternate within the run and the median of the rounds is reported. NV12 rows (a decoder
 surface at a pitch of the width rounded up to 256, 480x640 and 1080x1920) time three ways to the same
 planes, alternating: (a) the fused NV12 launch, (b) the RGB kernel alone on the converted frame, (c)
-``nv12_to_rgb`` followed by the RGB kernel, which is what a pod without the fused path runs.
+``nv12_to_rgb`` followed by the RGB kernel, which is what a pod without the fused path runs. The other
+layouts of the same picture (``nv21_*``, ``i420_*``, ``bgr_*``, ``rgba_*``, ``bgra_*``, and ``rgbcrop_*``: RGB
+rows at a padded pitch, read in place against ``.contiguous()`` first) are timed as the same triple.
 """
 from __future__ import annotations
 
@@ -253,12 +255,29 @@ def image_bench(a) -> int:
             r[f"{name}_{k}_us"] = round(statistics.median(vs), 1)
         r[f"{name}_rounds_us"] = {k: [round(v, 1) for v in vs] for k, vs in t.items()}
 
-    from walkai_nos_amd.models.workload.processor import Nv12
-    frames = {}
+    from walkai_nos_amd.models.workload.processor import Nv12, Packed, Yuv420p
+    frames, layouts = {}, {}
     for h, w in ((480, 640), (1080, 1920)):
         pitch = -(-w // 256) * 256
-        frames[f"{h}x{w}"] = Nv12.from_buffer(torch.randint(0, 256, (pitch * h * 3 // 2,), generator=g,
-                                                            dtype=torch.uint8).cuda(), h, w, pitch)
+        surface = torch.randint(0, 256, (pitch * h * 3 // 2,), generator=g, dtype=torch.uint8).cuda()
+        frames[f"{h}x{w}"] = Nv12.from_buffer(surface, h, w, pitch)
+        # the other layouts: the same surface read as NV21 and as I420, and its picture as packed pixels (BGR
+        # and RGBA rows side by side, BGRA and RGB in a buffer whose rows are padded to a multiple of 256 bytes)
+        rgb = frames[f"{h}x{w}"].rgb()
+        alpha = torch.randint(0, 256, (1, h, w, 1), generator=g, dtype=torch.uint8).cuda()
+
+        def padded(img):
+            rb = img.shape[2] * img.shape[3]
+            buf = torch.zeros(h, -(-rb // 256) * 256, dtype=torch.uint8, device="cuda")
+            view = buf[:, :rb].unflatten(1, img.shape[2:])[None]
+            view.copy_(img)
+            return view
+        layouts[f"{h}x{w}"] = {"nv21": Nv12.from_buffer(surface, h, w, pitch, vu=True),
+                               "i420": Yuv420p.from_buffer(surface, h, w, pitch),
+                               "bgr": Packed(rgb[..., [2, 1, 0]].contiguous(), "bgr"),
+                               "rgba": Packed(torch.cat((rgb, alpha), dim=-1), "rgba"),
+                               "bgra": Packed(padded(torch.cat((rgb[..., [2, 1, 0]], alpha), dim=-1)), "bgra"),
+                               "rgbcrop": Packed(padded(rgb), "rgb")}
     results = []
     for prof, label in (("spx_nps1", "spx"), ("cpx_nps1", "cpx")):
         if label not in a.slices.split(","):
@@ -280,6 +299,13 @@ def image_bench(a) -> int:
                        lambda: I.image_patch_planes(rgb, out, 16, IMAGENET_MEAN, IMAGENET_STD),
                        lambda: I.image_patch_planes(I.nv12_to_rgb(f.y, f.uv), out, 16, IMAGENET_MEAN, IMAGENET_STD),
                        s, a.iters)
+                for layout, fr in layouts[name].items():
+                    conv = fr.rgb()
+                    triple(r, f"{layout}_{name}", out,
+                           lambda: fr.patch_planes(out, 16, IMAGENET_MEAN, IMAGENET_STD),
+                           lambda: I.image_patch_planes(conv, out, 16, IMAGENET_MEAN, IMAGENET_STD),
+                           lambda: I.image_patch_planes(fr.rgb(), out, 16, IMAGENET_MEAN, IMAGENET_STD),
+                           s, a.iters)
             pair(r, "detections", lambda: I.detections(logits, boxes, target, 0.5),
                  lambda: I.detections_reference(logits, boxes, target, 0.5), s, a.iters)
             with torch.cuda.stream(s), torch.no_grad():

@@ -17,7 +17,10 @@ synthetic, ``--image-hw``) through the fused preprocess, the model and the detec
 (``YolosSmall.detect_image``), all inside the warm-up and the captured graph; the JSON line then
 carries ``"end_to_end": true`` and ``"detections"``, the number of boxes above ``--threshold``.
 ``--pixel-format nv12`` hands it what a video decoder does instead: one NV12 surface (Y rows, then UV
-rows, ``--pitch`` bytes apart), converted inside the same preprocess launch.
+rows, ``--pitch`` bytes apart), converted inside the same preprocess launch. ``nv21`` is that with V first;
+``i420`` / ``yv12`` a software decoder's planar surface (Y rows at ``--pitch``, then the two chroma planes at
+half of it); ``bgr``, ``rgba`` and ``bgra`` packed pixels as OpenCV or a compositor hands them out. ``--pitch``
+applies to every format (for the packed ones and ``rgb`` it is the bytes between rows of a padded buffer).
 """
 from __future__ import annotations
 
@@ -72,10 +75,11 @@ def main(argv=None) -> int:
     ap.add_argument("--image-hw", default="480,640", help="--end-to-end: the synthetic source image's height,width")
     ap.add_argument("--size", default="800,1333", help="--end-to-end: the processor's shortest,longest edge")
     ap.add_argument("--threshold", type=float, default=0.5, help="--end-to-end: detection score threshold")
-    ap.add_argument("--pixel-format", choices=("rgb", "nv12"), default="rgb",
-                    help="--end-to-end: interleaved RGB, or an NV12 decoder surface (even height)")
+    ap.add_argument("--pixel-format", choices=("rgb", "bgr", "rgba", "bgra", "nv12", "nv21", "i420", "yv12"),
+                    default="rgb", help="--end-to-end: packed pixels, or a decoder's 4:2:0 surface (even height)")
     ap.add_argument("--pitch", type=int, default=0,
-                    help="--end-to-end, nv12: bytes between rows of the surface (default: the width rounded up to 256)")
+                    help="--end-to-end: bytes between rows of the surface (default: the width rounded up to 256 for "
+                         "the 4:2:0 formats, rows side by side for the packed ones)")
     args = ap.parse_args(argv)
     t_boot = time.perf_counter()
     import torch
@@ -88,17 +92,28 @@ def main(argv=None) -> int:
     model = YolosSmall().to(dev).eval()
     seed = int(os.environ.get("NOS_POD_SEED", "0"))
     if args.end_to_end:
-        from ..models.workload.processor import Nv12, YolosProcessor
+        from ..models.workload.processor import Nv12, Packed, YolosProcessor, Yuv420p
         ih, iw = (int(v) for v in args.image_hw.split(","))
         shortest, longest = (int(v) for v in args.size.split(","))
         model.processor = YolosProcessor(shortest, longest, patch=model.c.patch_size)
         gen = torch.Generator().manual_seed(seed)
-        if args.pixel_format == "nv12":
+        fmt = args.pixel_format
+        if fmt in ("nv12", "nv21", "i420", "yv12"):
             pitch = args.pitch or -(-iw // 256) * 256
-            img = Nv12.from_buffer(torch.randint(0, 256, (pitch * (ih + ih // 2),), generator=gen,
-                                                 dtype=torch.uint8).to(dev), ih, iw, pitch)
-        else:
+            buf = torch.randint(0, 256, (pitch * (ih + ih // 2),), generator=gen, dtype=torch.uint8).to(dev)
+            if fmt in ("nv12", "nv21"):
+                img = Nv12.from_buffer(buf, ih, iw, pitch, vu=fmt == "nv21")
+            else:
+                img = Yuv420p.from_buffer(buf, ih, iw, pitch, order=fmt)
+        elif fmt == "rgb" and not args.pitch:
             img = torch.randint(0, 256, (ih, iw, 3), generator=gen, dtype=torch.uint8).to(dev)
+        else:
+            C = len(fmt)
+            pitch = args.pitch or iw * C
+            if pitch < iw * C:
+                ap.error(f"--pitch {pitch} is smaller than a row of {iw} {fmt} pixels")
+            buf = torch.randint(0, 256, (ih * pitch,), generator=gen, dtype=torch.uint8).to(dev)
+            img = Packed(buf.as_strided((ih, iw, C), (pitch, C, 1)), fmt)
         hw = model.processor.size((ih, iw))
 
         def infer():

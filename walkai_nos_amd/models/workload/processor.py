@@ -14,11 +14,16 @@ pixel mask, because one call runs images of one size.
 A video decoder's NV12 surface goes in as :class:`Nv12` wherever an image does: the colour conversion
 (BT.601 or BT.709, limited or full range, in exact integers: ``ops.image.nv12_to_rgb``) is fused into
 the same launch. It takes chroma nearest — luma ``(r, c)`` uses chroma ``(r >> 1, c >> 1)``, as the
-usual one-call library conversions do; bilinear chroma upsampling is not offered.
+usual one-call library conversions do; bilinear chroma upsampling is not offered. NV21 is the same class
+with ``vu=True``; a software decoder's planar I420 / YV12 surface is :class:`Yuv420p`; OpenCV's BGR, a
+compositor's RGBA / BGRA, and any of them (or RGB) as a crop or with padded rows is :class:`Packed` — a
+non-contiguous RGB view may also be passed as it is. None of them is copied or converted first: every
+layout has its staging loop in the one kernel, and equals the RGB path on the converted frame bit for bit.
+All of them are a :class:`Frame`, which is all the processor and the model know about them.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -30,15 +35,61 @@ IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 
 
+class Frame:
+    """An image batch of one size that is not a plain interleaved RGB tensor: what the processor and the model
+    ask of it. A subclass is a frozen dataclass whose tensor fields are named in ``PLANES`` and answers
+    :meth:`shape`, :meth:`rgb` and :meth:`patch_planes`. The buffers are held as they are given — a captured
+    graph reads them by address."""
+    PLANES: Tuple[str, ...] = ()
+
+    @property
+    def shape(self) -> Tuple[int, int, int, int]:
+        """``(B, h, w, 3)``: the shape of the RGB batch this frame stands for."""
+        raise NotImplementedError
+
+    def rgb(self) -> torch.Tensor:
+        """The frame converted: contiguous uint8 ``[B, h, w, 3]``."""
+        raise NotImplementedError
+
+    def patch_planes(self, hw: Tuple[int, int], patch: int, mean: Sequence[float], std: Sequence[float],
+                     want_pixels: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """``ops.image.image_patch_planes`` of :meth:`rgb`, by this layout's fused launch."""
+        raise NotImplementedError
+
+    @property
+    def device(self) -> torch.device:
+        return getattr(self, self.PLANES[0]).device
+
+    @property
+    def is_cuda(self) -> bool:
+        return getattr(self, self.PLANES[0]).is_cuda
+
+    def to(self, device) -> "Frame":
+        """On ``device``; the same object (and the same buffers) when it is there already."""
+        if device is None or self.device == torch.device(device):
+            return self
+        return replace(self, **{k: getattr(self, k).to(device) for k in self.PLANES})
+
+
+def _buffer(buf: Any, who: str) -> torch.Tensor:
+    t = torch.from_numpy(buf) if isinstance(buf, np.ndarray) else buf
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous():
+        raise ValueError(f"{who}: a contiguous uint8 tensor or ndarray")
+    return t
+
+
 @dataclass(frozen=True)
-class Nv12:
+class Nv12(Frame):
     """An NV12 frame (or a batch of one size): ``y`` uint8 ``[h, w]`` or ``[B, h, w]``, ``uv`` uint8
     ``[(h+1)//2, (w+1)//2, 2]`` (U, V) with the same leading ``B``; rows may be pitched. The planes are
-    held as they are given — a captured graph reads them by address."""
+    held as they are given — a captured graph reads them by address. ``vu``: the chroma pairs are (V, U),
+    which makes it NV21."""
     y: torch.Tensor
     uv: torch.Tensor
     matrix: str = "bt601"
     full_range: bool = False
+    vu: bool = False
+    PLANES = ("y", "uv")
 
     def __post_init__(self):
         I.nv12_planes(self.y, self.uv)
@@ -46,13 +97,11 @@ class Nv12:
 
     @classmethod
     def from_buffer(cls, buf: Any, h: int, w: int, pitch: Optional[int] = None, matrix: str = "bt601",
-                    full_range: bool = False) -> "Nv12":
+                    full_range: bool = False, vu: bool = False) -> "Nv12":
         """A decoder's single surface — ``h`` rows of Y, then ``h / 2`` rows of UV, all ``pitch`` bytes
         apart (default ``w``) — as the two planes, without a copy. ``buf``: a contiguous uint8 tensor or
         ndarray of at least ``(3 h / 2 - 1) * pitch + 2 * ((w + 1) // 2)`` bytes."""
-        t = torch.from_numpy(buf) if isinstance(buf, np.ndarray) else buf
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous():
-            raise ValueError("Nv12.from_buffer: a contiguous uint8 tensor or ndarray")
+        t = _buffer(buf, "Nv12.from_buffer")
         h, w = int(h), int(w)
         pitch = w if pitch is None else int(pitch)
         cw2 = 2 * ((w + 1) // 2)
@@ -65,35 +114,127 @@ class Nv12:
             raise ValueError(f"Nv12.from_buffer: {h}x{w} at pitch {pitch} takes {need} bytes, the buffer has {t.numel()}")
         off = t.storage_offset()
         return cls(t.as_strided((h, w), (pitch, 1), off),
-                   t.as_strided((h // 2, cw2 // 2, 2), (pitch, 2, 1), off + h * pitch), matrix, full_range)
+                   t.as_strided((h // 2, cw2 // 2, 2), (pitch, 2, 1), off + h * pitch), matrix, full_range, vu)
 
     def batched(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(y [B, h, w], uv [B, ch, cw, 2])`` views."""
         return I.nv12_planes(self.y, self.uv)
 
-    # what the processor and the model ask of an image batch
     @property
     def shape(self) -> Tuple[int, int, int, int]:
-        """``(B, h, w, 3)``: the shape of the RGB batch this frame stands for."""
         return tuple(self.batched()[0].shape) + (3,)
-
-    @property
-    def device(self) -> torch.device:
-        return self.y.device
-
-    @property
-    def is_cuda(self) -> bool:
-        return self.y.is_cuda
-
-    def to(self, device) -> "Nv12":
-        """On ``device``; the same object (and the same buffers) when it is there already."""
-        if device is None or self.y.device == torch.device(device):
-            return self
-        return Nv12(self.y.to(device), self.uv.to(device), self.matrix, self.full_range)
 
     def rgb(self) -> torch.Tensor:
         """The frame converted: uint8 ``[B, h, w, 3]`` (``ops.image.nv12_to_rgb``)."""
+        if self.vu:
+            return I.nv12_to_rgb(self.y, self.uv, self.matrix, self.full_range, vu=True)
         return I.nv12_to_rgb(self.y, self.uv, self.matrix, self.full_range)
+
+    def patch_planes(self, hw, patch, mean, std, want_pixels=False):
+        if self.vu:
+            return I.nv12_patch_planes(self.y, self.uv, hw, patch, mean, std, self.matrix, self.full_range,
+                                       want_pixels, vu=True)
+        return I.nv12_patch_planes(self.y, self.uv, hw, patch, mean, std, self.matrix, self.full_range, want_pixels)
+
+
+@dataclass(frozen=True)
+class Yuv420p(Frame):
+    """A planar 4:2:0 frame (or a batch of one size): ``y`` uint8 ``[h, w]`` or ``[B, h, w]``, ``u`` and ``v``
+    uint8 ``[(h+1)//2, (w+1)//2]`` with the same leading ``B``; every plane may have its own row pitch. The
+    fields say what a plane holds, not where it lies: for YV12 pass the second plane of the surface as ``u``."""
+    y: torch.Tensor
+    u: torch.Tensor
+    v: torch.Tensor
+    matrix: str = "bt601"
+    full_range: bool = False
+    PLANES = ("y", "u", "v")
+
+    def __post_init__(self):
+        I.yuv420_planes(self.y, self.u, self.v)
+        I.nv12_table(self.matrix, self.full_range)
+
+    @classmethod
+    def from_buffer(cls, buf: Any, h: int, w: int, pitch: Optional[int] = None, chroma_pitch: Optional[int] = None,
+                    order: str = "i420", matrix: str = "bt601", full_range: bool = False) -> "Yuv420p":
+        """A software decoder's single surface — ``h`` rows of Y ``pitch`` bytes apart (default ``w``), then
+        ``h / 2`` rows of the first chroma plane ``chroma_pitch`` apart (default ``pitch // 2``), then the
+        second chroma plane — as the three planes, without a copy. ``order``: ``i420`` has U first, ``yv12``
+        V first. ``buf``: a contiguous uint8 tensor or ndarray that holds all of it."""
+        t = _buffer(buf, "Yuv420p.from_buffer")
+        h, w = int(h), int(w)
+        if order not in ("i420", "yv12"):
+            raise ValueError(f"Yuv420p.from_buffer: order {order!r} is neither 'i420' nor 'yv12'")
+        if h <= 0 or w <= 0 or h % 2:
+            raise ValueError("Yuv420p.from_buffer: positive sizes and an even height (chroma rows follow the Y rows)")
+        pitch = w if pitch is None else int(pitch)
+        cpitch = pitch // 2 if chroma_pitch is None else int(chroma_pitch)
+        cw, ch = (w + 1) // 2, h // 2
+        if pitch < w:
+            raise ValueError(f"Yuv420p.from_buffer: pitch {pitch} is smaller than a row of {w} pixels")
+        if cpitch < cw:
+            raise ValueError(f"Yuv420p.from_buffer: chroma pitch {cpitch} is smaller than a chroma row of {cw} bytes")
+        need = h * pitch + (2 * ch - 1) * cpitch + cw
+        if t.numel() < need:
+            raise ValueError(f"Yuv420p.from_buffer: {h}x{w} at pitches {pitch} and {cpitch} takes {need} bytes, "
+                             f"the buffer has {t.numel()}")
+        off = t.storage_offset()
+        first = t.as_strided((ch, cw), (cpitch, 1), off + h * pitch)
+        second = t.as_strided((ch, cw), (cpitch, 1), off + h * pitch + ch * cpitch)
+        u, v = (first, second) if order == "i420" else (second, first)
+        return cls(t.as_strided((h, w), (pitch, 1), off), u, v, matrix, full_range)
+
+    def batched(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``(y [B, h, w], u [B, ch, cw], v [B, ch, cw])`` views."""
+        return I.yuv420_planes(self.y, self.u, self.v)
+
+    @property
+    def shape(self) -> Tuple[int, int, int, int]:
+        return tuple(self.batched()[0].shape) + (3,)
+
+    def rgb(self) -> torch.Tensor:
+        """The frame converted: uint8 ``[B, h, w, 3]`` (``ops.image.yuv420_to_rgb``)."""
+        return I.yuv420_to_rgb(self.y, self.u, self.v, self.matrix, self.full_range)
+
+    def patch_planes(self, hw, patch, mean, std, want_pixels=False):
+        return I.yuv420p_patch_planes(self.y, self.u, self.v, hw, patch, mean, std, self.matrix, self.full_range,
+                                      want_pixels)
+
+
+@dataclass(frozen=True)
+class Packed(Frame):
+    """Packed pixels in another order or at another pitch than a plain RGB tensor: ``data`` uint8 ``[h, w, C]``
+    or ``[B, h, w, C]`` in ``order`` (``rgb``, ``bgr``: C = 3; ``rgba``, ``bgra``: C = 4, the fourth byte
+    ignored). The bytes of a row are contiguous; rows and images lie wherever their strides put them, so a
+    crop of a larger frame or a capture buffer with padded rows is read in place."""
+    data: torch.Tensor
+    order: str = "rgb"
+    PLANES = ("data",)
+
+    def __post_init__(self):
+        if self.order not in I.PACKED_ORDERS:
+            raise ValueError(f"Packed: channel order {self.order!r} is none of {sorted(I.PACKED_ORDERS)}")
+        C = I.PACKED_ORDERS[self.order][0]
+        d = self.data
+        if not isinstance(d, torch.Tensor) or d.dtype != torch.uint8 or d.dim() not in (3, 4) or d.shape[-1] != C \
+                or 0 in d.shape:
+            raise ValueError(f"Packed: {self.order} takes a uint8 [h, w, {C}] or [B, h, w, {C}] tensor")
+        if not I._packed_strides(self.batched()):
+            raise ValueError("Packed: rows may be pitched, but the bytes of a row are contiguous")
+
+    def batched(self) -> torch.Tensor:
+        """The ``[B, h, w, C]`` view."""
+        return self.data if self.data.dim() == 4 else self.data[None]
+
+    @property
+    def shape(self) -> Tuple[int, int, int, int]:
+        return tuple(self.batched().shape[:3]) + (3,)
+
+    def rgb(self) -> torch.Tensor:
+        """The colour bytes re-ordered: contiguous uint8 ``[B, h, w, 3]`` (``ops.image.packed_to_rgb``)."""
+        return I.packed_to_rgb(self.batched(), self.order)
+
+    def patch_planes(self, hw, patch, mean, std, want_pixels=False):
+        return I.packed_patch_planes(self.batched(), self.order, hw, patch, mean, std, want_pixels)
 
 
 class YolosProcessor:
@@ -109,8 +250,9 @@ class YolosProcessor:
     @staticmethod
     def as_batch(image: Any, device: Optional[torch.device] = None) -> torch.Tensor:
         """A uint8 ``[B, h, w, 3]`` tensor from a uint8 HWC (or BHWC) tensor or ndarray, or a PIL image;
-        an :class:`Nv12` frame stays one (it answers ``shape``, ``device`` and ``is_cuda`` as the batch would)."""
-        if isinstance(image, Nv12):
+        a :class:`Frame` (:class:`Nv12`, :class:`Yuv420p`, :class:`Packed`) stays one (it answers ``shape``,
+        ``device`` and ``is_cuda`` as the batch would)."""
+        if isinstance(image, Frame):
             return image.to(device)
         if not isinstance(image, (torch.Tensor, np.ndarray)):
             try:
@@ -133,16 +275,17 @@ class YolosProcessor:
         hw = self.size(tuple(img.shape[1:3]))
         if img.is_cuda:
             return self.patch_planes(img, hw, want_pixels=True)[1]
-        return I.pixels_reference(img.rgb() if isinstance(img, Nv12) else img, hw, self.mean, self.std)
+        return I.pixels_reference(img.rgb() if isinstance(img, Frame) else img, hw, self.mean, self.std)
 
-    def patch_planes(self, img: Any, hw: Tuple[int, int], want_pixels: bool = False) \
+    def patch_planes(self, img: Any, hw: Tuple[int, int], want_pixels: bool = False, patch: Optional[int] = None) \
             -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """The x3 planes of the patch matrix (and the pixels on request) of :meth:`as_batch`'s result,
-        resized to ``hw``: ``ops.image.image_patch_planes``, or ``nv12_patch_planes`` for an :class:`Nv12`."""
-        if isinstance(img, Nv12):
-            return I.nv12_patch_planes(img.y, img.uv, hw, self.patch, self.mean, self.std, img.matrix,
-                                       img.full_range, want_pixels)
-        return I.image_patch_planes(img, hw, self.patch, self.mean, self.std, want_pixels)
+        resized to ``hw``: ``ops.image.image_patch_planes``, or the fused launch of a :class:`Frame`'s layout
+        (``patch``: another patch side than the processor's)."""
+        patch = self.patch if patch is None else patch
+        if isinstance(img, Frame):
+            return img.patch_planes(hw, patch, self.mean, self.std, want_pixels)
+        return I.image_patch_planes(img, hw, patch, self.mean, self.std, want_pixels)
 
     @staticmethod
     def results(count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor) \

@@ -42,7 +42,7 @@ import torch.nn.functional as F
 from ...ops import image as I
 from ...ops import kernels as K
 from ...ops.graph_cache import GraphCache
-from .processor import Nv12, YolosProcessor
+from .processor import YolosProcessor
 
 
 @dataclass
@@ -270,8 +270,8 @@ class YolosSmall(nn.Module):
                 and (3 * p * p) % 32 == 0 and I.fusable(tuple(img.shape[1:3]), hw, p))
 
     def encode_image(self, image_u8) -> torch.Tensor:
-        """:meth:`encode` from a uint8 HWC image (tensor, ndarray or PIL) or an NV12 frame
-        (``processor.Nv12``, converted inside the same kernel: ``ops.image.nv12_patch_planes``): resized by
+        """:meth:`encode` from a uint8 HWC image (tensor, ndarray or PIL) or a ``processor.Frame`` (NV12 / NV21,
+        planar 4:2:0, BGR / RGBA / BGRA, pitched views: converted inside the same kernel): resized by
         ``self.processor``'s rule, normalised and split into the patch GEMM's x3 planes by one kernel
         (``ops.image.image_patch_planes``) — no fp32 image is materialised. In ``f32`` mode, off the GPU
         or for a batch it is ``encode(processor.preprocess(image))``."""
@@ -284,11 +284,7 @@ class YolosSmall(nn.Module):
         p = self.c.patch_size
         P = (hw[0] // p) * (hw[1] // p)
         x = self.token_template(hw).clone()
-        if isinstance(img, Nv12):
-            planes, _ = I.nv12_patch_planes(img.y, img.uv, hw, p, self.processor.mean, self.processor.std,
-                                            img.matrix, img.full_range)
-        else:
-            planes, _ = I.image_patch_planes(img, hw, p, self.processor.mean, self.processor.std)
+        planes, _ = self.processor.patch_planes(img, hw, patch=p)
         gemm_x3(planes, self.patch.weight.reshape(self.patch.weight.shape[0], -1), self.patch.bias,
                 residual2=pe[0, 1:1 + P], out=x[0, 1:1 + P])
         return self._run_blocks(x, mid)
@@ -297,7 +293,7 @@ class YolosSmall(nn.Module):
         """Image in, detections out, with no host synchronisation (so it can be captured in a graph):
         ``{"logits", "pred_boxes"}`` of the model and ``{"count", "scores", "labels", "boxes"}`` of
         ``ops.image.detections`` — survivors first, in token order, boxes in pixels of the original
-        image (of an ``Nv12`` frame: of its Y plane; a captured graph reads the frame's buffers by address, so a
+        image as it was passed (of a YUV frame: of its Y plane; of a crop: of the crop; a captured graph reads the frame's buffers by address, so a
         new frame written into them is what the next replay detects on).
         ``self.processor.results(count, scores, labels, boxes)`` gives the per-image lists."""
         img = self.processor.as_batch(image_u8, self.pos_embed.device)

@@ -26,6 +26,15 @@ is rounded to uint8 between the two passes, so pixels differ from it by less tha
   bit-equal to :func:`image_patch_planes` of :func:`nv12_to_rgb`. Chroma is taken nearest — luma
   ``(r, c)`` uses chroma ``(r >> 1, c >> 1)``, what the usual one-call library conversions do;
   bilinear chroma upsampling (and with it chroma siting) is not offered.
+* :func:`yuv420_to_rgb` / :func:`yuv420p_patch_planes` — planar 4:2:0 (I420 / YV12: what a software decoder and
+  most JPEG decoders give), three planes with a pitch each; ``nv12_patch_planes(..., vu=True)`` is NV21. The
+  planar function is the definition of the conversion: :func:`nv12_to_rgb` is it on the de-interleaved planes.
+* :func:`packed_patch_planes` — BGR, RGBA and BGRA, and RGB at any row pitch, batch stride and alignment: a
+  crop ``frame[:, y0:y1, x0:x1]`` or a padded capture buffer is read in place. :func:`image_patch_planes`
+  sends a non-contiguous RGB view there instead of copying it.
+
+Every layout is bit-equal to :func:`image_patch_planes` of the converted or re-ordered contiguous RGB frame,
+which is also what runs on the CPU, with the ``torch`` backend and past a layout's footprint limit.
 """
 from __future__ import annotations
 
@@ -49,6 +58,11 @@ MAX_PATCH = 16
 MAX_FOOTPRINT = 72
 #: columns of a patch's footprint the NV12 staging loop takes (4-column groups in the same LDS row)
 NV12_MAX_FOOTPRINT = 69
+#: the same for planar 4:2:0 and for packed pixels read through pitches (all of them stage 4-column groups)
+YUV420P_MAX_FOOTPRINT = 69
+PACKED_MAX_FOOTPRINT = 69
+#: packed channel orders: bytes per pixel and the index of red, green and blue in a pixel
+PACKED_ORDERS = {"rgb": (3, (0, 1, 2)), "bgr": (3, (2, 1, 0)), "rgba": (4, (0, 1, 2)), "bgra": (4, (2, 1, 0))}
 #: detections kernel limits: rows per image, classes with "no object"
 MAX_ROWS, MAX_CLASSES = 1024, 128
 
@@ -73,10 +87,17 @@ def _L() -> ctypes.CDLL:
             L.nos_image_patch_planes_nv12.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64,
                                                       ctypes.POINTER(ctypes.c_int)] + \
                 L.nos_image_patch_planes_u8.argtypes[1:]
+            L.nos_image_patch_planes_nv12_order.argtypes = L.nos_image_patch_planes_nv12.argtypes + [i32]
+            L.nos_image_patch_planes_yuv420p.argtypes = [vp] * 9 + [i64] * 6 + [ctypes.POINTER(ctypes.c_int)] + \
+                L.nos_image_patch_planes_u8.argtypes[1:]
+            L.nos_image_patch_planes_packed.argtypes = [vp, vp, vp, i64, i64, ctypes.c_char_p] + \
+                L.nos_image_patch_planes_u8.argtypes[1:]
             L.nos_detections_f32.argtypes = [vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, vp, vp]
             L.nos_image_last_error.restype = ctypes.c_char_p
             if (L.nos_image_taps(), L.nos_image_max_footprint(), L.nos_image_max_patch(),
-                    L.nos_image_nv12_max_footprint()) != (TAPS, MAX_FOOTPRINT, MAX_PATCH, NV12_MAX_FOOTPRINT):
+                    L.nos_image_nv12_max_footprint(), L.nos_image_yuv420p_max_footprint(),
+                    L.nos_image_packed_max_footprint()) != (TAPS, MAX_FOOTPRINT, MAX_PATCH, NV12_MAX_FOOTPRINT,
+                                                            YUV420P_MAX_FOOTPRINT, PACKED_MAX_FOOTPRINT):
                 raise NativeUnavailable(f"{LIB} was built with other limits than ops/image.py expects")
             _lib = L
         return _lib
@@ -243,7 +264,8 @@ def image_patch_planes(img_u8: torch.Tensor, out_hw: Tuple[int, int], patch: int
     [B, 3, H, W] fp32 or None)``: resized to ``out_hw``, normalised, and split into the x3 planes of
     the patch matrix (``kernels.patch_planes``' layout). One HIP launch on the GPU; on a CPU tensor,
     with the ``torch`` backend, or past the kernel's limits (:func:`fusable`), the fp32 torch
-    composition and ``split3`` of its im2col."""
+    composition and ``split3`` of its im2col. A view whose pixels are whole but whose rows or images
+    are not adjacent (a crop, a padded buffer) is read in place (:func:`packed_patch_planes`)."""
     if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[-1] != 3:
         raise ValueError("image_patch_planes: a uint8 [B, h, w, 3] image")
     B, h, w, _ = img_u8.shape
@@ -254,6 +276,8 @@ def image_patch_planes(img_u8: torch.Tensor, out_hw: Tuple[int, int], patch: int
     if tabs is None:
         px = pixels_reference(img_u8, (H, W), mean, std)
         return K.split3(im2col(px, patch)), (px if want_pixels else None)
+    if not img_u8.is_contiguous() and _packed_strides(img_u8) and tabs[5] <= PACKED_MAX_FOOTPRINT:
+        return packed_patch_planes(img_u8, "rgb", (H, W), patch, mean, std, want_pixels)
     img = img_u8.contiguous()
     gh, gw = H // patch, W // patch
     planes = torch.empty(3, B * gh * gw, 3 * patch * patch, dtype=torch.bfloat16, device=img.device)
@@ -320,20 +344,52 @@ def nv12_planes(y: torch.Tensor, uv: torch.Tensor) -> Tuple[torch.Tensor, torch.
     return y, uv
 
 
-def nv12_to_rgb(y: torch.Tensor, uv: torch.Tensor, matrix: str = "bt601", full_range: bool = False) -> torch.Tensor:
-    """An NV12 frame as interleaved RGB, uint8 ``[B, h, w, 3]``: the definition of the conversion (and
+def yuv420_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, any_strides: bool = False) \
+        -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The three planes of a planar 4:2:0 frame as ``[B, h, w]`` and two ``[B, (h+1)//2, (w+1)//2]`` views,
+    checked: uint8, one device, matching shapes, each plane's rows possibly pitched but contiguous inside
+    (``any_strides``: not even that, for the torch definition, which reads the halves of an interleaved plane)."""
+    if not all(isinstance(t, torch.Tensor) and t.dtype == torch.uint8 for t in (y, u, v)):
+        raise ValueError("yuv420: the Y, U and V planes are uint8 tensors")
+    if y.dim() == 2 and u.dim() == 2 and v.dim() == 2:
+        y, u, v = y[None], u[None], v[None]
+    if y.dim() != 3 or u.dim() != 3 or v.dim() != 3 or 0 in y.shape:
+        raise ValueError("yuv420: Y is [B, h, w] (or [h, w]) and U, V [B, (h+1)//2, (w+1)//2] (or without B)")
+    B, h, w = y.shape
+    want = (B, (h + 1) // 2, (w + 1) // 2)
+    if tuple(u.shape) != want or tuple(v.shape) != want:
+        raise ValueError(f"yuv420: a {h}x{w} Y plane takes U and V planes of shape {want}, not {tuple(u.shape)} "
+                         f"and {tuple(v.shape)}")
+    if y.device != u.device or y.device != v.device:
+        raise ValueError(f"yuv420: all planes on one device, not {y.device}, {u.device} and {v.device}")
+    if not any_strides and any(t.shape[2] > 1 and t.stride(2) != 1 for t in (y, u, v)):
+        raise ValueError("yuv420: rows may be pitched, but the bytes of a row are contiguous")
+    return y, u, v
+
+
+def yuv420_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, matrix: str = "bt601",
+                  full_range: bool = False) -> torch.Tensor:
+    """A planar 4:2:0 frame as interleaved RGB, uint8 ``[B, h, w, 3]``: the definition of the conversion (and
     what runs on the CPU, with the ``torch`` backend and past the kernel's limits). Nearest chroma,
     exact int32 arithmetic on :func:`nv12_table`."""
-    y, uv = nv12_planes(y, uv)
+    y, u, v = yuv420_planes(y, u, v, any_strides=True)
     t = nv12_table(matrix, full_range)
     h, w = y.shape[1:]
     rows, cols = torch.arange(h, device=y.device) >> 1, torch.arange(w, device=y.device) >> 1
     # the largest term is below 2^25 (138 438 x 128, 76 309 x 255) and the sum below 2^27: int32 cannot overflow
     yy = y.to(torch.int32) - t[9]
-    c = uv.to(torch.int32)[:, rows][:, :, cols]
-    u, v = c[..., 0] - t[10], c[..., 1] - t[11]
-    out = [(t[3 * k] * yy + t[3 * k + 1] * u + t[3 * k + 2] * v + 32768) >> 16 for k in range(3)]
+    uu = u.to(torch.int32)[:, rows][:, :, cols] - t[10]
+    vv = v.to(torch.int32)[:, rows][:, :, cols] - t[11]
+    out = [(t[3 * k] * yy + t[3 * k + 1] * uu + t[3 * k + 2] * vv + 32768) >> 16 for k in range(3)]
     return torch.stack(out, dim=-1).clamp_(0, 255).to(torch.uint8)
+
+
+def nv12_to_rgb(y: torch.Tensor, uv: torch.Tensor, matrix: str = "bt601", full_range: bool = False,
+                vu: bool = False) -> torch.Tensor:
+    """An NV12 frame as interleaved RGB, uint8 ``[B, h, w, 3]``: :func:`yuv420_to_rgb` of its de-interleaved
+    planes (``vu``: the pairs are (V, U), NV21)."""
+    y, uv = nv12_planes(y, uv)
+    return yuv420_to_rgb(y, uv[..., 1 if vu else 0], uv[..., 0 if vu else 1], matrix, full_range)
 
 
 def _storage_bounds(t: torch.Tensor) -> Tuple[int, int]:
@@ -343,11 +399,12 @@ def _storage_bounds(t: torch.Tensor) -> Tuple[int, int]:
 
 def nv12_patch_planes(y: torch.Tensor, uv: torch.Tensor, out_hw: Tuple[int, int], patch: int, mean: Sequence[float],
                       std: Sequence[float], matrix: str = "bt601", full_range: bool = False,
-                      want_pixels: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                      want_pixels: bool = False, vu: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """:func:`image_patch_planes` of an NV12 frame (:func:`nv12_planes`' layout), bit-equal to
     ``image_patch_planes(nv12_to_rgb(y, uv, matrix, full_range), ...)`` — which is what runs on a CPU
     tensor, with the ``torch`` backend and past the kernel's limits. On the GPU one HIP launch reads
-    the two planes in place, by their strides: a pitched surface is not copied."""
+    the two planes in place, by their strides: a pitched surface is not copied. ``vu``: the chroma pairs
+    are (V, U), which is NV21."""
     y, uv = nv12_planes(y, uv)
     table = nv12_table(matrix, full_range)
     B, h, w = y.shape
@@ -356,21 +413,119 @@ def nv12_patch_planes(y: torch.Tensor, uv: torch.Tensor, out_hw: Tuple[int, int]
     if _use_hip(y) and fusable((h, w), (H, W), patch):
         tabs = _device_tables(h, w, H, W, patch, y.device)
     if tabs is None or tabs[5] > NV12_MAX_FOOTPRINT:
-        return image_patch_planes(nv12_to_rgb(y, uv, matrix, full_range), (H, W), patch, mean, std, want_pixels)
+        rgb = nv12_to_rgb(y, uv, matrix, full_range, vu=True) if vu else nv12_to_rgb(y, uv, matrix, full_range)
+        return image_patch_planes(rgb, (H, W), patch, mean, std, want_pixels)
     gh, gw = H // patch, W // patch
     planes = torch.empty(3, B * gh * gw, 3 * patch * patch, dtype=torch.bfloat16, device=y.device)
     pixels = torch.empty(B, 3, H, W, dtype=torch.float32, device=y.device) if want_pixels else None
     yidx, ywt, xidx, xwt, max_fh, max_fw = tabs
     a, b = affine(mean, std)
     F3 = ctypes.c_float * 3
-    rc = _L().nos_image_patch_planes_nv12(y.data_ptr(), *_storage_bounds(y), uv.data_ptr(), *_storage_bounds(uv),
+    args = (y.data_ptr(), *_storage_bounds(y), uv.data_ptr(), *_storage_bounds(uv),
                                           y.stride(1), uv.stride(1), y.stride(0), uv.stride(0),
                                           (ctypes.c_int * 12)(*table), planes.data_ptr(),
                                           pixels.data_ptr() if want_pixels else None, yidx.data_ptr(), ywt.data_ptr(),
                                           xidx.data_ptr(), xwt.data_ptr(), ywt.shape[0], xwt.shape[0], ywt.shape[1],
                                           max_fh, max_fw, F3(*a), F3(*b), B, h, w, H, W, patch, gh, gw, image_wgs(),
                                           torch.cuda.current_stream().cuda_stream)
+    rc = _L().nos_image_patch_planes_nv12_order(*args, 1) if vu else _L().nos_image_patch_planes_nv12(*args)
     _check(rc, "nv12_patch_planes")
+    return planes, pixels
+
+
+def _outputs(B: int, H: int, W: int, patch: int, want_pixels: bool, device: torch.device):
+    gh, gw = H // patch, W // patch
+    planes = torch.empty(3, B * gh * gw, 3 * patch * patch, dtype=torch.bfloat16, device=device)
+    pixels = torch.empty(B, 3, H, W, dtype=torch.float32, device=device) if want_pixels else None
+    return planes, pixels, gh, gw
+
+
+def _tail_args(tabs: tuple, planes: torch.Tensor, pixels: Optional[torch.Tensor], mean, std, B, h, w, H, W, patch,
+               gh, gw) -> tuple:
+    """The arguments every image entry shares, from the output planes on."""
+    yidx, ywt, xidx, xwt, max_fh, max_fw = tabs
+    a, b = affine(mean, std)
+    F3 = ctypes.c_float * 3
+    return (planes.data_ptr(), pixels.data_ptr() if pixels is not None else None, yidx.data_ptr(), ywt.data_ptr(),
+            xidx.data_ptr(), xwt.data_ptr(), ywt.shape[0], xwt.shape[0], ywt.shape[1], max_fh, max_fw, F3(*a), F3(*b),
+            B, h, w, H, W, patch, gh, gw, image_wgs(), torch.cuda.current_stream().cuda_stream)
+
+
+# ---- planar 4:2:0 -------------------------------------------------------------------------------
+def yuv420p_patch_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, out_hw: Tuple[int, int], patch: int,
+                         mean: Sequence[float], std: Sequence[float], matrix: str = "bt601", full_range: bool = False,
+                         want_pixels: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """:func:`image_patch_planes` of a planar 4:2:0 frame (:func:`yuv420_planes`' layout; I420, or YV12 with
+    the planes passed by what they hold), bit-equal to ``image_patch_planes(yuv420_to_rgb(y, u, v, matrix,
+    full_range), ...)`` — which is what runs on a CPU tensor, with the ``torch`` backend and past the kernel's
+    limits. On the GPU one HIP launch reads the three planes in place, each by its own strides."""
+    y, u, v = yuv420_planes(y, u, v)
+    table = nv12_table(matrix, full_range)
+    B, h, w = y.shape
+    H, W = int(out_hw[0]), int(out_hw[1])
+    tabs = None
+    if _use_hip(y) and fusable((h, w), (H, W), patch):
+        tabs = _device_tables(h, w, H, W, patch, y.device)
+    if tabs is None or tabs[5] > YUV420P_MAX_FOOTPRINT:
+        return image_patch_planes(yuv420_to_rgb(y, u, v, matrix, full_range), (H, W), patch, mean, std, want_pixels)
+    planes, pixels, gh, gw = _outputs(B, H, W, patch, want_pixels, y.device)
+    rc = _L().nos_image_patch_planes_yuv420p(y.data_ptr(), *_storage_bounds(y), u.data_ptr(), *_storage_bounds(u),
+                                             v.data_ptr(), *_storage_bounds(v), y.stride(1), u.stride(1), v.stride(1),
+                                             y.stride(0), u.stride(0), v.stride(0), (ctypes.c_int * 12)(*table),
+                                             *_tail_args(tabs, planes, pixels, mean, std, B, h, w, H, W, patch, gh, gw))
+    _check(rc, "yuv420p_patch_planes")
+    return planes, pixels
+
+
+# ---- packed pixels ------------------------------------------------------------------------------
+def _packed_strides(img: torch.Tensor) -> bool:
+    """Whole pixels side by side in a row (rows and images wherever their strides put them)."""
+    C = img.shape[3]
+    return img.stride(3) == 1 and (img.shape[2] == 1 or img.stride(2) == C) \
+        and (img.shape[1] == 1 or img.stride(1) >= img.shape[2] * C)
+
+
+def packed_to_rgb(img: torch.Tensor, order: str = "rgb") -> torch.Tensor:
+    """Packed pixels ``[B, h, w, 3 | 4]`` in ``order`` as contiguous interleaved RGB ``[B, h, w, 3]``: the colour
+    bytes re-indexed, a fourth byte dropped (no premultiplication)."""
+    if order not in PACKED_ORDERS:
+        raise ValueError(f"packed: channel order {order!r} is none of {sorted(PACKED_ORDERS)}")
+    C, idx = PACKED_ORDERS[order]
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != C:
+        raise ValueError(f"packed: {order} takes a uint8 [B, h, w, {C}] image")
+    # (slices stacked, not an index list: no index tensor is copied from the host, so it can be captured)
+    return torch.stack([img[..., i] for i in idx], dim=-1)
+
+
+def packed_patch_planes(img: torch.Tensor, order: str, out_hw: Tuple[int, int], patch: int, mean: Sequence[float],
+                        std: Sequence[float], want_pixels: bool = False) \
+        -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """:func:`image_patch_planes` of packed pixels ``[B, h, w, C]`` uint8 in ``order`` (``rgb``, ``bgr``: C = 3;
+    ``rgba``, ``bgra``: C = 4, the fourth byte ignored), bit-equal to ``image_patch_planes(packed_to_rgb(img,
+    order), ...)`` — which is what runs on a CPU tensor, with the ``torch`` backend and past the kernel's limits.
+    ``stride(3) == 1`` and ``stride(2) == C``; rows and images lie wherever ``stride(1)`` and ``stride(0)`` put
+    them (a crop, a padded capture buffer, a flipped batch), and on the GPU one HIP launch reads them there."""
+    if order not in PACKED_ORDERS:
+        raise ValueError(f"packed: channel order {order!r} is none of {sorted(PACKED_ORDERS)}")
+    C = PACKED_ORDERS[order][0]
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != C \
+            or 0 in img.shape:
+        raise ValueError(f"packed: {order} takes a uint8 [B, h, w, {C}] image")
+    if not _packed_strides(img):
+        raise ValueError("packed: rows may be pitched, but the bytes of a row are contiguous "
+                         f"(stride(3) == 1, stride(2) == {C}, stride(1) >= {C} * w)")
+    B, h, w, _ = img.shape
+    H, W = int(out_hw[0]), int(out_hw[1])
+    tabs = None
+    if _use_hip(img) and fusable((h, w), (H, W), patch):
+        tabs = _device_tables(h, w, H, W, patch, img.device)
+    if tabs is None or tabs[5] > PACKED_MAX_FOOTPRINT:
+        return image_patch_planes(packed_to_rgb(img, order), (H, W), patch, mean, std, want_pixels)
+    planes, pixels, gh, gw = _outputs(B, H, W, patch, want_pixels, img.device)
+    rc = _L().nos_image_patch_planes_packed(img.data_ptr(), *_storage_bounds(img), img.stride(1), img.stride(0),
+                                            order.encode(),
+                                            *_tail_args(tabs, planes, pixels, mean, std, B, h, w, H, W, patch, gh, gw))
+    _check(rc, "packed_patch_planes")
     return planes, pixels
 
 
