@@ -56,7 +56,8 @@ template <bool FDIV = false>
 __global__ __launch_bounds__(256, 1) void attn_fwd_x3w(const float* __restrict__ qkv, float* __restrict__ out,
                                                        __bf16* __restrict__ outp, float* __restrict__ part_o,
                                                        float* __restrict__ part_ml, int B, int T, int H, int h0,
-                                                       int Ht, float scale_log2e, int Pk, int* __restrict__ cnt) {
+                                                       int Ht, float scale_log2e, int Pk, int* __restrict__ cnt,
+                                                       int q0, int Tq) {
   constexpr int G = 8;  // query tiles per workgroup: 4 waves x 2
   __shared__ __attribute__((aligned(16))) __bf16 lds_k[2 * 3 * XK_PLANE];
   __shared__ __attribute__((aligned(16))) __bf16 lds_v[2 * 3 * XV_PLANE];
@@ -65,7 +66,9 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_x3w(const float* __restrict__
   const PinnedBlock pb = pinned_block(unsigned(Pk >> 22) & 0xffu);
   if (pb.id < 0 || pb.id >= P) return;
   const int w = (Pk >> 30) ? pb.id : xcd_major_n(pb.id, P, pb.nx);
-  const int NK = (T + 31) / 32, QT = NK, QG = (QT + G - 1) / G;
+  // query window: the queries are rows q0 .. q0+Tq-1 (query tile qt holds rows q0 + 32*qt + j), the
+  // keys all T rows; the output is compact, [B][Tq][D]
+  const int NK = (T + 31) / 32, QT = (Tq + 31) / 32, QG = (QT + G - 1) / G;
   const long long U = (long long)B * H * QG * NK;
   const float rP = FDIV ? 1.f / float(P) : 0.f, rNK = FDIV ? 1.f / float(NK) : 0.f;
   const float rQG = FDIV ? 1.f / float(QG) : 0.f, rH = FDIV ? 1.f / float(H) : 0.f;
@@ -95,8 +98,8 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_x3w(const float* __restrict__
 
     bf16x8 qa[3][4], qb[3][4];
     {
-      const float* qpa = basef + size_t(min(qtA * 32 + j, T - 1)) * ld + head * HD + 8 * hf;
-      const float* qpb = basef + size_t(min(qtB * 32 + j, T - 1)) * ld + head * HD + 8 * hf;
+      const float* qpa = basef + size_t(q0 + min(qtA * 32 + j, Tq - 1)) * ld + head * HD + 8 * hf;
+      const float* qpb = basef + size_t(q0 + min(qtB * 32 + j, Tq - 1)) * ld + head * HD + 8 * hf;
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         const f32x4 alo = *reinterpret_cast<const f32x4*>(qpa + 16 * s);
@@ -382,11 +385,11 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_x3w(const float* __restrict__
     const bool whole = kb0 == 0 && kb1 == NK;
     auto store_tile = [&](int t, const f32x16& o0, const f32x16& o1, float l) {
       const int q = (qg * G + 2 * wv + t) * 32 + j;
-      if (q >= T) return;
+      if (q >= Tq) return;
       const float inv = 1.f / l;
-      const size_t orow = (size_t(b) * T + q) * D + head * HD;
+      const size_t orow = (size_t(b) * Tq + q) * D + head * HD;
       if (outp) {
-        const size_t op = size_t(B) * T * D;
+        const size_t op = size_t(B) * Tq * D;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int d = key_of(r, hf);
@@ -485,13 +488,13 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_x3w(const float* __restrict__
 
 int nos_attn_x3w_launch(bool fdiv, dim3 grid, hipStream_t s, const float* qkv, float* out, __bf16* outp,
                         float* part_o, float* part_ml, int B, int T, int H, int h0, int Ht, float scale_log2e,
-                        int Pk, int* cnt) {
+                        int Pk, int* cnt, int q0, int Tq) {
   if (fdiv)
     hipLaunchKernelGGL(attn_fwd_x3w<true>, grid, dim3(256), 0, s, qkv, out, outp, part_o, part_ml, B, T, H, h0, Ht,
-                       scale_log2e, Pk, cnt);
+                       scale_log2e, Pk, cnt, q0, Tq);
   else
     hipLaunchKernelGGL(attn_fwd_x3w<false>, grid, dim3(256), 0, s, qkv, out, outp, part_o, part_ml, B, T, H, h0, Ht,
-                       scale_log2e, Pk, cnt);
+                       scale_log2e, Pk, cnt, q0, Tq);
   return int(hipPeekAtLastError());  // left set for the caller's check_launch
 }
 

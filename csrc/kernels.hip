@@ -661,9 +661,11 @@ template <int G>
 __global__ __launch_bounds__(256) void attn_sk_lds_fixup(const float* __restrict__ part_o,
                                                          const float* __restrict__ part_ml, float* __restrict__ out,
                                                          int B, int T, int H, int P, __bf16* __restrict__ outp,
-                                                         int h0, int Ht, unsigned pin) {
+                                                         int h0, int Ht, unsigned pin, int Tq) {
   __shared__ float s_tile[64][33];
-  const int NK = (T + 31) / 32, QT = NK, QG = (QT + G - 1) / G;
+  // Tq: query rows of the launch that left the partials (T, or its query window's): the output is
+  // [B][Tq][D]
+  const int NK = (T + 31) / 32, QT = (Tq + 31) / 32, QG = (QT + G - 1) / G;
   const long long U = (long long)B * H * QG * NK;
   const bool narrow_stores = (pin >> 8) & 1u;  // A/B: the earlier 2-byte plane stores
   const bool xcd_local = (pin >> 9) & 1u;
@@ -758,14 +760,14 @@ __global__ __launch_bounds__(256) void attn_sk_lds_fixup(const float* __restrict
 #pragma unroll
   for (int i = 0; i < 8; ++i) s_tile[(tid + 256 * i) >> 5][q] = acc[i] * inv;
   __syncthreads();
-  const size_t plane = size_t(B) * T * D;
+  const size_t plane = size_t(B) * Tq * D;
   if (!narrow_stores) {
     // transposed store: thread -> (query row, 8 consecutive dims), one pass: each plane row of the
     // tile leaves as 16-B stores (the fp32 output as two)
     const int jq = tid >> 3, c8 = 8 * (tid & 7);
     const int qq = qt * 32 + jq;
-    if (qq < T) {
-      const size_t i = (size_t(b) * T + qq) * D + head * HD + c8;
+    if (qq < Tq) {
+      const size_t i = (size_t(b) * Tq + qq) * D + head * HD + c8;
       f32x8 v;
 #pragma unroll
       for (int dd = 0; dd < 8; ++dd) v[dd] = s_tile[c8 + dd][jq];
@@ -785,8 +787,8 @@ __global__ __launch_bounds__(256) void attn_sk_lds_fixup(const float* __restrict
   const int d = tid & 63;
   for (int jq = tid >> 6; jq < 32; jq += 4) {
     const int qq = qt * 32 + jq;
-    if (qq >= T) break;
-    const size_t i = (size_t(b) * T + qq) * D + head * HD + d;
+    if (qq >= Tq) break;
+    const size_t i = (size_t(b) * Tq + qq) * D + head * HD + d;
     if (outp)
       store_x3(outp, plane, i, s_tile[d][jq]);
     else
@@ -1058,7 +1060,7 @@ __global__ __launch_bounds__(64 * G, 8 / G) void attn_fwd_x3p(const __bf16* __re
                                                              float* __restrict__ out, __bf16* __restrict__ outp,
                                                              float* __restrict__ part_o, float* __restrict__ part_ml,
                                                              int B, int T, int H, int h0, int Ht, float scale_log2e,
-                                                             int Pk) {
+                                                             int Pk, int qw0, int Tq) {
   static_assert(G == 4 || G == 8, "4 or 8 query tiles per workgroup");
   __shared__ __attribute__((aligned(16))) __bf16 lds_k[2 * 3 * XK_PLANE];
   __shared__ __attribute__((aligned(16))) __bf16 lds_v[2 * 3 * XV_PLANE];
@@ -1068,7 +1070,9 @@ __global__ __launch_bounds__(64 * G, 8 / G) void attn_fwd_x3p(const __bf16* __re
   const PinnedBlock pb = pinned_block(unsigned(Pk >> 22) & 0xffu);
   if (pb.id < 0 || pb.id >= P) return;
   const int w = (Pk >> 30) ? pb.id : xcd_major_n(pb.id, P, pb.nx);
-  const int NK = (T + 31) / 32, QT = NK, QG = (QT + G - 1) / G;
+  // query window: the queries are rows qw0 .. qw0+Tq-1 (query tile qt holds rows qw0 + 32*qt + j),
+  // the keys all T rows; the output is compact, [B][Tq][D]
+  const int NK = (T + 31) / 32, QT = (Tq + 31) / 32, QG = (QT + G - 1) / G;
   const long long U = (long long)B * H * QG * NK;
   // FDIV (host-checked: every numerator < 2^23): reciprocal divisions for the bookkeeping
   const float rP = FDIV ? 1.f / float(P) : 0.f, rNK = FDIV ? 1.f / float(NK) : 0.f;
@@ -1105,7 +1109,7 @@ __global__ __launch_bounds__(64 * G, 8 / G) void attn_fwd_x3p(const __bf16* __re
 
     bf16x8 qf[3][4];
     {
-      const int qrow = min(q0 + j, T - 1);
+      const int qrow = qw0 + min(q0 + j, Tq - 1);
       if constexpr (F32IN) {
         const float* qp = basef + size_t(qrow) * ld + head * HD + 8 * hf;
 #pragma unroll
@@ -1361,11 +1365,11 @@ __global__ __launch_bounds__(64 * G, 8 / G) void attn_fwd_x3p(const __bf16* __re
     if (active) {
       if (kb0 == 0 && kb1 == NK) {
         const int q = q0 + j;
-        if (q < T) {
+        if (q < Tq) {
           const float inv = 1.f / l;
-          const size_t orow = (size_t(b) * T + q) * D + head * HD;
+          const size_t orow = (size_t(b) * Tq + q) * D + head * HD;
           if (outp) {
-            const size_t op = size_t(B) * T * D;
+            const size_t op = size_t(B) * Tq * D;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               const int d = key_of(r, hf);
@@ -1517,9 +1521,22 @@ int nos_attention_x3_wg_per_cu() {
 // workgroups share one block's K/V in L2 (with every head in flight at once, the K/V planes of all
 // heads are the L2 working set — the traffic concurrent partitions contend for). Workspace:
 // nos_attention_ws_bytes of the LDS variant (variant 0 layout), merged by the same fixup kernel.
+// Query window: the queries are rows q0 .. q0+Tq-1 of the T rows (q0 arbitrary), the keys and values
+// all T rows, and the output is compact: fp32 [B, Tq, H*64] or planes [3][B*Tq*H*64]. The units are
+// B*hn*ceil(ceil(Tq/32)/G)*ceil(T/32); a windowed launch (anything but q0 = 0, Tq = T) runs the
+// pipelined kernels and always merges through the separate fixup launch.
 static int attention_x3_launch(const void* qkv3, size_t plane_stride, float* out, void* outp, float* ws, int B,
                                int T, int H, int h0, int hn, int head_dim, float scale, int waves, void* stream,
-                               bool f32in, bool fixup = true, int* cnt = nullptr) {
+                               bool f32in, bool fixup, int* cnt, int q0, int Tq) {
+  if (q0 < 0 || Tq <= 0 || (long long)q0 + Tq > T) {
+    g_err = "attention x3: query window out of range (needs q0 >= 0, Tq > 0, q0 + Tq <= T)";
+    return -1;
+  }
+  const bool windowed = q0 != 0 || Tq != T;
+  if (windowed && (!g_x3_pipelined || cnt != nullptr || !fixup)) {
+    g_err = "attention x3: a query window needs the pipelined kernel and the separate fixup launch";
+    return -1;
+  }
   if ((out == nullptr) == (outp == nullptr)) {
     g_err = "attention x3: exactly one of out / outp";
     return -1;
@@ -1550,7 +1567,7 @@ static int attention_x3_launch(const void* qkv3, size_t plane_stride, float* out
   }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int G = nos_attention_x3_group();
-  const int NK = (T + 31) / 32, QG = (NK + G - 1) / G;
+  const int NK = (T + 31) / 32, QT = (Tq + 31) / 32, QG = (QT + G - 1) / G;
   float* part_o = ws;
   float* part_ml = ws + size_t(waves) * 2 * G * HD * 32;
   __bf16* op = reinterpret_cast<__bf16*>(outp);
@@ -1576,25 +1593,25 @@ static int attention_x3_launch(const void* qkv3, size_t plane_stride, float* out
                        sl2, waves);
   else if (G == 8 && f32in && g_x3_wide)
     nos_attn_x3w_launch(fdiv, grid, s, reinterpret_cast<const float*>(qkv3), out, op, part_o, part_ml, B, T, hn, h0,
-                        H, sl2, pk, fixup ? cnt : nullptr);
+                        H, sl2, pk, fixup ? cnt : nullptr, q0, Tq);
   else if (G == 8 && f32in && (g_x3_flags & 2))
     hipLaunchKernelGGL((attn_fwd_x3p<8, false, true, true>), grid, dim3(512), 0, s, q3, plane_stride, out, op,
-                       part_o, part_ml, B, T, hn, h0, H, sl2, pk);
+                       part_o, part_ml, B, T, hn, h0, H, sl2, pk, q0, Tq);
   else if (G == 8 && f32in && fdiv)
     hipLaunchKernelGGL((attn_fwd_x3p<8, false, true, false, true>), grid, dim3(512), 0, s, q3, plane_stride, out,
-                       op, part_o, part_ml, B, T, hn, h0, H, sl2, pk);
+                       op, part_o, part_ml, B, T, hn, h0, H, sl2, pk, q0, Tq);
   else if (G == 8 && f32in)
     hipLaunchKernelGGL((attn_fwd_x3p<8, false, true>), grid, dim3(512), 0, s, q3, plane_stride, out, op, part_o,
-                       part_ml, B, T, hn, h0, H, sl2, pk);
+                       part_ml, B, T, hn, h0, H, sl2, pk, q0, Tq);
   else if (G == 8 && (g_x3_flags & 1))
     hipLaunchKernelGGL((attn_fwd_x3p<8, true>), grid, dim3(512), 0, s, q3, plane_stride, out, op, part_o,
-                       part_ml, B, T, hn, h0, H, sl2, pk);
+                       part_ml, B, T, hn, h0, H, sl2, pk, q0, Tq);
   else if (G == 8)
     hipLaunchKernelGGL(attn_fwd_x3p<8>, grid, dim3(512), 0, s, q3, plane_stride, out, op, part_o, part_ml, B,
-                       T, hn, h0, H, sl2, pk);
+                       T, hn, h0, H, sl2, pk, q0, Tq);
   else
     hipLaunchKernelGGL(attn_fwd_x3p<4>, grid, dim3(256), 0, s, q3, plane_stride, out, op, part_o, part_ml, B,
-                       T, hn, h0, H, sl2, pk);
+                       T, hn, h0, H, sl2, pk, q0, Tq);
   if (int rc = check_launch("attn_fwd_x3")) return rc;
   if (!fixup) return 0;  // the partials are merged by the consumer (attn_proj.hip)
   if (cnt && G == 8 && f32in && g_x3_wide && g_x3_pipelined) return 0;  // merged in the kernel
@@ -1603,23 +1620,42 @@ static int attention_x3_launch(const void* qkv3, size_t plane_stride, float* out
   if (G == 8)
     hipLaunchKernelGGL(attn_sk_lds_fixup<8>, dim3(pinned_grid(8 * ((B * hn * QG * 8 + 7) / 8), pin)), dim3(256), 0, s,
                        part_o, part_ml,
-                       out, B, T, hn, waves, op, h0, H, fpin);
+                       out, B, T, hn, waves, op, h0, H, fpin, Tq);
   else
     hipLaunchKernelGGL(attn_sk_lds_fixup<4>, dim3(pinned_grid(B * hn * QG * 4, pin)), dim3(256), 0, s,
                        part_o, part_ml,
-                       out, B, T, hn, waves, op, h0, H, fpin);
+                       out, B, T, hn, waves, op, h0, H, fpin, Tq);
   return check_launch("attn_sk_lds_fixup");
 }
 
 int nos_attention_x3_sk_heads(const void* qkv3, size_t plane_stride, float* out, void* outp, float* ws, int B,
                               int T, int H, int h0, int hn, int head_dim, float scale, int waves, void* stream) {
-  return attention_x3_launch(qkv3, plane_stride, out, outp, ws, B, T, H, h0, hn, head_dim, scale, waves, stream, false);
+  return attention_x3_launch(qkv3, plane_stride, out, outp, ws, B, T, H, h0, hn, head_dim, scale, waves, stream, false,
+                             true, nullptr, 0, T);
+}
+
+// the same for the query rows q0 .. q0+Tq-1 only (keys and values: all T rows); out fp32
+// [B, Tq, H*64] or outp its planes [3][B*Tq*H*64]
+int nos_attention_x3_sk_heads_window(const void* qkv3, size_t plane_stride, float* out, void* outp, float* ws, int B,
+                                     int T, int H, int h0, int hn, int head_dim, float scale, int waves, int q0,
+                                     int Tq, void* stream) {
+  return attention_x3_launch(qkv3, plane_stride, out, outp, ws, B, T, H, h0, hn, head_dim, scale, waves, stream, false,
+                             true, nullptr, q0, Tq);
 }
 
 // the same from an fp32 packed QKV tensor [B, T, 3*H*64] (split to planes inside the kernel)
 int nos_attention_x3f_sk_heads(const float* qkv, float* out, void* outp, float* ws, int B, int T, int H, int h0,
                                int hn, int head_dim, float scale, int waves, void* stream) {
-  return attention_x3_launch(qkv, 8, out, outp, ws, B, T, H, h0, hn, head_dim, scale, waves, stream, true);
+  return attention_x3_launch(qkv, 8, out, outp, ws, B, T, H, h0, hn, head_dim, scale, waves, stream, true, true,
+                             nullptr, 0, T);
+}
+
+// fp32 QKV in, the query rows q0 .. q0+Tq-1 only (see nos_attention_x3_sk_heads_window)
+int nos_attention_x3f_sk_heads_window(const float* qkv, float* out, void* outp, float* ws, int B, int T, int H,
+                                      int h0, int hn, int head_dim, float scale, int waves, int q0, int Tq,
+                                      void* stream) {
+  return attention_x3_launch(qkv, 8, out, outp, ws, B, T, H, h0, hn, head_dim, scale, waves, stream, true, true,
+                             nullptr, q0, Tq);
 }
 
 // the same with the stream-K merge inside the wide kernel (attn_fwd_x3w) when it runs: cnt holds
@@ -1633,7 +1669,8 @@ int nos_attention_x3f_sk_heads_merged(const float* qkv, float* out, void* outp, 
     g_err = "attention x3 merged: needs B*hn*QG row counters";
     return -1;
   }
-  return attention_x3_launch(qkv, 8, out, outp, ws, B, T, H, h0, hn, head_dim, scale, waves, stream, true, true, cnt);
+  return attention_x3_launch(qkv, 8, out, outp, ws, B, T, H, h0, hn, head_dim, scale, waves, stream, true, true, cnt, 0,
+                             T);
 }
 
 // The x3 attention from fp32 QKV over all heads WITHOUT the stream-K fixup: split query tiles
@@ -1645,7 +1682,8 @@ int nos_attention_x3f_partials(const float* qkv, float* out, float* ws, int B, i
     g_err = "attention x3 partials: needs the fp32 direct-output buffer";
     return -1;
   }
-  return attention_x3_launch(qkv, 8, out, nullptr, ws, B, T, H, 0, H, head_dim, scale, waves, stream, true, false);
+  return attention_x3_launch(qkv, 8, out, nullptr, ws, B, T, H, 0, H, head_dim, scale, waves, stream, true, false,
+                             nullptr, 0, T);
 }
 
 int nos_attention_x3_sk(const void* qkv3, size_t plane_stride, float* out, void* outp, float* ws, int B, int T,
@@ -1817,7 +1855,7 @@ int nos_attention_f32_sk(const float* qkv, float* out, float* ws, int B, int T, 
                        scale_log2e, waves);
     if (int rc = check_launch("attn_fwd_sk_lds")) return rc;
     hipLaunchKernelGGL(attn_sk_lds_fixup<4>, dim3(B * H * QG * 4), dim3(256), 0, s, part_o, part_ml, out, B, T, H, waves,
-                       static_cast<__bf16*>(nullptr), 0, H, 0u);
+                       static_cast<__bf16*>(nullptr), 0, H, 0u, T);
     return check_launch("attn_sk_lds_fixup");
   }
   float* part_o = ws;

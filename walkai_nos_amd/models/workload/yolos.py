@@ -19,6 +19,19 @@ DETR-style MLP heads) built for the MI355X inference path:
 * ``encode_image`` / ``detect_image`` take a uint8 photo instead of ready pixels: the processor's
   resize and normalisation fused with the patch GEMM's x3 split, and the post-process, one HIP
   launch each (:mod:`walkai_nos_amd.ops.image`, :mod:`.processor`);
+* the last block runs on the detection rows only ("detection tail"). ``detect`` reads nothing but
+  the last ``nd`` = 100 rows, and a row of a block's output depends on the other rows only through K
+  and V: so in the last block the attention queries, the projection, LN2, fc1, GELU and fc2 of the
+  class/patch rows (3301 of 3401 at the demo's size) feed nothing and are skipped —
+  ``forward`` / ``detect_image`` go through ``encode_detection``: the QKV GEMM on every row, the x3
+  attention with a query window (``q0 = T - nd``, ``Tq = nd``), then the three GEMMs at M = nd. The
+  Q third of that QKV GEMM is still computed for the pruned rows (about 9 us on the whole GPU; left
+  for later). The rule is one of shapes only: the tail is taken when it at least halves the block's
+  32-row query tiles, ``2*ceil(nd/32) <= ceil(T/32)`` (taken at T = 3401 and 257, not at T <= 224);
+  ``NOS_DET_TAIL=0/1`` or ``set_detection_tail`` override it. Where it is taken, ``forward`` equals
+  ``detect(encode(x))`` to fp32 rounding, not bit for bit (the lazy softmax rescale is decided per
+  32-row tile, and the stream-K split points and tuned tiles follow the shape); ``encode`` /
+  ``encode_image`` keep returning every row. Measured: ``docs/benchmark.md``, "Round 7";
 * ``load_hf_state_dict`` maps a ``transformers`` ``YolosForObjectDetection`` state dict onto this
   module, which is how numerical parity is tested
   (``tests/test_infra.py::test_yolos_matches_transformers_reference``) — there is no network, so
@@ -32,6 +45,7 @@ image is resized by the YOLOS processor to 800x1066 (shortest edge 800) -> 50x66
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
@@ -72,6 +86,33 @@ CACHED_SIZES = 4
 
 #: the demo's input after YolosImageProcessor (640x480 COCO image -> shortest edge 800)
 DEMO_INPUT_HW = (800, 1066)
+
+
+_det_tail: Optional[bool] = None
+
+
+def set_detection_tail(on: Optional[bool]) -> None:
+    """Force the last block onto the detection rows only (True) or onto every row (False); None:
+    ``NOS_DET_TAIL`` (``0`` / ``1``), else the shape rule of :func:`detection_tail_rule`. For A/B runs
+    and for tests at small T; read at every forward."""
+    global _det_tail
+    _det_tail = on
+
+
+def detection_tail_rule(T: int, nd: int) -> bool:
+    """The last block runs on the ``nd`` detection rows when that at least halves its 32-row query
+    tiles. Below that there is one query group and one or two GEMM row tiles either way."""
+    return 2 * ((nd + 31) // 32) <= (T + 31) // 32
+
+
+def detection_tail(T: int, nd: int) -> bool:
+    """:func:`detection_tail_rule` unless overridden (:func:`set_detection_tail`, ``NOS_DET_TAIL``)."""
+    if _det_tail is not None:
+        return _det_tail
+    env = os.environ.get("NOS_DET_TAIL", "").strip()
+    if env in ("0", "1"):
+        return env == "1"
+    return detection_tail_rule(T, nd)
 
 
 class _Block(nn.Module):
@@ -115,6 +156,46 @@ class _Block(nn.Module):
         f3 = K.linear_x3(h3, self.fc1.weight, self.fc1.bias, gelu=True, out_x3=True)
         nl = (next_ln.weight, next_ln.bias, next_ln.eps) if next_ln is not None else None
         return K.linear_residual_ln_x3(f3, self.fc2.weight, self.fc2.bias, x, residual2=mid, ln=nl)
+
+    def tail_supported(self, x: torch.Tensor) -> bool:
+        """The attention that would run on ``x`` takes a query window: the reference math (CPU,
+        ``torch`` backend) and the pipelined x3 kernels do; the fused attention + projection kernel
+        (``NOS_ATTN_PROJ_FUSED=1``), the block-at-a-time x3 kernel and the f32-MFMA attention do not."""
+        if K.x3_active(x):
+            return K.attention_x3_windowed() and not (K.attention_input_f32()
+                                                      and K.attn_proj_fusable(self.c.num_heads, self.c.head_dim))
+        return not (x.is_cuda and K.get_backend() == "hip")
+
+    def forward_tail(self, x: torch.Tensor, h3: Optional[torch.Tensor], nd: int) -> torch.Tensor:
+        """The block for a caller that reads only the last ``nd`` rows: ``[B, nd, D]``, the same rows
+        :meth:`forward` / :meth:`forward_x3` give to fp32 rounding. K and V need every row, so the QKV
+        GEMM runs on all of ``x``; the attention takes the last ``nd`` rows as its queries, and the
+        projection, LN2, fc1 + GELU and fc2 run on those rows alone (``h3``: LN1(x) as planes when
+        the previous block made it, as for :meth:`forward_x3`)."""
+        T = x.shape[1]
+        H, Dh = self.c.num_heads, self.c.head_dim
+        eps, scale = self.c.layer_norm_eps, 1.0 / math.sqrt(self.c.head_dim)
+        xd = x[:, T - nd:].contiguous()   # a view for B = 1
+        if K.x3_active(x):
+            if h3 is None:
+                h3 = K.layernorm_x3(x, self.ln1.weight, self.ln1.bias, eps)
+            if K.attention_input_f32():
+                qkv = K.linear_x3(h3, self.qkv.weight, self.qkv.bias)
+                o3 = K.attention_qkv_x3f(qkv, H, Dh, scale, q0=T - nd, q_rows=nd)
+            else:
+                qkv3 = K.linear_x3(h3, self.qkv.weight, self.qkv.bias, out_x3=True)
+                o3 = K.attention_qkv_x3(qkv3, H, Dh, scale, q0=T - nd, q_rows=nd)
+            xd, h3 = K.linear_residual_ln_x3(o3, self.proj.weight, self.proj.bias, xd,
+                                             ln=(self.ln2.weight, self.ln2.bias, eps))
+            f3 = K.linear_x3(h3, self.fc1.weight, self.fc1.bias, gelu=True, out_x3=True)
+            return K.linear_residual_ln_x3(f3, self.fc2.weight, self.fc2.bias, xd, ln=None)[0]
+        h = K.layernorm(x, self.ln1.weight, self.ln1.bias, eps)
+        qkv = K.linear(h, self.qkv.weight, self.qkv.bias)
+        o = K.attention_ref(qkv, H, Dh, scale, T - nd, nd)                  # [B, nd, D]
+        xd = K.linear_residual(o, self.proj.weight, self.proj.bias, xd)
+        h = K.layernorm(xd, self.ln2.weight, self.ln2.bias, eps)
+        h = K.linear_gelu(h, self.fc1.weight, self.fc1.bias)
+        return K.linear_residual(h, self.fc2.weight, self.fc2.bias, xd)
 
     def forward(self, x: torch.Tensor, mid: Optional[torch.Tensor] = None) -> torch.Tensor:
         B, T, D = x.shape
@@ -229,11 +310,24 @@ class YolosSmall(nn.Module):
 
     # -- forward -------------------------------------------------------------------------
     def forward(self, pixels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        return self.detect(self.encode(pixels))
+        return self.detect(self.encode_detection(pixels))
 
     def encode(self, pixels: torch.Tensor) -> torch.Tensor:
         """Tokens after the last block, ``[B, T, D]`` (before ``ln_f``): every row, not only the
-        detection rows the heads read."""
+        detection rows the heads read — the last block runs in full here, whatever the detection
+        tail's rule says (:meth:`encode_detection` is the form that skips the other rows)."""
+        return self._run_blocks(*self._embed(pixels))
+
+    def encode_detection(self, pixels: torch.Tensor) -> torch.Tensor:
+        """The detection rows after the last block, ``[B, nd, D]`` (before ``ln_f``): what
+        :meth:`detect` reads of :meth:`encode`'s tokens. Where the detection tail is taken
+        (:func:`detection_tail`) the last block computes these rows only, equal to
+        ``encode(pixels)[:, -nd:]`` to fp32 rounding; elsewhere they are that slice itself."""
+        return self._run_blocks(*self._embed(pixels), det_only=True)
+
+    def _embed(self, pixels: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """The token rows before the first block (patches + class / detection tokens + position
+        embeddings) and the mid position embeddings."""
         B, _, Hh, Ww = pixels.shape
         pe, mid = self.position_embeddings((Hh, Ww))
         nd = self.c.num_detection_tokens
@@ -248,18 +342,27 @@ class YolosSmall(nn.Module):
         else:
             xp = K.patch_embed(pixels, self.patch.weight, self.patch.bias, self.c.patch_size)   # [B, P, D]
             x = torch.cat((self.cls_token.expand(B, -1, -1), xp, self.det_tokens.expand(B, -1, -1)), dim=1) + pe
-        return self._run_blocks(x, mid)
+        return x, mid
 
-    def _run_blocks(self, x: torch.Tensor, mid: Optional[torch.Tensor]) -> torch.Tensor:
+    def _run_blocks(self, x: torch.Tensor, mid: Optional[torch.Tensor], det_only: bool = False) -> torch.Tensor:
+        """Every block on ``x``: ``[B, T, D]`` — or, with ``det_only``, the detection rows
+        ``[B, nd, D]``, the last block running on those rows alone where the detection tail is taken."""
+        nd = self.c.num_detection_tokens
+        last = len(self.blocks) - 1
+        tail = det_only and detection_tail(x.shape[1], nd) and self.blocks[last].tail_supported(x)
         if K.x3_active(x):
             h3 = None
             for i, blk in enumerate(self.blocks):
+                if tail and i == last:
+                    return blk.forward_tail(x, h3, nd)
                 nxt = self.blocks[i + 1].ln1 if i + 1 < len(self.blocks) else None
                 x, h3 = blk.forward_x3(x, mid[i] if mid is not None and i < self.c.num_layers - 1 else None, h3, nxt)
         else:
             for i, blk in enumerate(self.blocks):
+                if tail and i == last:
+                    return blk.forward_tail(x, None, nd)
                 x = blk(x, mid[i] if mid is not None and i < self.c.num_layers - 1 else None)
-        return x
+        return x[:, -nd:] if det_only else x
 
     # -- image in, detections out ----------------------------------------------------------
     def _image_fused(self, img: torch.Tensor, hw: Tuple[int, int]) -> bool:
@@ -269,16 +372,18 @@ class YolosSmall(nn.Module):
         return (img.shape[0] == 1 and img.is_cuda and K.x3_active(self.pos_embed) and self.c.num_channels == 3
                 and (3 * p * p) % 32 == 0 and I.fusable(tuple(img.shape[1:3]), hw, p))
 
-    def encode_image(self, image_u8) -> torch.Tensor:
-        """:meth:`encode` from a uint8 HWC image (tensor, ndarray or PIL) or a ``processor.Frame`` (NV12 / NV21,
-        planar 4:2:0, BGR / RGBA / BGRA, pitched views: converted inside the same kernel): resized by
+    def encode_image(self, image_u8, det_only: bool = False) -> torch.Tensor:
+        """:meth:`encode` (every row, ``[B, T, D]``; with ``det_only`` :meth:`encode_detection`, the
+        detection rows ``[B, nd, D]``) from a uint8 HWC image (tensor, ndarray or PIL) or a
+        ``processor.Frame`` (NV12 / NV21, planar 4:2:0, BGR / RGBA / BGRA, pitched views: converted inside the same kernel): resized by
         ``self.processor``'s rule, normalised and split into the patch GEMM's x3 planes by one kernel
         (``ops.image.image_patch_planes``) — no fp32 image is materialised. In ``f32`` mode, off the GPU
         or for a batch it is ``encode(processor.preprocess(image))``."""
         img = self.processor.as_batch(image_u8, self.pos_embed.device)
         hw = self.processor.size(tuple(img.shape[1:3]))
         if not self._image_fused(img, hw):
-            return self.encode(self.processor.preprocess(img))
+            px = self.processor.preprocess(img)
+            return self.encode_detection(px) if det_only else self.encode(px)
         from ...ops.gemm import gemm_x3
         pe, mid = self.position_embeddings(hw)
         p = self.c.patch_size
@@ -287,7 +392,11 @@ class YolosSmall(nn.Module):
         planes, _ = self.processor.patch_planes(img, hw, patch=p)
         gemm_x3(planes, self.patch.weight.reshape(self.patch.weight.shape[0], -1), self.patch.bias,
                 residual2=pe[0, 1:1 + P], out=x[0, 1:1 + P])
-        return self._run_blocks(x, mid)
+        return self._run_blocks(x, mid, det_only=det_only)
+
+    def encode_detection_image(self, image_u8) -> torch.Tensor:
+        """:meth:`encode_detection` from an image: ``encode_image``'s input, the detection rows out."""
+        return self.encode_image(image_u8, det_only=True)
 
     def detect_image(self, image_u8, threshold: float = 0.5) -> Dict[str, torch.Tensor]:
         """Image in, detections out, with no host synchronisation (so it can be captured in a graph):
@@ -297,7 +406,7 @@ class YolosSmall(nn.Module):
         new frame written into them is what the next replay detects on).
         ``self.processor.results(count, scores, labels, boxes)`` gives the per-image lists."""
         img = self.processor.as_batch(image_u8, self.pos_embed.device)
-        logits, boxes = self.detect(self.encode_image(img))
+        logits, boxes = self.detect(self.encode_detection_image(img))
         count, scores, labels, xyxy = I.detections(logits, boxes, self._target_sizes(img), threshold)
         return {"logits": logits, "pred_boxes": boxes, "count": count, "scores": scores, "labels": labels,
                 "boxes": xyxy}
@@ -310,8 +419,8 @@ class YolosSmall(nn.Module):
                                   lambda: torch.tensor([[h, w]] * B, dtype=torch.float32).to(img.device))
 
     def detect(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """``(logits, boxes)`` from :meth:`encode`'s tokens: ``ln_f`` and the two MLP heads on the
-        detection rows."""
+        """``(logits, boxes)`` from :meth:`encode`'s tokens or :meth:`encode_detection`'s rows:
+        ``ln_f`` and the two MLP heads on the last ``nd`` rows."""
         hip = x.shape[0] == 1 and x.is_cuda and K.get_backend() == "hip"
         det = x[:, -self.c.num_detection_tokens:, :]
         if hip and x.is_contiguous() and self.heads_fusable():

@@ -528,6 +528,12 @@ def gemm_x3_f32a(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] 
 #: LDS-DMA tiles offered to the split-K partial path (32x32 MFMA and 16x16 MFMA, 4 and 8 waves)
 SPLIT_TILES = (7, 9, 10, 11, 12, 13, 14, 18, 23, 24, 29, 32, 35, 36, 38)
 SPLIT_COUNTS = (2, 3, 4)
+#: further split counts offered when the GEMM is a single row of tiles (M <= SMALL_M, the detection
+#: tail's M = 100): with N = 384 that is 3 to 12 tiles, and more K splits are the only other source
+#: of workgroups. nos_gemm_x3_partials takes at most 8 splits (three bits of its epilogue word), so
+#: 12 is not on offer; the ``Kd // stage >= 2 * splits`` rule holds for these as for SPLIT_COUNTS
+SMALL_M = 128
+SMALL_M_SPLIT_COUNTS = (6, 8)
 #: smallest slice that times split-K against the fused path: on 32-CU (CPX) slices the isolated
 #: timing picks split-K, but with all eight partitions busy the fused path serves 2% more
 #: (383.0 vs 375.6 inf/s per GPU; 64-CU request lanes keep split-K: 438.6 vs 430.7,
@@ -619,6 +625,15 @@ def split_candidates(N: int, Kd: int) -> list:
     return out
 
 
+def small_m_split_candidates(cands: list, Kd: int) -> list:
+    """The tiles of ``cands`` (:func:`split_candidates`) again with SMALL_M_SPLIT_COUNTS."""
+    out = []
+    for c in dict.fromkeys(c for c, _ in cands):
+        bk = 64 if X3_TILES[c][3].endswith("64") else 32
+        out += [(c, sp) for sp in SMALL_M_SPLIT_COUNTS if Kd // bk >= 2 * sp]
+    return out
+
+
 _fused_cache: Dict[tuple, tuple] = {}
 #: the tuner's timings per key (ms for 3 graph-replayed calls), for tools/model_replay.py --tables
 _fused_times: Dict[tuple, Dict[tuple, float]] = {}
@@ -662,7 +677,10 @@ def linear_residual_ln_x3(a3: torch.Tensor, w: torch.Tensor, b: torch.Tensor, re
         else:
             stream = torch.cuda.current_stream()
             times = {("unsplit",): _gpu_time(unsplit, stream)}
-            for c, sp in split_candidates(N, Kd):
+            cands = split_candidates(N, Kd)
+            if M <= SMALL_M:
+                cands = cands + small_m_split_candidates(cands, Kd)
+            for c, sp in cands:
                 times[("split", c, sp)] = _gpu_time(lambda c=c, sp=sp: split(c, sp), stream)
             # stream-K partials (gemm_x3k): opt-in — on the model's shapes it is 15-25% slower than
             # the best split-K / unsplit pipeline (profiles/gemm_tuner_r4_streamk.json)

@@ -163,13 +163,21 @@ def split3(x: torch.Tensor) -> torch.Tensor:
 
 
 _x3_wg: Optional[int] = None
+_x3_pipelined = True
 
 
 def set_attention_x3_pipelined(on: bool) -> None:
     """True (default): the software-pipelined x3 attention kernel; False: block-at-a-time (A/B)."""
-    global _x3_wg
+    global _x3_wg, _x3_pipelined
     _check(_L().nos_attention_x3_set_pipelined(1 if on else 0))
     _x3_wg = None
+    _x3_pipelined = bool(on)
+
+
+def attention_x3_windowed() -> bool:
+    """True when the x3 attention that would run takes a query window (``q0`` / ``q_rows``): the
+    pipelined kernels do, the block-at-a-time A/B kernel does not."""
+    return _x3_pipelined
 
 
 def set_attention_x3_group(g: int) -> None:
@@ -226,6 +234,37 @@ def attention_x3_waves(cus: int, B: int = 0, T: int = 0, H: int = 0) -> int:
     return aligned if aligned >= 0.9 * slots else slots
 
 
+#: (query-group, key-block) units per workgroup of a windowed x3 attention launch
+#: (:func:`attention_window_waves`)
+WINDOW_UNITS_PER_WG = 8
+_window_units: Optional[int] = None
+
+
+def set_attention_window_units(n: Optional[int]) -> None:
+    """Units per workgroup of a windowed launch (None = ``NOS_ATTN_WINDOW_UNITS`` or the rule's
+    :data:`WINDOW_UNITS_PER_WG`); for A/B runs."""
+    global _window_units
+    _window_units = n
+
+
+def attention_window_waves(cus: int, B: int, T: int, H: int, q_rows: int) -> int:
+    """Persistent grid of a windowed x3 attention launch (``q_rows`` queries against ``T`` keys).
+    Every workgroup that does not finish a whole key range writes a fixed partial image (8 tiles x
+    (64 x 32 + 64) fp32, about 66 KB per slot) whatever its share of key blocks, and the fixup reads
+    them all back: with few units (642 at the workload's last block, against 8988 of a full launch)
+    a grid that fills every slot of the slice is mostly partial traffic. So: one workgroup per
+    :data:`WINDOW_UNITS_PER_WG` units, capped at the slice's resident slots
+    (``profiles/attn_window_grid_r7.json``)."""
+    global _x3_wg
+    if _x3_wg is None:
+        _x3_wg = int(_L().nos_attention_x3_wg_per_cu())
+    env = os.environ.get("NOS_ATTN_WINDOW_UNITS")
+    per = _window_units if _window_units is not None else (int(env) if env else WINDOW_UNITS_PER_WG)
+    g = attention_x3_group()
+    units = B * H * (((q_rows + 31) // 32 + g - 1) // g) * ((T + 31) // 32)
+    return max(1, min(_x3_wg * cus, (units + per - 1) // max(1, per)))
+
+
 _head_block: Optional[int] = None
 
 
@@ -246,20 +285,35 @@ def attention_head_block(cus: int, heads: int) -> int:
 
 
 def attention_x3(planes: torch.Tensor, out: torch.Tensor, heads: int, head_dim: int, scale: float,
-                 waves: int, head_block: Optional[int] = None) -> torch.Tensor:
+                 waves: int, head_block: Optional[int] = None, q0: int = 0,
+                 q_rows: Optional[int] = None) -> torch.Tensor:
     """Stream-K attention over the x3 planes ``[3, B, T, 3*H*64]`` of a packed QKV tensor. ``out`` is
     fp32 ``[B, T, H*64]`` or bf16 ``[3, B, T, H*64]`` (the output leaves as x3 planes); the heads run
-    ``head_block`` at a time (default: all)."""
+    ``head_block`` at a time (default: all). With ``q_rows`` the queries are rows ``q0 .. q0+q_rows-1``
+    only (keys and values: every row) and ``out`` holds ``q_rows`` rows instead of ``T``."""
     _, B, T, _ = planes.shape
+    _check_window_out(out, B, T if q_rows is None else q_rows, heads * head_dim)
     ws = torch.empty(waves * 2 * (64 * 32 + 64) * attention_x3_group(), dtype=torch.float32, device=planes.device)
     x3_out = out.dtype == torch.bfloat16
     hb = heads if head_block is None else max(1, min(heads, int(head_block)))
     for h0 in range(0, heads, hb):
-        _check(_L().nos_attention_x3_sk_heads(planes.data_ptr(), planes[0].numel(),
-                                              None if x3_out else out.data_ptr(), out.data_ptr() if x3_out else None,
-                                              ws.data_ptr(), B, T, heads, h0, min(hb, heads - h0), head_dim, scale,
-                                              waves, _stream()))
+        o, op = (None, out.data_ptr()) if x3_out else (out.data_ptr(), None)
+        if q_rows is not None:
+            _check(_L().nos_attention_x3_sk_heads_window(planes.data_ptr(), planes[0].numel(), o, op, ws.data_ptr(), B,
+                                                         T, heads, h0, min(hb, heads - h0), head_dim, scale, waves,
+                                                         int(q0), int(q_rows), _stream()))
+        else:
+            _check(_L().nos_attention_x3_sk_heads(planes.data_ptr(), planes[0].numel(), o, op, ws.data_ptr(), B, T,
+                                                  heads, h0, min(hb, heads - h0), head_dim, scale, waves, _stream()))
     return out
+
+
+def _check_window_out(out: torch.Tensor, B: int, rows: int, D: int) -> None:
+    """The kernels index ``out`` as a contiguous ``[(3,) B, rows, D]`` buffer: refuse anything smaller
+    here, before a launch (a bad window itself is refused by the launcher)."""
+    if rows > 0 and (out.numel() != (3 if out.dtype == torch.bfloat16 else 1) * B * rows * D
+                     or not out.is_contiguous()):
+        raise ValueError(f"attention x3: out must be a contiguous buffer of B={B} x {rows} rows x {D}")
 
 
 def attention_input_f32() -> bool:
@@ -303,19 +357,26 @@ def _row_counters(device: torch.device, n: int) -> torch.Tensor:
 
 
 def attention_x3f(qkv: torch.Tensor, out: torch.Tensor, heads: int, head_dim: int, scale: float, waves: int,
-                  head_block: Optional[int] = None) -> torch.Tensor:
-    """:func:`attention_x3` from an fp32 packed QKV tensor ``[B, T, 3*H*64]`` (split in-kernel)."""
+                  head_block: Optional[int] = None, q0: int = 0, q_rows: Optional[int] = None) -> torch.Tensor:
+    """:func:`attention_x3` from an fp32 packed QKV tensor ``[B, T, 3*H*64]`` (split in-kernel). A
+    windowed launch (``q_rows``) always merges through the separate fixup launch."""
     B, T, _ = qkv.shape
     qkv = qkv.contiguous()
+    _check_window_out(out, B, T if q_rows is None else q_rows, heads * head_dim)
     ws = torch.empty(waves * 2 * (64 * 32 + 64) * attention_x3_group(), dtype=torch.float32, device=qkv.device)
     x3_out = out.dtype == torch.bfloat16
     hb = heads if head_block is None else max(1, min(heads, int(head_block)))
     L = _L()
     rows = B * hb * (((T + 31) // 32 + 7) // 8)
-    cnt = _row_counters(qkv.device, rows) if attention_merge_in_kernel() and attention_x3_wide() else None
+    cnt = (_row_counters(qkv.device, rows)
+           if q_rows is None and attention_merge_in_kernel() and attention_x3_wide() else None)
     for h0 in range(0, heads, hb):
         o, op = (None, out.data_ptr()) if x3_out else (out.data_ptr(), None)
-        if cnt is not None:
+        if q_rows is not None:
+            _check(L.nos_attention_x3f_sk_heads_window(qkv.data_ptr(), o, op, ws.data_ptr(), B, T, heads, h0,
+                                                       min(hb, heads - h0), head_dim, scale, waves, int(q0),
+                                                       int(q_rows), _stream()))
+        elif cnt is not None:
             _check(L.nos_attention_x3f_sk_heads_merged(qkv.data_ptr(), o, op, ws.data_ptr(), cnt.data_ptr(),
                                                        cnt.numel(), B, T, heads, h0, min(hb, heads - h0), head_dim,
                                                        scale, waves, _stream()))
@@ -325,15 +386,27 @@ def attention_x3f(qkv: torch.Tensor, out: torch.Tensor, heads: int, head_dim: in
     return out
 
 
-def attention_qkv_x3f(qkv: torch.Tensor, heads: int, head_dim: int, scale: float) -> torch.Tensor:
-    """fp32 packed QKV in, x3 planes ``[3, B, T, H*64]`` of the attention output out."""
+def attention_qkv_x3f(qkv: torch.Tensor, heads: int, head_dim: int, scale: float, q0: int = 0,
+                      q_rows: Optional[int] = None) -> torch.Tensor:
+    """fp32 packed QKV in, x3 planes ``[3, B, T, H*64]`` of the attention output out — with
+    ``q_rows``, ``[3, B, q_rows, H*64]``: the rows ``q0 .. q0+q_rows-1`` only."""
     B, T, _ = qkv.shape
     if not _use_hip(qkv):
-        return split3(attention_ref(qkv, heads, head_dim, scale))
-    out = torch.empty(3, B, T, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
+        return split3(attention_ref(qkv, heads, head_dim, scale, q0, q_rows))
     cus = slice_cus()
     hb = attention_head_block(cus, heads)
-    return attention_x3f(qkv, out, heads, head_dim, scale, attention_x3_waves(cus, B, T, hb), head_block=hb)
+    if q_rows is None:
+        out = torch.empty(3, B, T, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
+        return attention_x3f(qkv, out, heads, head_dim, scale, attention_x3_waves(cus, B, T, hb), head_block=hb)
+    _window_ok(q0, q_rows, T)
+    out = torch.empty(3, B, q_rows, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
+    return attention_x3f(qkv, out, heads, head_dim, scale, attention_window_waves(cus, B, T, hb, q_rows),
+                         head_block=hb, q0=q0, q_rows=q_rows)
+
+
+def _window_ok(q0: int, q_rows: int, T: int) -> None:
+    if q0 < 0 or q_rows <= 0 or q0 + q_rows > T:
+        raise ValueError(f"attention: query window [{q0}, {q0 + q_rows}) outside the {T} rows")
 
 
 def attn_proj_fusable(heads: int, head_dim: int) -> bool:
@@ -382,16 +455,23 @@ def attention_proj_ln_x3f(qkv: torch.Tensor, heads: int, head_dim: int, scale: f
     return x, planes
 
 
-def attention_qkv_x3(planes: torch.Tensor, heads: int, head_dim: int, scale: float) -> torch.Tensor:
-    """x3 planes of packed QKV in, x3 planes ``[3, B, T, H*64]`` of the attention output out."""
+def attention_qkv_x3(planes: torch.Tensor, heads: int, head_dim: int, scale: float, q0: int = 0,
+                     q_rows: Optional[int] = None) -> torch.Tensor:
+    """x3 planes of packed QKV in, x3 planes ``[3, B, T, H*64]`` of the attention output out — with
+    ``q_rows``, ``[3, B, q_rows, H*64]``: the rows ``q0 .. q0+q_rows-1`` only."""
     _, B, T, _ = planes.shape
     if not _use_hip(planes):
         qkv = (planes[0].double() + planes[1].double() + planes[2].double()).float()
-        return split3(attention_ref(qkv, heads, head_dim, scale))
-    out = torch.empty(3, B, T, heads * head_dim, dtype=torch.bfloat16, device=planes.device)
+        return split3(attention_ref(qkv, heads, head_dim, scale, q0, q_rows))
     cus = slice_cus()
     hb = attention_head_block(cus, heads)
-    return attention_x3(planes, out, heads, head_dim, scale, attention_x3_waves(cus, B, T, hb), head_block=hb)
+    if q_rows is None:
+        out = torch.empty(3, B, T, heads * head_dim, dtype=torch.bfloat16, device=planes.device)
+        return attention_x3(planes, out, heads, head_dim, scale, attention_x3_waves(cus, B, T, hb), head_block=hb)
+    _window_ok(q0, q_rows, T)
+    out = torch.empty(3, B, q_rows, heads * head_dim, dtype=torch.bfloat16, device=planes.device)
+    return attention_x3(planes, out, heads, head_dim, scale, attention_window_waves(cus, B, T, hb, q_rows),
+                        head_block=hb, q0=q0, q_rows=q_rows)
 
 
 def set_backend(name: str) -> None:
@@ -435,6 +515,10 @@ def _L() -> ctypes.CDLL:
             L.nos_attention_x3_sk_heads.argtypes = [vp, ctypes.c_size_t, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32,
                                                     i32, vp]
             L.nos_attention_x3f_sk_heads.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp]
+            L.nos_attention_x3_sk_heads_window.argtypes = [vp, ctypes.c_size_t, vp, vp, vp, i32, i32, i32, i32, i32,
+                                                           i32, f32, i32, i32, i32, vp]
+            L.nos_attention_x3f_sk_heads_window.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32,
+                                                            i32, i32, vp]
             L.nos_attention_x3f_sk_heads_merged.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32,
                                                             i32, vp]
             L.nos_attention_x3f_partials.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]
@@ -731,9 +815,15 @@ def patch_embed(pixels: torch.Tensor, w: torch.Tensor, b: torch.Tensor, patch: i
     return y.view(B, gh * gw, -1)
 
 
-def attention_ref(qkv: torch.Tensor, heads: int, head_dim: int, scale: float) -> torch.Tensor:
+def attention_ref(qkv: torch.Tensor, heads: int, head_dim: int, scale: float, q0: int = 0,
+                  q_rows: Optional[int] = None) -> torch.Tensor:
+    """``[B, T, H*Dh]`` — with ``q_rows``, the rows ``q0 .. q0+q_rows-1`` only (``[B, q_rows, H*Dh]``;
+    keys and values are every row)."""
     B, T, _ = qkv.shape
     q, k, v = qkv.view(B, T, 3, heads, head_dim).permute(2, 0, 3, 1, 4)
+    if q_rows is not None:
+        _window_ok(q0, q_rows, T)
+        q, T = q[:, :, q0:q0 + q_rows], q_rows
     o = F.scaled_dot_product_attention(q, k, v, scale=scale)
     return o.transpose(1, 2).reshape(B, T, heads * head_dim)
 
