@@ -1,5 +1,5 @@
 // Stream-K work split of a tiled GEMM, shared by the producer (gemm_x3k in gemm_x3.hip) and the
-// consumer (splitk_layernorm_f32 in kernels.hip) so both agree on which partial plane holds what.
+// consumer (splitk_layernorm_f32 in norm.hip) so both agree on which partial plane holds what.
 //
 // The GEMM's work is U = tiles * nk units (one unit = one K stage of one tile, tiles row-major,
 // a tile's stages consecutive); workgroup w of P owns units [w*U/P, (w+1)*U/P). A tile's stages

@@ -1,8 +1,9 @@
-// Device helpers shared by the x3 attention kernels of kernels.hip and attn_wide.hip: the vector
-// types, the exact three-bf16-plane split of fp32 ("x3", see kernels.hip "fp32 as three bf16
-// planes"), the 32x32 MFMA accumulator layout, the stream-K bookkeeping and the LDS tile strides.
-// attn_wide.hip is its own translation unit because it is compiled with its own code-generation
-// options (walkai_nos_amd/ops/build.py); every helper here is inline and TU-local.
+// Device helpers shared by the attention kernels of attn_x3.hip, attn_wide.hip and attn_f32.hip and
+// the plane-writing kernels of norm.hip: the vector types, the exact three-bf16-plane split of fp32
+// ("x3", see attn_x3.hip "fp32 as three bf16 planes"), the 32x32 MFMA accumulator layout, the
+// stream-K bookkeeping and the LDS tile strides. attn_wide.hip is its own translation unit because
+// it is compiled with its own code-generation options (walkai_nos_amd/ops/build.py); every helper
+// here is inline and TU-local.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -63,6 +64,14 @@ __device__ __forceinline__ float half_sum(float x) {
 // stream-K: wave w of P owns the units [w*U/P, (w+1)*U/P)
 __device__ __forceinline__ long long sk_begin(long long w, long long U, long long P) { return w * U / P; }
 
+// any P: XCD x (= phys % 8) owns the contiguous logical run of its P/8 (+1 for the first P % 8
+// XCDs) workgroups — a bijection, so a grid trimmed to query-group boundaries (252 on 256 CUs)
+// keeps each XCD on about one head's K/V
+__device__ __forceinline__ int sk_logical(int phys, int P) {
+  const int x = phys % 8, q = P / 8, r = P % 8;
+  return x * q + min(x, r) + phys / 8;
+}
+
 // floor(n / d) for 0 <= n < 2^23 through the f32 reciprocal rd = 1/d (within one of the quotient
 // there; one integer correction makes it exact): the stream-K bookkeeping of a segment as a few
 // vector instructions instead of 64-bit scalar divisions (~150 instructions each, before the
@@ -86,7 +95,7 @@ __device__ __forceinline__ f32x16 mfma_x3(const bf16x8& a0, const bf16x8& a1, co
 }
 
 // LDS tiles of the x3 kernels (bf16 elements): K rows of 64 dims padded to 72, V^T read groups at
-// a 96-element row stride (kernels.hip "x3 attention": conflict-free ds_read_b128 / read_tr16)
+// a 96-element row stride (attn_x3.hip "x3 attention": conflict-free ds_read_b128 / read_tr16)
 constexpr int XK_STR = 72, XV_STR = 96;
 constexpr int XK_PLANE = 32 * XK_STR, XV_PLANE = 32 * XV_STR;
 
@@ -100,3 +109,8 @@ int nos_attn_x3w_launch(bool fdiv, dim3 grid, hipStream_t s, const float* qkv, f
                         float* part_o, float* part_ml, int B, int T, int H, int h0, int Ht, float scale_log2e, int Pk,
                         int* cnt, int q0, int Tq);
 int nos_attn_x3w_occupancy();
+
+// attn_x3.hip: attn_sk_lds_fixup<4> as attn_f32.hip's attn_fwd_sk_lds launches it (all heads, fp32
+// output, unpinned, no query window); the instantiation exists once, in attn_x3.hip
+void nos_attn_sk_lds_fixup4_launch(dim3 grid, hipStream_t s, const float* part_o, const float* part_ml, float* out,
+                                   int B, int T, int H, int P);

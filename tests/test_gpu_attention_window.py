@@ -6,6 +6,7 @@ of the same input on the window's rows and the bound that of ``test_gpu_kernel_e
 
 Every launch writes into a NaN-filled buffer with NaN guard rows before and after the output: the
 guards must come back untouched and no NaN may be left inside."""
+import ctypes
 import os
 
 import pytest
@@ -241,11 +242,12 @@ def test_bad_windows_are_refused_on_the_host(K, q0, Tq):
     for x3 in (False, True):
         buf, out = guarded(x3, B, rows, H)
         o, op = (None, out.data_ptr()) if x3 else (out.data_ptr(), None)
-        rc = L.nos_attention_x3f_sk_heads_window(qkv.data_ptr(), o, op, ws.data_ptr(), B, T, H, 0, H, 64, SCALE, 4,
-                                                 q0, Tq, K._stream())
+        common = dict(out=o, outp=op, ws=ws.data_ptr(), B=B, T=T, H=H, head_dim=64, scale=SCALE, waves=4, q0=q0, Tq=Tq)
+        d = K._x3_desc(qkv=qkv.data_ptr(), f32in=1, **common)
+        rc = L.nos_attention_x3(ctypes.byref(d), K._stream())
         assert rc != 0 and "query window" in L.nos_kernels_last_error().decode()
-        rc = L.nos_attention_x3_sk_heads_window(planes.data_ptr(), planes[0].numel(), o, op, ws.data_ptr(), B, T, H,
-                                                0, H, 64, SCALE, 4, q0, Tq, K._stream())
+        d = K._x3_desc(qkv=planes.data_ptr(), f32in=0, plane_stride=planes[0].numel(), **common)
+        rc = L.nos_attention_x3(ctypes.byref(d), K._stream())
         assert rc != 0 and "query window" in L.nos_kernels_last_error().decode()
         torch.cuda.synchronize()
         assert bool(torch.isnan(buf.float()).all())

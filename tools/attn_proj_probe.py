@@ -35,8 +35,10 @@ def main() -> None:
     waves = K.attention_x3_waves(cus, B, T, H)
     ws = torch.empty(waves * 2 * (64 * 32 + 64) * 8, device="cuda")
     od = torch.empty(B, T, D, device="cuda")
-    K._check(L.nos_attention_x3f_partials(qkv.data_ptr(), od.data_ptr(), ws.data_ptr(), B, T, H, Dh, 0.125, waves,
-                                          K._stream()))
+
+    def partials():
+        K._attention_x3_launch(qkv, True, od, H, Dh, 0.125, waves, partials=ws)
+    partials()
     from walkai_nos_amd.ops.gemm import weight_planes
     w3 = weight_planes(w)
     x = torch.empty_like(r)
@@ -79,8 +81,7 @@ def main() -> None:
     o3 = K.attention_qkv_x3f(qkv, H, Dh, 0.125)
     K.linear_residual_ln_x3(o3, w, b, r, ln=ln)  # tune (and split the weight) before capture
     out["attention_with_fixup_us"] = timed(lambda: K.attention_qkv_x3f(qkv, H, Dh, 0.125))
-    out["attention_partials_us"] = timed(lambda: L.nos_attention_x3f_partials(
-        qkv.data_ptr(), od.data_ptr(), ws.data_ptr(), B, T, H, Dh, 0.125, waves, K._stream()))
+    out["attention_partials_us"] = timed(partials)
     out["proj_ln_unfused_us"] = timed(lambda: K.linear_residual_ln_x3(o3, w, b, r, ln=ln))
     print(json.dumps(out))
     if a.out:

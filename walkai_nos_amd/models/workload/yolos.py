@@ -127,6 +127,17 @@ class _Block(nn.Module):
         self.fc1 = nn.Linear(d, f)
         self.fc2 = nn.Linear(f, d)
 
+    def attention_x3(self, h3: torch.Tensor, q0: int = 0, q_rows: Optional[int] = None) -> torch.Tensor:
+        """QKV GEMM + attention on LN1(x) as planes; the output as planes, of every row or of the
+        rows ``q0 .. q0+q_rows-1``. QKV leaves the GEMM as fp32 (4 B per element; the attention splits
+        it in-kernel) or as planes (:func:`K.attention_input_f32`)."""
+        H, Dh = self.c.num_heads, self.c.head_dim
+        if K.attention_input_f32():
+            qkv = K.linear_x3(h3, self.qkv.weight, self.qkv.bias)
+            return K.attention_qkv_x3f(qkv, H, Dh, 1.0 / math.sqrt(Dh), q0=q0, q_rows=q_rows)
+        qkv3 = K.linear_x3(h3, self.qkv.weight, self.qkv.bias, out_x3=True)
+        return K.attention_qkv_x3(qkv3, H, Dh, 1.0 / math.sqrt(Dh), q0=q0, q_rows=q_rows)
+
     def forward_x3(self, x: torch.Tensor, mid: Optional[torch.Tensor], h3: Optional[torch.Tensor],
                    next_ln: Optional[nn.LayerNorm]) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """The x3 path with the LayerNorms folded into the producing step: ``h3`` is LN1(x) as planes
@@ -138,20 +149,13 @@ class _Block(nn.Module):
         eps = self.c.layer_norm_eps
         if h3 is None:
             h3 = K.layernorm_x3(x, self.ln1.weight, self.ln1.bias, eps)
-        if K.attention_input_f32():
+        if K.attention_input_f32() and K.attn_proj_fusable(H, Dh):
+            # attention partials -> one merge + projection + residual + LN2 kernel
             qkv = K.linear_x3(h3, self.qkv.weight, self.qkv.bias)
-            if K.attn_proj_fusable(H, Dh):
-                # attention partials -> one merge + projection + residual + LN2 kernel
-                x, h3 = K.attention_proj_ln_x3f(qkv, H, Dh, 1.0 / math.sqrt(Dh), self.proj.weight, self.proj.bias,
-                                                x, (self.ln2.weight, self.ln2.bias, eps))
-            else:
-                o3 = K.attention_qkv_x3f(qkv, H, Dh, 1.0 / math.sqrt(Dh))
-                x, h3 = K.linear_residual_ln_x3(o3, self.proj.weight, self.proj.bias, x,
-                                                ln=(self.ln2.weight, self.ln2.bias, eps))
+            x, h3 = K.attention_proj_ln_x3f(qkv, H, Dh, 1.0 / math.sqrt(Dh), self.proj.weight, self.proj.bias,
+                                            x, (self.ln2.weight, self.ln2.bias, eps))
         else:
-            qkv3 = K.linear_x3(h3, self.qkv.weight, self.qkv.bias, out_x3=True)
-            o3 = K.attention_qkv_x3(qkv3, H, Dh, 1.0 / math.sqrt(Dh))
-            x, h3 = K.linear_residual_ln_x3(o3, self.proj.weight, self.proj.bias, x,
+            x, h3 = K.linear_residual_ln_x3(self.attention_x3(h3), self.proj.weight, self.proj.bias, x,
                                             ln=(self.ln2.weight, self.ln2.bias, eps))
         f3 = K.linear_x3(h3, self.fc1.weight, self.fc1.bias, gelu=True, out_x3=True)
         nl = (next_ln.weight, next_ln.bias, next_ln.eps) if next_ln is not None else None
@@ -179,12 +183,7 @@ class _Block(nn.Module):
         if K.x3_active(x):
             if h3 is None:
                 h3 = K.layernorm_x3(x, self.ln1.weight, self.ln1.bias, eps)
-            if K.attention_input_f32():
-                qkv = K.linear_x3(h3, self.qkv.weight, self.qkv.bias)
-                o3 = K.attention_qkv_x3f(qkv, H, Dh, scale, q0=T - nd, q_rows=nd)
-            else:
-                qkv3 = K.linear_x3(h3, self.qkv.weight, self.qkv.bias, out_x3=True)
-                o3 = K.attention_qkv_x3(qkv3, H, Dh, scale, q0=T - nd, q_rows=nd)
+            o3 = self.attention_x3(h3, q0=T - nd, q_rows=nd)
             xd, h3 = K.linear_residual_ln_x3(o3, self.proj.weight, self.proj.bias, xd,
                                              ln=(self.ln2.weight, self.ln2.bias, eps))
             f3 = K.linear_x3(h3, self.fc1.weight, self.fc1.bias, gelu=True, out_x3=True)
@@ -204,13 +203,7 @@ class _Block(nn.Module):
             # every fp32 product on the bf16 matrix cores in x3 form: activations leave their
             # producer as three exact bf16 planes; the residual stream stays fp32
             h3 = K.layernorm_x3(x, self.ln1.weight, self.ln1.bias, self.c.layer_norm_eps)
-            if K.attention_input_f32():
-                # QKV leaves the GEMM as fp32 (4 B per element); attention splits it in-kernel
-                qkv = K.linear_x3(h3, self.qkv.weight, self.qkv.bias)
-                o3 = K.attention_qkv_x3f(qkv, H, Dh, 1.0 / math.sqrt(Dh))
-            else:
-                qkv3 = K.linear_x3(h3, self.qkv.weight, self.qkv.bias, out_x3=True)
-                o3 = K.attention_qkv_x3(qkv3, H, Dh, 1.0 / math.sqrt(Dh))
+            o3 = self.attention_x3(h3)
             x = K.linear_x3(o3, self.proj.weight, self.proj.bias, residual=x)
             h3 = K.layernorm_x3(x, self.ln2.weight, self.ln2.bias, self.c.layer_norm_eps)
             f3 = K.linear_x3(h3, self.fc1.weight, self.fc1.bias, gelu=True, out_x3=True)

@@ -114,7 +114,8 @@ TARGETS: Sequence[Target] = (
     Target("libnos_hbmlimit.so", ["hbm_limit.cpp"], "g++", flags=["-D__HIP_PLATFORM_AMD__"], libs=["dl"]),
     Target("libnos_barrier.so", ["rccl_barrier.cpp"], "g++", flags=["-D__HIP_PLATFORM_AMD__"],
            libs=["rccl", "amdhip64"]),
-    Target("libnos_kernels.so", ["kernels.hip", "gemm.hip", "gemm_x3.hip", "head.hip", "attn_proj.hip", "attn_wide.hip"],
+    Target("libnos_kernels.so", ["kernels.hip", "norm.hip", "attn_f32.hip", "attn_x3.hip", "gemm.hip", "gemm_x3.hip",
+                                 "head.hip", "attn_proj.hip", "attn_wide.hip"],
            "hipcc", source_flags={"attn_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}),
     # the image half of the workload (uint8 image -> patch planes, logits -> detections): a library of its own
     Target("libnos_image.so", ["image.hip"], "hipcc"),

@@ -5,7 +5,8 @@ On a GPU tensor the HIP path is mandatory unless the caller explicitly selects t
 backend (used only as the measured baseline in the benchmark's A/B mode): a missing
 ``libnos_kernels.so`` raises instead of silently falling back.
 
-Kernels (``csrc/kernels.hip``, ``csrc/gemm_x3.hip``, ``csrc/gemm.hip``):
+Kernels (``csrc/norm.hip``, ``csrc/attn_x3.hip``, ``csrc/attn_wide.hip``, ``csrc/attn_f32.hip``,
+``csrc/gemm_x3.hip``, ``csrc/gemm.hip``; ``csrc/kernels.hip`` holds the error string and the pin they share):
 
 * fp32 matmuls run in the **x3** form by default (``set_fp32_matmul``): every fp32 operand as three
   exact bf16 planes, six bf16 MFMAs per block, fp32-accurate; producers emit planes directly
@@ -101,15 +102,30 @@ _total_cus: Optional[int] = None
 
 
 _waves_per_cu: Optional[int] = None
+_x3_wg: Optional[int] = None
 _variant = 0
+
+
+def _drop_occupancy() -> None:
+    """Every attention setter calls this: which kernel the library asks the occupancy of follows its
+    switches, so neither cached answer outlives a change of any of them."""
+    global _waves_per_cu, _x3_wg
+    _waves_per_cu = _x3_wg = None
+
+
+def _x3_wg_per_cu() -> int:
+    global _x3_wg
+    if _x3_wg is None:
+        _x3_wg = int(_L().nos_attention_x3_wg_per_cu())
+    return _x3_wg
 
 
 def set_attention_variant(variant: int) -> None:
     """0 = LDS-shared K/V workgroup kernel (default); 2 / 3 = one-wave-per-tile stream-K kernel
     with 2 or 3 resident waves per SIMD (A/B reference)."""
-    global _waves_per_cu, _variant
+    global _variant
     _check(_L().nos_attention_set_variant(variant))
-    _waves_per_cu = None
+    _drop_occupancy()
     _variant = variant
 
 
@@ -162,30 +178,23 @@ def split3(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
-_x3_wg: Optional[int] = None
-_x3_pipelined = True
-
-
 def set_attention_x3_pipelined(on: bool) -> None:
     """True (default): the software-pipelined x3 attention kernel; False: block-at-a-time (A/B)."""
-    global _x3_wg, _x3_pipelined
     _check(_L().nos_attention_x3_set_pipelined(1 if on else 0))
-    _x3_wg = None
-    _x3_pipelined = bool(on)
+    _drop_occupancy()
 
 
 def attention_x3_windowed() -> bool:
     """True when the x3 attention that would run takes a query window (``q0`` / ``q_rows``): the
     pipelined kernels do, the block-at-a-time A/B kernel does not."""
-    return _x3_pipelined
+    return bool(_L().nos_attention_x3_pipelined())
 
 
 def set_attention_x3_group(g: int) -> None:
     """Query tiles per workgroup of the pipelined x3 kernel: 4 (two 256-thread workgroups per CU)
     or 8 (one 512-thread workgroup per CU sharing every K/V block: half the K/V traffic)."""
-    global _x3_wg
     _check(_L().nos_attention_x3_set_group(int(g)))
-    _x3_wg = None
+    _drop_occupancy()
 
 
 def set_attention_x3_wide(on: bool) -> None:
@@ -194,6 +203,7 @@ def set_attention_x3_wide(on: bool) -> None:
     two-waves-per-SIMD ``attn_fwd_x3p<8>``. Same units, partials and per-tile arithmetic: the
     outputs are bit-identical (``profiles/attn_wide_ab_r6.json``: the wide kernel 4-8% faster)."""
     _check(_L().nos_attention_x3_set_wide(1 if on else 0))
+    _drop_occupancy()
 
 
 def attention_x3_wide_default() -> bool:
@@ -216,10 +226,7 @@ def attention_x3_waves(cus: int, B: int = 0, T: int = 0, H: int = 0) -> int:
     one or two whole key ranges with one prologue each. Measured on the whole GPU (T = 3401, 84
     groups): 252 workgroups 100 us vs 256 120 us (`profiles/attn_grid_r2.json`); DPX 126 vs 128:
     145 vs 153 us; smaller slices keep every slot."""
-    global _x3_wg
-    if _x3_wg is None:
-        _x3_wg = int(_L().nos_attention_x3_wg_per_cu())
-    per_cu = _x3_wg
+    per_cu = _x3_wg_per_cu()
     if not T:
         return per_cu * cus
     nk = (T + 31) // 32
@@ -255,14 +262,11 @@ def attention_window_waves(cus: int, B: int, T: int, H: int, q_rows: int) -> int
     a grid that fills every slot of the slice is mostly partial traffic. So: one workgroup per
     :data:`WINDOW_UNITS_PER_WG` units, capped at the slice's resident slots
     (``profiles/attn_window_grid_r7.json``)."""
-    global _x3_wg
-    if _x3_wg is None:
-        _x3_wg = int(_L().nos_attention_x3_wg_per_cu())
     env = os.environ.get("NOS_ATTN_WINDOW_UNITS")
     per = _window_units if _window_units is not None else (int(env) if env else WINDOW_UNITS_PER_WG)
     g = attention_x3_group()
     units = B * H * (((q_rows + 31) // 32 + g - 1) // g) * ((T + 31) // 32)
-    return max(1, min(_x3_wg * cus, (units + per - 1) // max(1, per)))
+    return max(1, min(_x3_wg_per_cu() * cus, (units + per - 1) // max(1, per)))
 
 
 _head_block: Optional[int] = None
@@ -284,6 +288,50 @@ def attention_head_block(cus: int, heads: int) -> int:
     return max(1, min(heads, n))
 
 
+class NosAttnX3(ctypes.Structure):
+    """The x3 attention's launch descriptor (``csrc/attn_x3.h``, field for field)."""
+    _fields_ = [("size", ctypes.c_int), ("f32in", ctypes.c_int), ("qkv", ctypes.c_void_p),
+                ("plane_stride", ctypes.c_size_t), ("out", ctypes.c_void_p), ("outp", ctypes.c_void_p),
+                ("ws", ctypes.c_void_p), ("cnt", ctypes.c_void_p), ("ncnt", ctypes.c_int), ("fixup", ctypes.c_int),
+                ("B", ctypes.c_int), ("T", ctypes.c_int), ("H", ctypes.c_int), ("h0", ctypes.c_int),
+                ("hn", ctypes.c_int), ("head_dim", ctypes.c_int), ("scale", ctypes.c_float),
+                ("waves", ctypes.c_int), ("q0", ctypes.c_int), ("Tq", ctypes.c_int)]
+
+
+def _x3_desc(**fields) -> NosAttnX3:
+    """A descriptor from its fields by name; unnamed ones are zero / null, except: every head, every
+    query row, the separate fixup launch."""
+    fields = {"h0": 0, "hn": fields["H"], "q0": 0, "Tq": fields["T"], "fixup": 1, **fields}
+    return NosAttnX3(size=ctypes.sizeof(NosAttnX3), **fields)
+
+
+def _x3_workspace(waves: int, group: int, device) -> torch.Tensor:
+    """Stream-K partials of an x3 attention launch: two slots per workgroup of ``group`` query tiles,
+    each tile a ``[64][32]`` image and its ``(m, l)`` pairs."""
+    return torch.empty(waves * 2 * (64 * 32 + 64) * group, dtype=torch.float32, device=device)
+
+
+def _attention_x3_launch(src: torch.Tensor, f32in: bool, out: torch.Tensor, heads: int, head_dim: int, scale: float,
+                         waves: int, head_block: Optional[int] = None, q0: int = 0, q_rows: Optional[int] = None,
+                         merge: bool = False, partials: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One ``nos_attention_x3`` launch per block of ``head_block`` heads (default: all) over ``src``:
+    fp32 ``[B, T, 3*H*64]`` (``f32in``) or its planes ``[3, B, T, 3*H*64]``. ``partials``: the caller's
+    workspace, left unmerged for it (no fixup)."""
+    B, T = src.shape[-3], src.shape[-2]
+    _check_window_out(out, B, T if q_rows is None else q_rows, heads * head_dim)
+    ws = _x3_workspace(waves, attention_x3_group(), src.device) if partials is None else partials
+    o, op = (None, out.data_ptr()) if out.dtype == torch.bfloat16 else (out.data_ptr(), None)
+    hb = heads if head_block is None else max(1, min(heads, int(head_block)))
+    cnt = _row_counters(src.device, B * hb * (((T + 31) // 32 + 7) // 8)) if merge else None
+    for h0 in range(0, heads, hb):
+        d = _x3_desc(qkv=src.data_ptr(), f32in=f32in, plane_stride=0 if f32in else src[0].numel(), out=o, outp=op,
+                     ws=ws.data_ptr(), cnt=cnt.data_ptr() if merge else None, ncnt=cnt.numel() if merge else 0,
+                     fixup=partials is None, B=B, T=T, H=heads, h0=h0, hn=min(hb, heads - h0), head_dim=head_dim,
+                     scale=scale, waves=waves, q0=int(q0), Tq=T if q_rows is None else int(q_rows))
+        _check(_L().nos_attention_x3(ctypes.byref(d), _stream()))
+    return out
+
+
 def attention_x3(planes: torch.Tensor, out: torch.Tensor, heads: int, head_dim: int, scale: float,
                  waves: int, head_block: Optional[int] = None, q0: int = 0,
                  q_rows: Optional[int] = None) -> torch.Tensor:
@@ -291,21 +339,7 @@ def attention_x3(planes: torch.Tensor, out: torch.Tensor, heads: int, head_dim: 
     fp32 ``[B, T, H*64]`` or bf16 ``[3, B, T, H*64]`` (the output leaves as x3 planes); the heads run
     ``head_block`` at a time (default: all). With ``q_rows`` the queries are rows ``q0 .. q0+q_rows-1``
     only (keys and values: every row) and ``out`` holds ``q_rows`` rows instead of ``T``."""
-    _, B, T, _ = planes.shape
-    _check_window_out(out, B, T if q_rows is None else q_rows, heads * head_dim)
-    ws = torch.empty(waves * 2 * (64 * 32 + 64) * attention_x3_group(), dtype=torch.float32, device=planes.device)
-    x3_out = out.dtype == torch.bfloat16
-    hb = heads if head_block is None else max(1, min(heads, int(head_block)))
-    for h0 in range(0, heads, hb):
-        o, op = (None, out.data_ptr()) if x3_out else (out.data_ptr(), None)
-        if q_rows is not None:
-            _check(_L().nos_attention_x3_sk_heads_window(planes.data_ptr(), planes[0].numel(), o, op, ws.data_ptr(), B,
-                                                         T, heads, h0, min(hb, heads - h0), head_dim, scale, waves,
-                                                         int(q0), int(q_rows), _stream()))
-        else:
-            _check(_L().nos_attention_x3_sk_heads(planes.data_ptr(), planes[0].numel(), o, op, ws.data_ptr(), B, T,
-                                                  heads, h0, min(hb, heads - h0), head_dim, scale, waves, _stream()))
-    return out
+    return _attention_x3_launch(planes, False, out, heads, head_dim, scale, waves, head_block, q0, q_rows)
 
 
 def _check_window_out(out: torch.Tensor, B: int, rows: int, D: int) -> None:
@@ -360,48 +394,36 @@ def attention_x3f(qkv: torch.Tensor, out: torch.Tensor, heads: int, head_dim: in
                   head_block: Optional[int] = None, q0: int = 0, q_rows: Optional[int] = None) -> torch.Tensor:
     """:func:`attention_x3` from an fp32 packed QKV tensor ``[B, T, 3*H*64]`` (split in-kernel). A
     windowed launch (``q_rows``) always merges through the separate fixup launch."""
-    B, T, _ = qkv.shape
-    qkv = qkv.contiguous()
-    _check_window_out(out, B, T if q_rows is None else q_rows, heads * head_dim)
-    ws = torch.empty(waves * 2 * (64 * 32 + 64) * attention_x3_group(), dtype=torch.float32, device=qkv.device)
-    x3_out = out.dtype == torch.bfloat16
-    hb = heads if head_block is None else max(1, min(heads, int(head_block)))
-    L = _L()
-    rows = B * hb * (((T + 31) // 32 + 7) // 8)
-    cnt = (_row_counters(qkv.device, rows)
-           if q_rows is None and attention_merge_in_kernel() and attention_x3_wide() else None)
-    for h0 in range(0, heads, hb):
-        o, op = (None, out.data_ptr()) if x3_out else (out.data_ptr(), None)
-        if q_rows is not None:
-            _check(L.nos_attention_x3f_sk_heads_window(qkv.data_ptr(), o, op, ws.data_ptr(), B, T, heads, h0,
-                                                       min(hb, heads - h0), head_dim, scale, waves, int(q0),
-                                                       int(q_rows), _stream()))
-        elif cnt is not None:
-            _check(L.nos_attention_x3f_sk_heads_merged(qkv.data_ptr(), o, op, ws.data_ptr(), cnt.data_ptr(),
-                                                       cnt.numel(), B, T, heads, h0, min(hb, heads - h0), head_dim,
-                                                       scale, waves, _stream()))
-        else:
-            _check(L.nos_attention_x3f_sk_heads(qkv.data_ptr(), o, op, ws.data_ptr(), B, T, heads, h0,
-                                                min(hb, heads - h0), head_dim, scale, waves, _stream()))
-    return out
+    merge = q_rows is None and attention_merge_in_kernel() and attention_x3_wide()
+    return _attention_x3_launch(qkv.contiguous(), True, out, heads, head_dim, scale, waves, head_block, q0, q_rows,
+                                merge=merge)
+
+
+def _attention_qkv_x3(src: torch.Tensor, f32in: bool, heads: int, head_dim: int, scale: float, q0: int,
+                      q_rows: Optional[int]) -> torch.Tensor:
+    """The body of :func:`attention_qkv_x3f` / :func:`attention_qkv_x3`: the output planes and the grid
+    for the slice, then the launcher of ``src``'s kind (by its public name: tests spy on those)."""
+    B, T = src.shape[-3], src.shape[-2]
+    if not _use_hip(src):
+        qkv = src if f32in else (src[0].double() + src[1].double() + src[2].double()).float()
+        return split3(attention_ref(qkv, heads, head_dim, scale, q0, q_rows))
+    launch = attention_x3f if f32in else attention_x3
+    cus = slice_cus()
+    hb = attention_head_block(cus, heads)
+    if q_rows is None:
+        out = torch.empty(3, B, T, heads * head_dim, dtype=torch.bfloat16, device=src.device)
+        return launch(src, out, heads, head_dim, scale, attention_x3_waves(cus, B, T, hb), head_block=hb)
+    _window_ok(q0, q_rows, T)
+    out = torch.empty(3, B, q_rows, heads * head_dim, dtype=torch.bfloat16, device=src.device)
+    return launch(src, out, heads, head_dim, scale, attention_window_waves(cus, B, T, hb, q_rows),
+                  head_block=hb, q0=q0, q_rows=q_rows)
 
 
 def attention_qkv_x3f(qkv: torch.Tensor, heads: int, head_dim: int, scale: float, q0: int = 0,
                       q_rows: Optional[int] = None) -> torch.Tensor:
     """fp32 packed QKV in, x3 planes ``[3, B, T, H*64]`` of the attention output out — with
     ``q_rows``, ``[3, B, q_rows, H*64]``: the rows ``q0 .. q0+q_rows-1`` only."""
-    B, T, _ = qkv.shape
-    if not _use_hip(qkv):
-        return split3(attention_ref(qkv, heads, head_dim, scale, q0, q_rows))
-    cus = slice_cus()
-    hb = attention_head_block(cus, heads)
-    if q_rows is None:
-        out = torch.empty(3, B, T, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
-        return attention_x3f(qkv, out, heads, head_dim, scale, attention_x3_waves(cus, B, T, hb), head_block=hb)
-    _window_ok(q0, q_rows, T)
-    out = torch.empty(3, B, q_rows, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
-    return attention_x3f(qkv, out, heads, head_dim, scale, attention_window_waves(cus, B, T, hb, q_rows),
-                         head_block=hb, q0=q0, q_rows=q_rows)
+    return _attention_qkv_x3(qkv, True, heads, head_dim, scale, q0, q_rows)
 
 
 def _window_ok(q0: int, q_rows: int, T: int) -> None:
@@ -436,11 +458,10 @@ def attention_proj_ln_x3f(qkv: torch.Tensor, heads: int, head_dim: int, scale: f
     qkv = qkv.contiguous()
     if waves is None:
         waves = attention_x3_waves(slice_cus(), B, T, heads)
-    ws = torch.empty(waves * 2 * (64 * 32 + 64) * 8, dtype=torch.float32, device=qkv.device)
     odirect = torch.empty(B, T, D, dtype=torch.float32, device=qkv.device)
+    ws = _x3_workspace(waves, 8, qkv.device)
+    _attention_x3_launch(qkv, True, odirect, heads, head_dim, scale, waves, partials=ws)
     L = _L()
-    _check(L.nos_attention_x3f_partials(qkv.data_ptr(), odirect.data_ptr(), ws.data_ptr(), B, T, heads, head_dim,
-                                        scale, waves, _stream()))
     w3 = weight_planes(w)
     res = residual.contiguous()
     if res.shape != (B, T, D) and res.numel() != B * T * D:
@@ -459,19 +480,7 @@ def attention_qkv_x3(planes: torch.Tensor, heads: int, head_dim: int, scale: flo
                      q_rows: Optional[int] = None) -> torch.Tensor:
     """x3 planes of packed QKV in, x3 planes ``[3, B, T, H*64]`` of the attention output out — with
     ``q_rows``, ``[3, B, q_rows, H*64]``: the rows ``q0 .. q0+q_rows-1`` only."""
-    _, B, T, _ = planes.shape
-    if not _use_hip(planes):
-        qkv = (planes[0].double() + planes[1].double() + planes[2].double()).float()
-        return split3(attention_ref(qkv, heads, head_dim, scale, q0, q_rows))
-    cus = slice_cus()
-    hb = attention_head_block(cus, heads)
-    if q_rows is None:
-        out = torch.empty(3, B, T, heads * head_dim, dtype=torch.bfloat16, device=planes.device)
-        return attention_x3(planes, out, heads, head_dim, scale, attention_x3_waves(cus, B, T, hb), head_block=hb)
-    _window_ok(q0, q_rows, T)
-    out = torch.empty(3, B, q_rows, heads * head_dim, dtype=torch.bfloat16, device=planes.device)
-    return attention_x3(planes, out, heads, head_dim, scale, attention_window_waves(cus, B, T, hb, q_rows),
-                        head_block=hb, q0=q0, q_rows=q_rows)
+    return _attention_qkv_x3(planes, False, heads, head_dim, scale, q0, q_rows)
 
 
 def set_backend(name: str) -> None:
@@ -495,7 +504,6 @@ def _L() -> ctypes.CDLL:
         if _lib is None:
             L = load(LIB)
             vp, i32, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-            L.nos_layernorm_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, vp]
             L.nos_layernorm_f32_grid.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]
             L.nos_bias_gelu_f32.argtypes = [vp, vp, i32, i32, vp]
             L.nos_attention_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp]
@@ -511,17 +519,7 @@ def _L() -> ctypes.CDLL:
             L.nos_attention_x3_set_pipelined.argtypes = [i32]
             L.nos_attention_x3_set_group.argtypes = [i32]
             L.nos_attention_x3_set_wide.argtypes = [i32]
-            L.nos_attention_x3_sk.argtypes = [vp, ctypes.c_size_t, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]
-            L.nos_attention_x3_sk_heads.argtypes = [vp, ctypes.c_size_t, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32,
-                                                    i32, vp]
-            L.nos_attention_x3f_sk_heads.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp]
-            L.nos_attention_x3_sk_heads_window.argtypes = [vp, ctypes.c_size_t, vp, vp, vp, i32, i32, i32, i32, i32,
-                                                           i32, f32, i32, i32, i32, vp]
-            L.nos_attention_x3f_sk_heads_window.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32,
-                                                            i32, i32, vp]
-            L.nos_attention_x3f_sk_heads_merged.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32,
-                                                            i32, vp]
-            L.nos_attention_x3f_partials.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]
+            L.nos_attention_x3.argtypes = [ctypes.POINTER(NosAttnX3), vp]
             L.nos_attn_merge_proj_ln.argtypes = [vp, i32, vp, i32, i32, i32, vp, ctypes.c_size_t, vp, vp, vp, vp, f32,
                                                  vp, vp, vp]
             L.nos_attn_proj_last_error.restype = ctypes.c_char_p
