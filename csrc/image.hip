@@ -20,6 +20,10 @@
 //    BGRA: the colour bytes at offsets the host passes, a fourth byte never read as colour) at any row
 //    pitch, batch stride and alignment, so a crop or a padded capture buffer is read in place. All of them
 //    write RGB bytes in column groups of 4 into the LDS tile, and share every pass behind it.
+//  * image_patch_planes_yuv<Yuv<layout, hsub, sample bytes>> — the general YUV front end behind one descriptor
+//    (image_yuv.h): planar, semi-planar or packed 4:2:2 (YUY2 / UYVY / YVYU); 4:2:0, 4:2:2 or 4:4:4; 8-bit
+//    samples, or 10 / 12-bit codes in 16-bit words (P010's high bits, yuv420p10le's low bits), by a table scaled
+//    to the depth. Again only a staging loop (stage_yuv); the six entries above are as they were.
 //  * detections_f32 — softmax over the class logits, the best of the first L classes, the box in
 //    corner format scaled to the original image, and a stable compaction of the rows above the
 //    threshold; one workgroup per image, one wave per row.
@@ -29,6 +33,8 @@
 #include <cstdint>
 #include <cstdlib>
 #include <string>
+
+#include "image_yuv.h"
 
 namespace {
 thread_local std::string g_err;
@@ -93,9 +99,27 @@ struct PackedArgs {
 // packed pixels 12 or 16 source bytes; three dwords of RGB out): NG groups fit a row of the LDS tile, and
 // any GROUP_FMAX_W = 69 columns lie inside 18 consecutive groups wherever they start, so these layouts
 // cover footprints of up to 69 columns (scale 4 at patch 16); the host falls back past that.
-enum class Src { RGB, NV12, NV21, YUV420P, PACKED3, PACKED4 };
+// YUV is the general front end (image_yuv.h): its staging loop is instantiated per Yuv<layout, hsub, sample bytes>.
+enum class Src { RGB, NV12, NV21, YUV420P, PACKED3, PACKED4, YUV };
 constexpr int NG = RS / 12, GROUP_FMAX_W = NG * 4 - 3;
 constexpr int NV12_FMAX_W = GROUP_FMAX_W, YUV420P_FMAX_W = GROUP_FMAX_W, PACKED_FMAX_W = GROUP_FMAX_W;
+constexpr int YUV_FMAX_W = GROUP_FMAX_W;
+
+// The source of image_patch_planes_yuv_*: NosYuvSrc's runtime fields (all wave-uniform) and its planes; what
+// the instantiation fixes (layout, hsub, sample bytes) is not repeated here. mask = 2^depth - 1.
+struct YuvArgs {
+  PlaneArg pl[3];
+  int tab[12];
+  int vsub, depth, shift, mask, order;
+};
+enum { YUV_PLANAR = 0, YUV_SEMI = 1, YUV_PACKED = 2 };
+template <int LAYOUT_, int HSUB_, int SB_>
+struct Yuv {
+  static constexpr int LAYOUT = LAYOUT_, HSUB = HSUB_, SB = SB_;
+};
+struct NoYuv {
+  static constexpr int LAYOUT = -1, HSUB = 0, SB = 1;
+};
 
 // four bytes at q, of which those inside [lo, hi) are read: one aligned dword where q allows it
 __device__ __forceinline__ uint32_t load4(uintptr_t q, uintptr_t lo, uintptr_t hi) {
@@ -158,9 +182,82 @@ __device__ __forceinline__ void yuv_to_rgb4(const int* tab, uint32_t yy, Chroma 
   store_rgb4(dst, px);
 }
 
-// SrcArgs: what the layout's staging loop reads besides ImgArgs (Nv12Args, PlanarArgs, PackedArgs; the
-// contiguous RGB source is ImgArgs::img and takes an empty Nv12Args)
-template <Src S, class SrcArgs>
+// nv12_channel at any sample depth: the table is scaled by 2^(8 + depth), so the sum is clamped to
+// [0, 2^(16 + depth)) and the channel is its bits from 8 + depth up (clamp, then shift: see nv12_channel).
+// Exact in int32: the host checks the coefficients (24 bits) and the sum stays below 2^30 up to depth 12.
+__device__ __forceinline__ uint32_t yuv_channel(const int* t, int c, int y, int u, int v, int depth) {
+  const int s = __mul24(t[3 * c], y) + __mul24(t[3 * c + 1], u) + __mul24(t[3 * c + 2], v) + (1 << (7 + depth));
+  return uint32_t(min(max(s, 0), (1 << (16 + depth)) - 1)) >> (8 + depth);
+}
+
+// sample k of the dwords w (lowest address first): a byte, or a little-endian 16-bit word's code
+template <int SB>
+__device__ __forceinline__ int yuv_sample(const uint32_t* w, int k, int shift, int mask) {
+  if constexpr (SB == 1) return int((w[k >> 2] >> (8 * (k & 3))) & 255u);
+  else return int((((w[k >> 1] >> (16 * (k & 1))) & 0xffffu) >> shift) & uint32_t(mask));
+}
+
+// Four columns sx .. sx + 3 of row sy of a Yuv<layout, hsub, sample bytes> source as a column group of the LDS
+// tile. Nearest chroma: luma (r, c) takes chroma (r >> vsub, c >> hsub), so the group has 4 >> hsub chroma
+// samples under it. Reads: 4 * SB luma bytes and (4 >> hsub) * SB bytes of each chroma plane (planar), or
+// twice that of the interleaved pairs (semi-planar), or the group's two 4-byte macropixels in one read (packed).
+template <class Y>
+__device__ __forceinline__ void stage_yuv(const YuvArgs& n, int b, int sy, int sx, uint32_t* dst) {
+  constexpr int SB = Y::SB, HSUB = Y::HSUB, NC = 4 >> HSUB;
+  const int depth = SB == 1 ? 8 : n.depth, shift = SB == 1 ? 0 : n.shift, mask = SB == 1 ? 255 : n.mask;
+  int yy[4], uu[4], vv[4];
+  if constexpr (Y::LAYOUT == YUV_PACKED) {
+    // a macropixel is Y0 U Y1 V (0), U Y0 V Y1 (1) or Y0 V Y1 U (2): bit offsets of the first luma, U and V
+    const PlaneArg& s = n.pl[0];
+    const int ys = n.order == 1 ? 8 : 0, us = n.order == 0 ? 8 : n.order == 1 ? 0 : 24,
+              vs = n.order == 0 ? 24 : n.order == 1 ? 16 : 8;
+    uint32_t w[2];
+    load_bytes<8>(w, reinterpret_cast<uintptr_t>(s.p) + b * s.bs + sy * s.pitch + sx * 2, s.lo, s.hi);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      yy[2 * i] = int((w[i] >> ys) & 255u), yy[2 * i + 1] = int((w[i] >> (16 + ys)) & 255u);
+      uu[i] = int((w[i] >> us) & 255u), vv[i] = int((w[i] >> vs) & 255u);
+    }
+  } else {
+    const PlaneArg& py = n.pl[0];
+    uint32_t wy[SB];
+    load_bytes<4 * SB>(wy, reinterpret_cast<uintptr_t>(py.p) + b * py.bs + sy * py.pitch + sx * SB, py.lo, py.hi);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) yy[k] = yuv_sample<SB>(wy, k, shift, mask);
+    const int cy = sy >> n.vsub, cx = sx >> HSUB;
+    if constexpr (Y::LAYOUT == YUV_PLANAR) {
+      const PlaneArg &pu = n.pl[1], &pv = n.pl[2];
+      uint32_t wu[(NC * SB + 3) / 4], wv[(NC * SB + 3) / 4];
+      load_bytes<NC * SB>(wu, reinterpret_cast<uintptr_t>(pu.p) + b * pu.bs + cy * pu.pitch + cx * SB, pu.lo, pu.hi);
+      load_bytes<NC * SB>(wv, reinterpret_cast<uintptr_t>(pv.p) + b * pv.bs + cy * pv.pitch + cx * SB, pv.lo, pv.hi);
+#pragma unroll
+      for (int i = 0; i < NC; ++i) uu[i] = yuv_sample<SB>(wu, i, shift, mask), vv[i] = yuv_sample<SB>(wv, i, shift, mask);
+    } else {
+      // pairs of (U, V), or (V, U) with order 1
+      const PlaneArg& pc = n.pl[1];
+      uint32_t wc[(2 * NC * SB + 3) / 4];
+      load_bytes<2 * NC * SB>(wc, reinterpret_cast<uintptr_t>(pc.p) + b * pc.bs + cy * pc.pitch + cx * 2 * SB, pc.lo,
+                              pc.hi);
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        const int c0 = yuv_sample<SB>(wc, 2 * i, shift, mask), c1 = yuv_sample<SB>(wc, 2 * i + 1, shift, mask);
+        uu[i] = n.order ? c1 : c0, vv[i] = n.order ? c0 : c1;
+      }
+    }
+  }
+  uint32_t px[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int y = yy[k] - n.tab[9], u = uu[k >> HSUB] - n.tab[10], v = vv[k >> HSUB] - n.tab[11];
+    px[k] = yuv_channel(n.tab, 0, y, u, v, depth) | yuv_channel(n.tab, 1, y, u, v, depth) << 8 |
+            yuv_channel(n.tab, 2, y, u, v, depth) << 16;
+  }
+  store_rgb4(dst, px);
+}
+
+// SrcArgs: what the layout's staging loop reads besides ImgArgs (Nv12Args, PlanarArgs, PackedArgs, YuvArgs; the
+// contiguous RGB source is ImgArgs::img and takes an empty Nv12Args). Y: Src::YUV's Yuv<...>.
+template <Src S, class SrcArgs, class Y = NoYuv>
 __device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const SrcArgs& n) {
   constexpr bool GROUPS = S != Src::RGB;
   __shared__ __attribute__((aligned(16))) uint8_t src[FMAX * RS];
@@ -221,6 +318,8 @@ __device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const 
           load_bytes<2>(&vv, qv, n.v.lo, n.v.hi);
           yuv_to_rgb4(n.tab, load4(qy, n.y.lo, n.y.hi),
                       [uu, vv](int i, int v) { return ((v ? vv : uu) >> (8 * i)) & 255; }, dst);
+        } else if constexpr (S == Src::YUV) {
+          stage_yuv<Y>(n, b, sy, sx, dst);
         } else {
           // 4 pixels of C = 3 or 4 bytes: their 12 or 16 bytes from the row's aligned dwords, then the three
           // colour bytes of each by their offsets in a pixel (a fourth byte is dropped here)
@@ -323,6 +422,12 @@ __global__ __launch_bounds__(256) void image_patch_planes_packed3(ImgArgs a, Pac
 
 __global__ __launch_bounds__(256) void image_patch_planes_packed4(ImgArgs a, PackedArgs n) {
   image_patch_planes_body<Src::PACKED4>(a, n);
+}
+
+// the general YUV front end: one instantiation per (layout, hsub, sample bytes) the host launches
+template <class Y>
+__global__ __launch_bounds__(256) void image_patch_planes_yuv(ImgArgs a, YuvArgs n) {
+  image_patch_planes_body<Src::YUV, YuvArgs, Y>(a, n);
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -636,6 +741,80 @@ int nos_image_patch_planes_packed(const void* img, const void* lo, const void* h
   else
     hipLaunchKernelGGL(image_patch_planes_packed3, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, n);
   return check("image_patch_planes_packed");
+}
+
+int nos_image_yuv_max_footprint() { return YUV_FMAX_W; }
+
+// The same from any YUV surface NosYuvSrc (image_yuv.h) describes: planar, semi-planar or packed 4:2:2; 4:2:0,
+// 4:2:2 or 4:4:4; 8-bit samples or 10 / 12-bit codes in little-endian 16-bit words (in the high or the low bits;
+// the other bits are ignored, not required to be zero). Nothing is launched unless every check passes.
+int nos_image_patch_planes_yuv(const NosYuvSrc* src, void* planes, float* pixels, const int* yidx, const float* ywt,
+                               const int* xidx, const float* xwt, int ytab, int xtab, int taps, int max_fh, int max_fw,
+                               const float* a, const float* b, int B, int h, int w, int H, int W, int p, int gh, int gw,
+                               int wgs, void* stream) {
+  if (!src) return fail("image_patch_planes: null operand");
+  if (src->size != int(sizeof(NosYuvSrc)))
+    return fail("image_patch_planes_yuv: descriptor size mismatch (NosYuvSrc of another build)");
+  const NosYuvSrc& s = *src;
+  ImgArgs k{};
+  int grid = 0;
+  if (const int rc = image_args(k, grid, planes, pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a, b,
+                                B, h, w, H, W, p, gh, gw, wgs))
+    return rc;
+  if (max_fw > YUV_FMAX_W) return fail("image_patch_planes_yuv: a patch's source footprint exceeds 69 columns");
+  // the known combinations
+  const bool packed = s.layout == YUV_PACKED;
+  if (s.layout != YUV_PLANAR && s.layout != YUV_SEMI && !packed)
+    return fail("image_patch_planes_yuv: unknown layout (0 planar, 1 semi-planar, 2 packed 4:2:2)");
+  if (!((s.hsub == 1 && s.vsub == 1) || (s.hsub == 1 && s.vsub == 0) || (s.hsub == 0 && s.vsub == 0)))
+    return fail("image_patch_planes_yuv: unknown subsampling (hsub, vsub): (1, 1), (1, 0) or (0, 0)");
+  if (packed && (s.hsub != 1 || s.vsub != 0 || s.sample_bytes != 1))
+    return fail("image_patch_planes_yuv: packed sources are 4:2:2 with 8-bit samples");
+  if (s.sample_bytes == 1 ? (s.depth != 8 || s.shift != 0)
+                          : (s.sample_bytes != 2 || (s.depth != 10 && s.depth != 12) ||
+                             (s.shift != 0 && s.shift != 16 - s.depth)))
+    return fail("image_patch_planes_yuv: unknown sample format (1 byte: depth 8, shift 0; 2 bytes: depth 10 or 12, "
+                "shift 0 or 16 - depth)");
+  if (s.order < 0 || s.order > (packed ? 2 : s.layout == YUV_SEMI ? 1 : 0))
+    return fail("image_patch_planes_yuv: unknown order (semi-planar 0 UV / 1 VU; packed 0 YUYV / 1 UYVY / 2 YVYU)");
+  // rows and row bytes of every plane
+  const long long SB = s.sample_bytes, cw = (w + (1LL << s.hsub) - 1) >> s.hsub, ch = (h + (1LL << s.vsub) - 1) >> s.vsub;
+  const int np = packed ? 1 : s.layout == YUV_SEMI ? 2 : 3;
+  const long long rows[3] = {h, ch, ch};
+  const long long rowbytes[3] = {packed ? 4 * ((w + 1LL) / 2) : w * SB, s.layout == YUV_SEMI ? 2 * cw * SB : cw * SB,
+                                 cw * SB};
+  YuvArgs n{};
+  for (int i = 0; i < np; ++i) {
+    const NosYuvPlane& q = s.plane[i];
+    if (!q.p) return fail("image_patch_planes: null operand");
+    if (q.pitch < rowbytes[i]) return fail("image_patch_planes_yuv: a plane's pitch is smaller than its row's bytes");
+    if (!stride_range(q.pitch, q.bstride)) return fail("image_patch_planes_yuv: pitch or batch stride out of range");
+    if (SB == 2 && ((reinterpret_cast<uintptr_t>(q.p) | uintptr_t(q.pitch) | uintptr_t(q.bstride)) & 1))
+      return fail("image_patch_planes_yuv: 16-bit planes lie at an even address with an even pitch and batch stride");
+    if (!inside(B, q.p, q.lo, q.hi, q.bstride, rows[i], q.pitch, rowbytes[i]))
+      return fail("image_patch_planes_yuv: a plane does not lie inside its storage bounds");
+    n.pl[i] = plane_arg(q.p, q.lo, q.hi, q.pitch, q.bstride);
+  }
+  for (int i = 0; i < 12; ++i) {
+    if (i < 9 ? std::abs(s.tab[i]) >= (1 << 23) : (s.tab[i] < 0 || s.tab[i] >= (1 << s.depth)))
+      return fail("image_patch_planes_yuv: colour table: coefficients below 2^23 in size, offsets below 2^depth");
+    n.tab[i] = s.tab[i];
+  }
+  n.vsub = s.vsub, n.depth = s.depth, n.shift = s.shift, n.mask = (1 << s.depth) - 1, n.order = s.order;
+  void (*kern)(ImgArgs, YuvArgs) = nullptr;
+  switch (s.layout * 4 + s.hsub * 2 + (s.sample_bytes - 1)) {
+    case 0: kern = image_patch_planes_yuv<Yuv<YUV_PLANAR, 0, 1>>; break;
+    case 1: kern = image_patch_planes_yuv<Yuv<YUV_PLANAR, 0, 2>>; break;
+    case 2: kern = image_patch_planes_yuv<Yuv<YUV_PLANAR, 1, 1>>; break;
+    case 3: kern = image_patch_planes_yuv<Yuv<YUV_PLANAR, 1, 2>>; break;
+    case 4: kern = image_patch_planes_yuv<Yuv<YUV_SEMI, 0, 1>>; break;
+    case 5: kern = image_patch_planes_yuv<Yuv<YUV_SEMI, 0, 2>>; break;
+    case 6: kern = image_patch_planes_yuv<Yuv<YUV_SEMI, 1, 1>>; break;
+    case 7: kern = image_patch_planes_yuv<Yuv<YUV_SEMI, 1, 2>>; break;
+    default: kern = image_patch_planes_yuv<Yuv<YUV_PACKED, 1, 1>>; break;
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, n);
+  return check("image_patch_planes_yuv");
 }
 
 // logits [B][M][C] fp32, boxes [B][M][4] fp32, target [B][2] fp32 (height, width), all on the device ->

@@ -1,0 +1,43 @@
+// Source descriptor of the general YUV entry of the image kernel (image.hip): one struct, one entry point.
+// A new source parameter is a new field here, in walkai_nos_amd/ops/image.py's NosYuvSrc and in the launcher.
+#pragma once
+#include <stddef.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+// One plane: p its first byte, [lo, hi) the storage it lives in (no byte outside is read), pitch and
+// bstride the bytes between rows and between batch elements (bstride possibly negative).
+typedef struct NosYuvPlane {
+  const void* p;
+  const void* lo;
+  const void* hi;
+  long long pitch;
+  long long bstride;
+} NosYuvPlane;
+
+typedef struct NosYuvSrc {
+  int size;          // sizeof(NosYuvSrc): checked first, a mismatch is an error
+  int layout;        // 0 planar (y, u, v) | 1 semi-planar (y, interleaved chroma pairs) | 2 packed 4:2:2 (one plane)
+  int hsub, vsub;    // log2 chroma subsampling: (1, 1) 4:2:0, (1, 0) 4:2:2, (0, 0) 4:4:4; packed is (1, 0)
+  int sample_bytes;  // 1 | 2 (little-endian); packed is 1
+  int depth, shift;  // code = (word >> shift) & ((1 << depth) - 1); depth 8 (shift 0) when sample_bytes is 1,
+                     // else 10 or 12 with shift 0 (value in the low bits) or 16 - depth (in the high bits)
+  int order;         // semi-planar: 0 UV / 1 VU; packed: 0 YUYV / 1 UYVY / 2 YVYU; planar: 0
+  NosYuvPlane plane[3];  // planar y, u, v; semi-planar y, pairs; packed the one plane (the rest ignored)
+  int tab[12];       // ops/image.py's yuv_table: the matrix times 2^(8 + depth) by rows (R, G, B) x (Y, U, V),
+                     // each below 2^23 in size, then the offsets taken from Y, U and V (codes of that depth)
+} NosYuvSrc;
+
+// src, then the arguments of nos_image_patch_planes_u8 from `planes` on.
+int nos_image_patch_planes_yuv(const NosYuvSrc* src, void* planes, float* pixels, const int* yidx, const float* ywt,
+                               const int* xidx, const float* xwt, int ytab, int xtab, int taps, int max_fh, int max_fw,
+                               const float* a, const float* b, int B, int h, int w, int H, int W, int p, int gh, int gw,
+                               int wgs, void* stream);
+
+int nos_image_yuv_max_footprint(void);
+
+#ifdef __cplusplus
+}
+#endif

@@ -17,7 +17,9 @@ surface at a pitch of the width rounded up to 256, 480x640 and 1080x1920) time t
 planes, alternating: (a) the fused NV12 launch, (b) the RGB kernel alone on the converted frame, (c)
 ``nv12_to_rgb`` followed by the RGB kernel, which is what a pod without the fused path runs. The other
 layouts of the same picture (``nv21_*``, ``i420_*``, ``bgr_*``, ``rgba_*``, ``bgra_*``, and ``rgbcrop_*``: RGB
-rows at a padded pitch, read in place against ``.contiguous()`` first) are timed as the same triple.
+rows at a padded pitch, read in place against ``.contiguous()`` first) are timed as the same triple, and so are
+the surfaces of ``models/workload/surfaces.py``, one name per kernel instantiation (``i422_*``, ``i444_*``,
+``nv16_*``, ``nv24_*``, ``yuy2_*``, ``p010_*``, ``i010_*``, ``p210_*``, ``i410_*``, ``i012_*``).
 """
 from __future__ import annotations
 
@@ -278,6 +280,15 @@ def image_bench(a) -> int:
                                "rgba": Packed(torch.cat((rgb, alpha), dim=-1), "rgba"),
                                "bgra": Packed(padded(torch.cat((rgb[..., [2, 1, 0]], alpha), dim=-1)), "bgra"),
                                "rgbcrop": Packed(padded(rgb), "rgb")}
+        # 4:2:2, 4:4:4, packed 4:2:2 and 10 / 12-bit surfaces: one name per kernel instantiation, each a random
+        # surface of its own at the same 256-byte row pitch rule
+        from walkai_nos_amd.models.workload import surfaces
+        for fmt in ("i422", "i444", "nv16", "nv24", "yuy2", "p010", "i010", "p210", "i410", "i012"):
+            kind, _, depth = surfaces.FORMATS[fmt][:3]
+            row = 4 * ((w + 1) // 2) if kind == "packed" else w * (1 if depth == 8 else 2)
+            sp = -(-row // 256) * 256
+            buf = torch.randint(0, 256, (3 * sp * h,), generator=g, dtype=torch.uint8).cuda()
+            layouts[f"{h}x{w}"][fmt] = surfaces.from_buffer(fmt, buf, h, w, sp)
     results = []
     for prof, label in (("spx_nps1", "spx"), ("cpx_nps1", "cpx")):
         if label not in a.slices.split(","):

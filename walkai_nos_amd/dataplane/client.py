@@ -21,6 +21,9 @@ rows, ``--pitch`` bytes apart), converted inside the same preprocess launch. ``n
 ``i420`` / ``yv12`` a software decoder's planar surface (Y rows at ``--pitch``, then the two chroma planes at
 half of it); ``bgr``, ``rgba`` and ``bgra`` packed pixels as OpenCV or a compositor hands them out. ``--pitch``
 applies to every format (for the packed ones and ``rgb`` it is the bytes between rows of a padded buffer).
+The names of ``models/workload/surfaces.py`` — ``i422``, ``nv16``, ``i444``, ``nv24``, ``yuy2`` / ``uyvy``, a 10-bit
+decoder's ``p010`` / ``p210`` / ``p410``, ``i010`` (``yuv420p10le``) and their 12-bit forms — go the same way, and
+``--matrix bt601|bt709|bt2020`` and ``--full-range`` say how any YUV format's codes are read.
 """
 from __future__ import annotations
 
@@ -62,6 +65,11 @@ def _shim() -> Dict[str, Any]:
         return {"loaded": False}
 
 
+#: the names of models/workload/surfaces.py's FORMATS (spelled out: this module imports torch only after its arguments)
+SURFACES = ("i422", "yv16", "i444", "yv24", "nv16", "nv61", "nv24", "nv42", "yuy2", "uyvy", "yvyu",
+            "p010", "p012", "p210", "p410", "i010", "i012", "i210", "i410")
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser("nos pod client")
     ap.add_argument("--seconds", type=float, default=10.0)
@@ -75,11 +83,16 @@ def main(argv=None) -> int:
     ap.add_argument("--image-hw", default="480,640", help="--end-to-end: the synthetic source image's height,width")
     ap.add_argument("--size", default="800,1333", help="--end-to-end: the processor's shortest,longest edge")
     ap.add_argument("--threshold", type=float, default=0.5, help="--end-to-end: detection score threshold")
-    ap.add_argument("--pixel-format", choices=("rgb", "bgr", "rgba", "bgra", "nv12", "nv21", "i420", "yv12"),
-                    default="rgb", help="--end-to-end: packed pixels, or a decoder's 4:2:0 surface (even height)")
+    ap.add_argument("--pixel-format", choices=("rgb", "bgr", "rgba", "bgra", "nv12", "nv21", "i420", "yv12")
+                    + tuple(SURFACES), default="rgb",
+                    help="--end-to-end: packed pixels, a decoder's 4:2:0 surface (even height), or a 4:2:2 / 4:4:4 / "
+                         "packed 4:2:2 / 10- or 12-bit surface (models/workload/surfaces.py)")
     ap.add_argument("--pitch", type=int, default=0,
-                    help="--end-to-end: bytes between rows of the surface (default: the width rounded up to 256 for "
-                         "the 4:2:0 formats, rows side by side for the packed ones)")
+                    help="--end-to-end: bytes between rows of the surface (default: a luma row's bytes rounded up to "
+                         "256 for the YUV formats, rows side by side for the packed RGB ones)")
+    ap.add_argument("--matrix", choices=("bt601", "bt709", "bt2020"), default="bt601",
+                    help="--end-to-end: the YUV formats' colour matrix (bt2020 with the surfaces.py formats only)")
+    ap.add_argument("--full-range", action="store_true", help="--end-to-end: full-range YUV codes (default: limited)")
     args = ap.parse_args(argv)
     t_boot = time.perf_counter()
     import torch
@@ -98,13 +111,26 @@ def main(argv=None) -> int:
         model.processor = YolosProcessor(shortest, longest, patch=model.c.patch_size)
         gen = torch.Generator().manual_seed(seed)
         fmt = args.pixel_format
-        if fmt in ("nv12", "nv21", "i420", "yv12"):
+        if fmt in SURFACES:
+            from ..models.workload import surfaces
+            kind, sub, depth = surfaces.FORMATS[fmt][:3]
+            row = 4 * ((iw + 1) // 2) if kind == "packed" else iw * (1 if depth == 8 else 2)
+            pitch = args.pitch or -(-row // 256) * 256
+            if pitch < row:
+                ap.error(f"--pitch {pitch} is smaller than a row of {iw} {fmt} pixels ({row} bytes)")
+            # luma rows, then at most twice as many bytes of chroma (4:4:4)
+            buf = torch.randint(0, 256, (3 * pitch * ih,), generator=gen, dtype=torch.uint8).to(dev)
+            img = surfaces.from_buffer(fmt, buf, ih, iw, pitch, matrix=args.matrix, full_range=args.full_range)
+        elif fmt in ("nv12", "nv21", "i420", "yv12"):
+            if args.matrix == "bt2020":
+                ap.error(f"--matrix bt2020 is not offered for {fmt}")
             pitch = args.pitch or -(-iw // 256) * 256
             buf = torch.randint(0, 256, (pitch * (ih + ih // 2),), generator=gen, dtype=torch.uint8).to(dev)
             if fmt in ("nv12", "nv21"):
-                img = Nv12.from_buffer(buf, ih, iw, pitch, vu=fmt == "nv21")
+                img = Nv12.from_buffer(buf, ih, iw, pitch, args.matrix, args.full_range, vu=fmt == "nv21")
             else:
-                img = Yuv420p.from_buffer(buf, ih, iw, pitch, order=fmt)
+                img = Yuv420p.from_buffer(buf, ih, iw, pitch, order=fmt, matrix=args.matrix,
+                                          full_range=args.full_range)
         elif fmt == "rgb" and not args.pitch:
             img = torch.randint(0, 256, (ih, iw, 3), generator=gen, dtype=torch.uint8).to(dev)
         else:

@@ -19,7 +19,9 @@ with ``vu=True``; a software decoder's planar I420 / YV12 surface is :class:`Yuv
 compositor's RGBA / BGRA, and any of them (or RGB) as a crop or with padded rows is :class:`Packed` — a
 non-contiguous RGB view may also be passed as it is. None of them is copied or converted first: every
 layout has its staging loop in the one kernel, and equals the RGB path on the converted frame bit for bit.
-All of them are a :class:`Frame`, which is all the processor and the model know about them.
+All of them are a :class:`Frame`, which is all the processor and the model know about them. Further frames —
+4:2:2 and 4:4:4, packed YUY2 / UYVY, 10 / 12-bit P010 / ``yuv420p10le`` and kin, BT.2020 — live in
+:mod:`.surfaces`; nothing here names them.
 """
 from __future__ import annotations
 

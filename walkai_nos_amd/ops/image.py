@@ -32,6 +32,13 @@ is rounded to uint8 between the two passes, so pixels differ from it by less tha
 * :func:`packed_patch_planes` — BGR, RGBA and BGRA, and RGB at any row pitch, batch stride and alignment: a
   crop ``frame[:, y0:y1, x0:x1]`` or a padded capture buffer is read in place. :func:`image_patch_planes`
   sends a non-contiguous RGB view there instead of copying it.
+* :func:`yuv_to_rgb` / :func:`yuv_planar_patch_planes`, :func:`yuv_semiplanar_patch_planes`,
+  :func:`yuyv_patch_planes` — the rest of the YUV front end behind one launch descriptor (:class:`NosYuvSrc`):
+  4:2:2 and 4:4:4 beside 4:2:0, packed 4:2:2 (YUY2 / UYVY / YVYU), and 10 / 12-bit codes in 16-bit words (P010's
+  high bits or ``yuv420p10le``'s low bits; the other bits are ignored), with BT.2020 (non-constant luminance)
+  beside the two older matrices (:func:`yuv_table`). Chroma stays nearest; PQ / HLG code values are converted as
+  if SDR (no transfer function, no tone mapping); 16-bit-deep samples, Y210 / Y410 / AYUV and big-endian words
+  are not offered.
 
 Every layout is bit-equal to :func:`image_patch_planes` of the converted or re-ordered contiguous RGB frame,
 which is also what runs on the CPU, with the ``torch`` backend and past a layout's footprint limit.
@@ -61,6 +68,8 @@ NV12_MAX_FOOTPRINT = 69
 #: the same for planar 4:2:0 and for packed pixels read through pitches (all of them stage 4-column groups)
 YUV420P_MAX_FOOTPRINT = 69
 PACKED_MAX_FOOTPRINT = 69
+#: and for the general YUV entry (4:2:2, 4:4:4, packed 4:2:2, 10 / 12-bit samples)
+YUV_MAX_FOOTPRINT = 69
 #: packed channel orders: bytes per pixel and the index of red, green and blue in a pixel
 PACKED_ORDERS = {"rgb": (3, (0, 1, 2)), "bgr": (3, (2, 1, 0)), "rgba": (4, (0, 1, 2)), "bgra": (4, (2, 1, 0))}
 #: detections kernel limits: rows per image, classes with "no object"
@@ -92,12 +101,15 @@ def _L() -> ctypes.CDLL:
                 L.nos_image_patch_planes_u8.argtypes[1:]
             L.nos_image_patch_planes_packed.argtypes = [vp, vp, vp, i64, i64, ctypes.c_char_p] + \
                 L.nos_image_patch_planes_u8.argtypes[1:]
+            L.nos_image_patch_planes_yuv.argtypes = [ctypes.POINTER(NosYuvSrc)] + \
+                L.nos_image_patch_planes_u8.argtypes[1:]
             L.nos_detections_f32.argtypes = [vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, vp, vp]
             L.nos_image_last_error.restype = ctypes.c_char_p
             if (L.nos_image_taps(), L.nos_image_max_footprint(), L.nos_image_max_patch(),
                     L.nos_image_nv12_max_footprint(), L.nos_image_yuv420p_max_footprint(),
-                    L.nos_image_packed_max_footprint()) != (TAPS, MAX_FOOTPRINT, MAX_PATCH, NV12_MAX_FOOTPRINT,
-                                                            YUV420P_MAX_FOOTPRINT, PACKED_MAX_FOOTPRINT):
+                    L.nos_image_packed_max_footprint(), L.nos_image_yuv_max_footprint()) != \
+                    (TAPS, MAX_FOOTPRINT, MAX_PATCH, NV12_MAX_FOOTPRINT, YUV420P_MAX_FOOTPRINT, PACKED_MAX_FOOTPRINT,
+                     YUV_MAX_FOOTPRINT):
                 raise NativeUnavailable(f"{LIB} was built with other limits than ops/image.py expects")
             _lib = L
         return _lib
@@ -527,6 +539,282 @@ def packed_patch_planes(img: torch.Tensor, order: str, out_hw: Tuple[int, int], 
                                             *_tail_args(tabs, planes, pixels, mean, std, B, h, w, H, W, patch, gh, gw))
     _check(rc, "packed_patch_planes")
     return planes, pixels
+
+
+# ---- 4:2:2, 4:4:4, packed 4:2:2 and 10 / 12-bit samples -------------------------------------------
+#: :data:`NV12_MATRICES` and BT.2020 in its non-constant-luminance form (what 10-bit content usually carries)
+YUV_MATRICES = {**NV12_MATRICES, "bt2020": (0.2627, 0.0593)}
+YUV_DEPTHS = (8, 10, 12)
+#: log2 of the chroma subsampling ``(horizontal, vertical)``
+YUV_SUBSAMPLING = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
+#: packed 4:2:2: the byte of the first luma, of U and of V in a four-byte macropixel (the second luma two on)
+YUYV_ORDERS = {"yuyv": (0, 1, 3), "uyvy": (1, 0, 2), "yvyu": (0, 3, 1)}
+
+
+def _yuv_check(matrix: str, depth: int) -> None:
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"yuv: matrix {matrix!r} is none of {sorted(YUV_MATRICES)}")
+    if depth not in YUV_DEPTHS:
+        raise ValueError(f"yuv: depth {depth!r} is none of {YUV_DEPTHS}")
+
+
+def yuv_real_matrix(matrix: str = "bt601", full_range: bool = False, depth: int = 8) \
+        -> Tuple[np.ndarray, Tuple[int, int, int]]:
+    """:func:`nv12_real_matrix` for codes of ``depth`` bits, to 8-bit RGB: ``(M [3, 3], offsets)`` with ``rgb = M @
+    ((Y, U, V) - offsets)``. Limited range takes ``16 * 2^(depth-8)`` from Y and scales Y by ``255 / (219 *
+    2^(depth-8))`` and chroma by ``255 / (224 * 2^(depth-8))``; full range scales both by ``255 / (2^depth - 1)``;
+    both take ``2^(depth-1)`` from chroma."""
+    _yuv_check(matrix, depth)
+    kr, kb = YUV_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    up = float(1 << (depth - 8))
+    sy, sc = (255.0 / ((1 << depth) - 1),) * 2 if full_range else (255.0 / (219.0 * up), 255.0 / (224.0 * up))
+    m = np.array([[sy, 0.0, sc * 2.0 * (1.0 - kr)],
+                  [sy, -sc * 2.0 * kb * (1.0 - kb) / kg, -sc * 2.0 * kr * (1.0 - kr) / kg],
+                  [sy, sc * 2.0 * (1.0 - kb), 0.0]], dtype=np.float64)
+    return m, (0 if full_range else 16 << (depth - 8), 1 << (depth - 1), 1 << (depth - 1))
+
+
+def yuv_table(matrix: str = "bt601", full_range: bool = False, depth: int = 8) -> Tuple[int, ...]:
+    """The 12 integers :func:`yuv_to_rgb` and the kernel compute with: ``rint(M * 2^(8 + depth))`` of
+    :func:`yuv_real_matrix` by rows (R, G, B) x (Y, U, V), then the three offsets. Channel ``c`` is ``clip((t[3c]
+    (Y - t[9]) + t[3c+1] (U - t[10]) + t[3c+2] (V - t[11]) + 2^(7+depth)) >> (8+depth), 0, 255)``. At depth 8 it
+    is :func:`nv12_table`; in limited range the coefficients are the same integers at every depth. Every
+    coefficient is at most 140 363 (24-bit multiplies) and every sum below 5.81e8 in size (int32)."""
+    m, off = yuv_real_matrix(matrix, full_range, depth)
+    return tuple(int(v) for v in np.rint(m * float(1 << (8 + depth))).astype(np.int64).reshape(-1)) + tuple(off)
+
+
+def _sample_depth(t: torch.Tensor, depth: int, who: str) -> None:
+    if depth not in YUV_DEPTHS:
+        raise ValueError(f"{who}: depth {depth!r} is none of {YUV_DEPTHS}")
+    want = (torch.uint8,) if depth == 8 else (torch.uint16, torch.int16)
+    if not isinstance(t, torch.Tensor) or t.dtype not in want:
+        raise ValueError(f"{who}: depth {depth} takes " + ("uint8 planes" if depth == 8 else
+                                                            "uint16 (or int16) planes of little-endian words"))
+
+
+def yuv_codes(plane: torch.Tensor, depth: int = 8, msb: bool = False) -> torch.Tensor:
+    """A plane's sample codes as int32. uint8 (depth 8): its values. A 16-bit plane (``torch.uint16``, or
+    ``torch.int16`` read as the same bits) of depth 10 or 12: ``(word >> (16 - depth)) & (2^depth - 1)`` with
+    ``msb`` (P010's layout), ``word & (2^depth - 1)`` without (``yuv420p10le``'s). The other bits are ignored."""
+    _sample_depth(plane, depth, "yuv_codes")
+    if depth == 8:
+        return plane.to(torch.int32)
+    # (no shifts on uint16, and few other ops on the GPU: the same bits as int16, widened, the sign bits cut)
+    word = (plane if plane.dtype == torch.int16 else plane.view(torch.int16)).to(torch.int32) & 0xffff
+    return ((word >> (16 - depth)) if msb else word) & ((1 << depth) - 1)
+
+
+def yuv_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, subsampling: str = "420", depth: int = 8,
+               any_strides: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The three planes of a planar frame as ``[B, h, w]`` and two ``[B, ch, cw]`` views, checked: ``subsampling``
+    ``"420"`` has chroma ``[(h+1)//2, (w+1)//2]``, ``"422"`` ``[h, (w+1)//2]``, ``"444"`` ``[h, w]``; the dtype
+    goes with ``depth`` (:func:`yuv_codes`); one device; rows possibly pitched but contiguous inside
+    (``any_strides``: not even that, for the torch definition)."""
+    if subsampling not in YUV_SUBSAMPLING:
+        raise ValueError(f"yuv: subsampling {subsampling!r} is none of {sorted(YUV_SUBSAMPLING)}")
+    for t in (y, u, v):
+        _sample_depth(t, depth, "yuv")
+    if u.dtype != y.dtype or v.dtype != y.dtype:
+        raise ValueError("yuv: the three planes have one dtype")
+    if y.dim() == 2 and u.dim() == 2 and v.dim() == 2:
+        y, u, v = y[None], u[None], v[None]
+    if y.dim() != 3 or u.dim() != 3 or v.dim() != 3 or 0 in y.shape:
+        raise ValueError("yuv: Y is [B, h, w] (or [h, w]) and U, V [B, ch, cw] (or without B)")
+    hs, vs = YUV_SUBSAMPLING[subsampling]
+    B, h, w = y.shape
+    want = (B, (h + (1 << vs) - 1) >> vs, (w + (1 << hs) - 1) >> hs)
+    if tuple(u.shape) != want or tuple(v.shape) != want:
+        raise ValueError(f"yuv: a {h}x{w} Y plane takes 4:{subsampling[1:2]}:{subsampling[2:]} U and V planes of "
+                         f"shape {want}, not {tuple(u.shape)} and {tuple(v.shape)}")
+    if y.device != u.device or y.device != v.device:
+        raise ValueError(f"yuv: all planes on one device, not {y.device}, {u.device} and {v.device}")
+    if not any_strides and any(t.shape[2] > 1 and t.stride(2) != 1 for t in (y, u, v)):
+        raise ValueError("yuv: rows may be pitched, but the samples of a row are contiguous")
+    return y, u, v
+
+
+def yuv_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, subsampling: str = "420", depth: int = 8,
+               msb: bool = False, matrix: str = "bt601", full_range: bool = False) -> torch.Tensor:
+    """A planar frame of any of the three chroma geometries and sample depths as interleaved RGB, uint8 ``[B, h,
+    w, 3]``: the definition of the conversion (and what runs on the CPU, with the ``torch`` backend and past the
+    kernel's limits). Nearest chroma — luma ``(r, c)`` takes chroma ``(r >> vs, c >> hs)`` — and exact int32
+    arithmetic on :func:`yuv_table`. For ``"420"`` at depth 8 it equals :func:`yuv420_to_rgb`."""
+    y, u, v = yuv_planes(y, u, v, subsampling, depth, any_strides=True)
+    t = yuv_table(matrix, full_range, depth)
+    hs, vs = YUV_SUBSAMPLING[subsampling]
+    h, w = y.shape[1:]
+    rows, cols = torch.arange(h, device=y.device) >> vs, torch.arange(w, device=y.device) >> hs
+    # the largest sum is below 5.81e8 at depth 12: int32 cannot overflow
+    yy = yuv_codes(y, depth, msb) - t[9]
+    uu = yuv_codes(u, depth, msb)[:, rows][:, :, cols] - t[10]
+    vv = yuv_codes(v, depth, msb)[:, rows][:, :, cols] - t[11]
+    out = [(t[3 * k] * yy + t[3 * k + 1] * uu + t[3 * k + 2] * vv + (1 << (7 + depth))) >> (8 + depth)
+           for k in range(3)]
+    return torch.stack(out, dim=-1).clamp_(0, 255).to(torch.uint8)
+
+
+def yuv_semiplanar_planes(y: torch.Tensor, uv: torch.Tensor, subsampling: str = "420", depth: int = 8) \
+        -> Tuple[torch.Tensor, torch.Tensor]:
+    """The two planes of a semi-planar frame (NV16, NV24, P010, P210 ...) as ``[B, h, w]`` and ``[B, ch, cw, 2]``
+    views, checked as :func:`yuv_planes` checks; a chroma pair's two samples are adjacent."""
+    if not isinstance(uv, torch.Tensor) or uv.dim() not in (3, 4) or uv.shape[-1] != 2:
+        raise ValueError("yuv: the chroma plane of a semi-planar frame is [B, ch, cw, 2] (or without B)")
+    y, u, v = yuv_planes(y, uv[..., 0], uv[..., 1], subsampling, depth, any_strides=True)
+    uv = uv if uv.dim() == 4 else uv[None]
+    if (y.shape[2] > 1 and y.stride(2) != 1) or uv.stride(3) != 1 or (uv.shape[2] > 1 and uv.stride(2) != 2):
+        raise ValueError("yuv: rows may be pitched, but the samples of a row are contiguous (chroma interleaved)")
+    return y, uv
+
+
+def yuyv_planes(data: torch.Tensor, width: int, order: str = "yuyv") \
+        -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The luma and the two chroma planes of packed 4:2:2 as strided views ``[B, h, width]`` and two ``[B, h,
+    (width+1)//2]``. ``data``: uint8 ``[B, h, rowbytes]`` (or ``[h, rowbytes]``) with ``rowbytes >= 4 *
+    ceil(width / 2)``, contiguous inside a row; a macropixel is four bytes, ``yuyv`` (YUY2: Y0 U Y1 V), ``uyvy``
+    (U Y0 V Y1) or ``yvyu``. With an odd ``width`` the last macropixel's second luma is padding, never shown."""
+    if order not in YUYV_ORDERS:
+        raise ValueError(f"yuyv: order {order!r} is none of {sorted(YUYV_ORDERS)}")
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() not in (2, 3) or 0 in data.shape:
+        raise ValueError("yuyv: a uint8 [B, h, rowbytes] (or [h, rowbytes]) tensor")
+    data = data if data.dim() == 3 else data[None]
+    width = int(width)
+    cw = (width + 1) // 2
+    if width <= 0 or data.shape[2] < 4 * cw:
+        raise ValueError(f"yuyv: a row of {width} pixels takes {4 * cw} bytes, the rows have {data.shape[2]}")
+    if data.stride(2) != 1:
+        raise ValueError("yuyv: rows may be pitched, but the bytes of a row are contiguous")
+    yo, uo, vo = YUYV_ORDERS[order]
+    return data[..., yo::2][..., :width], data[..., uo::4][..., :cw], data[..., vo::4][..., :cw]
+
+
+def yuyv_to_rgb(data: torch.Tensor, width: int, order: str = "yuyv", matrix: str = "bt601",
+                full_range: bool = False) -> torch.Tensor:
+    """Packed 4:2:2 as interleaved RGB, uint8 ``[B, h, width, 3]``: :func:`yuv_to_rgb` of :func:`yuyv_planes`'
+    three views as ``"422"``."""
+    return yuv_to_rgb(*yuyv_planes(data, width, order), "422", 8, False, matrix, full_range)
+
+
+def yuv_semiplanar_to_rgb(y: torch.Tensor, uv: torch.Tensor, subsampling: str = "420", depth: int = 8,
+                          msb: bool = False, matrix: str = "bt601", full_range: bool = False,
+                          vu: bool = False) -> torch.Tensor:
+    """A semi-planar frame as interleaved RGB: :func:`yuv_to_rgb` of its de-interleaved planes (``vu``: the pairs
+    are (V, U))."""
+    y, uv = yuv_semiplanar_planes(y, uv, subsampling, depth)
+    return yuv_to_rgb(y, uv[..., 1 if vu else 0], uv[..., 0 if vu else 1], subsampling, depth, msb, matrix, full_range)
+
+
+class NosYuvPlane(ctypes.Structure):
+    """One plane of :class:`NosYuvSrc` (``csrc/image_yuv.h``, field for field)."""
+    _fields_ = [("p", ctypes.c_void_p), ("lo", ctypes.c_void_p), ("hi", ctypes.c_void_p),
+                ("pitch", ctypes.c_longlong), ("bstride", ctypes.c_longlong)]
+
+
+class NosYuvSrc(ctypes.Structure):
+    """The general YUV entry's source descriptor (``csrc/image_yuv.h``, field for field)."""
+    _fields_ = [("size", ctypes.c_int), ("layout", ctypes.c_int), ("hsub", ctypes.c_int), ("vsub", ctypes.c_int),
+                ("sample_bytes", ctypes.c_int), ("depth", ctypes.c_int), ("shift", ctypes.c_int),
+                ("order", ctypes.c_int), ("plane", NosYuvPlane * 3), ("tab", ctypes.c_int * 12)]
+
+
+YUV_PLANAR, YUV_SEMIPLANAR, YUV_PACKED = 0, 1, 2
+
+
+def yuv_src(layout: int, planes: Sequence[torch.Tensor], subsampling: str, depth: int, msb: bool, order: int,
+            table: Sequence[int]) -> NosYuvSrc:
+    """The descriptor of ``planes`` — views ``[B, rows, row elements]`` of uint8 or 16-bit samples, each read by
+    its own strides inside its own storage."""
+    hs, vs = YUV_SUBSAMPLING[subsampling]
+    src = NosYuvSrc(size=ctypes.sizeof(NosYuvSrc), layout=layout, hsub=hs, vsub=vs, sample_bytes=1 if depth == 8 else 2,
+                    depth=depth, shift=16 - depth if (msb and depth != 8) else 0, order=order)
+    for i, t in enumerate(planes):
+        lo, hi = _storage_bounds(t)
+        es = t.element_size()
+        # (a single row's stride says nothing: its pitch is the row itself)
+        src.plane[i] = NosYuvPlane(t.data_ptr(), lo, hi, (t.stride(1) if t.shape[1] > 1 else t.shape[2]) * es,
+                                   t.stride(0) * es)
+    for i, c in enumerate(table):
+        src.tab[i] = c
+    return src
+
+
+def _yuv_fused(first: torch.Tensor, hw: Tuple[int, int], out_hw: Tuple[int, int], patch: int) -> Optional[tuple]:
+    """The tap tables when the general YUV launch takes this call, else None (the composition runs)."""
+    if not (_use_hip(first) and fusable(hw, out_hw, patch)):
+        return None
+    tabs = _device_tables(hw[0], hw[1], out_hw[0], out_hw[1], patch, first.device)
+    return None if tabs is None or tabs[5] > YUV_MAX_FOOTPRINT else tabs
+
+
+def _yuv_launch(src: NosYuvSrc, tabs: tuple, B: int, h: int, w: int, H: int, W: int, patch: int, mean, std,
+                want_pixels: bool, device: torch.device, what: str):
+    planes, pixels, gh, gw = _outputs(B, H, W, patch, want_pixels, device)
+    rc = _L().nos_image_patch_planes_yuv(ctypes.byref(src),
+                                         *_tail_args(tabs, planes, pixels, mean, std, B, h, w, H, W, patch, gh, gw))
+    _check(rc, what)
+    return planes, pixels
+
+
+def yuv_planar_patch_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, out_hw: Tuple[int, int], patch: int,
+                            mean: Sequence[float], std: Sequence[float], subsampling: str = "420", depth: int = 8,
+                            msb: bool = False, matrix: str = "bt601", full_range: bool = False,
+                            want_pixels: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """:func:`image_patch_planes` of a planar frame (:func:`yuv_planes`' layout: I422, I444, I010, ``yuv422p10le``
+    ...), bit-equal to ``image_patch_planes(yuv_to_rgb(y, u, v, subsampling, depth, msb, matrix, full_range), ...)``
+    — which is what runs on a CPU tensor, with the ``torch`` backend and past the kernel's limits. On the GPU one
+    HIP launch reads the three planes in place, each by its own strides."""
+    y, u, v = yuv_planes(y, u, v, subsampling, depth)
+    table = yuv_table(matrix, full_range, depth)
+    B, h, w = y.shape
+    H, W = int(out_hw[0]), int(out_hw[1])
+    tabs = _yuv_fused(y, (h, w), (H, W), patch)
+    if tabs is None:
+        return image_patch_planes(yuv_to_rgb(y, u, v, subsampling, depth, msb, matrix, full_range), (H, W), patch,
+                                  mean, std, want_pixels)
+    src = yuv_src(YUV_PLANAR, (y, u, v), subsampling, depth, msb, 0, table)
+    return _yuv_launch(src, tabs, B, h, w, H, W, patch, mean, std, want_pixels, y.device, "yuv_planar_patch_planes")
+
+
+def yuv_semiplanar_patch_planes(y: torch.Tensor, uv: torch.Tensor, out_hw: Tuple[int, int], patch: int,
+                                mean: Sequence[float], std: Sequence[float], subsampling: str = "420", depth: int = 8,
+                                msb: bool = False, matrix: str = "bt601", full_range: bool = False,
+                                want_pixels: bool = False, vu: bool = False) \
+        -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The same of a semi-planar frame (:func:`yuv_semiplanar_planes`' layout: NV16 / NV61, NV24 / NV42, P010, P012,
+    P210, P410), bit-equal to ``image_patch_planes(yuv_semiplanar_to_rgb(...), ...)``. ``vu``: the pairs are
+    (V, U)."""
+    y, uv = yuv_semiplanar_planes(y, uv, subsampling, depth)
+    table = yuv_table(matrix, full_range, depth)
+    B, h, w = y.shape
+    H, W = int(out_hw[0]), int(out_hw[1])
+    tabs = _yuv_fused(y, (h, w), (H, W), patch)
+    if tabs is None:
+        rgb = yuv_semiplanar_to_rgb(y, uv, subsampling, depth, msb, matrix, full_range, vu)
+        return image_patch_planes(rgb, (H, W), patch, mean, std, want_pixels)
+    pairs = uv.as_strided((B, uv.shape[1], 2 * uv.shape[2]), (uv.stride(0), uv.stride(1), 1))   # a view, never a copy
+    src = yuv_src(YUV_SEMIPLANAR, (y, pairs), subsampling, depth, msb, int(bool(vu)), table)
+    return _yuv_launch(src, tabs, B, h, w, H, W, patch, mean, std, want_pixels, y.device,
+                       "yuv_semiplanar_patch_planes")
+
+
+def yuyv_patch_planes(data: torch.Tensor, width: int, order: str, out_hw: Tuple[int, int], patch: int,
+                      mean: Sequence[float], std: Sequence[float], matrix: str = "bt601", full_range: bool = False,
+                      want_pixels: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The same of packed 4:2:2 (:func:`yuyv_planes`' layout: YUY2, UYVY, YVYU), bit-equal to
+    ``image_patch_planes(yuyv_to_rgb(data, width, order, matrix, full_range), ...)``. On the GPU one HIP launch
+    reads a group's two macropixels in one read, the rows wherever their pitch puts them."""
+    yv = yuyv_planes(data, width, order)[0]
+    data = data if data.dim() == 3 else data[None]
+    table = yuv_table(matrix, full_range, 8)
+    B, h, w = yv.shape
+    H, W = int(out_hw[0]), int(out_hw[1])
+    tabs = _yuv_fused(data, (h, w), (H, W), patch)
+    if tabs is None:
+        return image_patch_planes(yuyv_to_rgb(data, width, order, matrix, full_range), (H, W), patch, mean, std,
+                                  want_pixels)
+    src = yuv_src(YUV_PACKED, (data,), "422", 8, False, tuple(YUYV_ORDERS).index(order), table)
+    return _yuv_launch(src, tabs, B, h, w, H, W, patch, mean, std, want_pixels, data.device, "yuyv_patch_planes")
 
 
 # ---- detections ---------------------------------------------------------------------------------
