@@ -24,6 +24,9 @@
 //    (image_yuv.h): planar, semi-planar or packed 4:2:2 (YUY2 / UYVY / YVYU); 4:2:0, 4:2:2 or 4:4:4; 8-bit
 //    samples, or 10 / 12-bit codes in 16-bit words (P010's high bits, yuv420p10le's low bits), by a table scaled
 //    to the depth. Again only a staging loop (stage_yuv); the six entries above are as they were.
+//  * image_patch_planes_yuv_bilinear<Yuv<layout, 1, sample bytes, 1>> — the same with bilinear chroma at a siting
+//    (stage_yuv_bilinear): five more instantiations, the subsampled layouts; each thread reads its group's chroma
+//    window straight from the planes (no chroma tile in LDS).
 //  * detections_f32 — softmax over the class logits, the best of the first L classes, the box in
 //    corner format scaled to the original image, and a stable compaction of the rows above the
 //    threshold; one workgroup per image, one wave per row.
@@ -112,13 +115,20 @@ struct YuvArgs {
   int tab[12];
   int vsub, depth, shift, mask, order;
 };
+// What the bilinear instantiations (Yuv<..., 1>) take beside it: the chroma planes' columns and rows, and the
+// weights in quarters of the two taps of an even and of an odd luma position, horizontally (wx) and vertically
+// (wy), by the siting. A type of its own, so that the nearest kernels' arguments are what they were.
+struct YuvBilinearArgs : YuvArgs {
+  int cw, ch;
+  int wx[4], wy[4];
+};
 enum { YUV_PLANAR = 0, YUV_SEMI = 1, YUV_PACKED = 2 };
-template <int LAYOUT_, int HSUB_, int SB_>
+template <int LAYOUT_, int HSUB_, int SB_, int CHROMA_ = 0>
 struct Yuv {
-  static constexpr int LAYOUT = LAYOUT_, HSUB = HSUB_, SB = SB_;
+  static constexpr int LAYOUT = LAYOUT_, HSUB = HSUB_, SB = SB_, CHROMA = CHROMA_;
 };
 struct NoYuv {
-  static constexpr int LAYOUT = -1, HSUB = 0, SB = 1;
+  static constexpr int LAYOUT = -1, HSUB = 0, SB = 1, CHROMA = 0;
 };
 
 // four bytes at q, of which those inside [lo, hi) are read: one aligned dword where q allows it
@@ -255,8 +265,122 @@ __device__ __forceinline__ void stage_yuv(const YuvArgs& n, int b, int sy, int s
   store_rgb4(dst, px);
 }
 
-// SrcArgs: what the layout's staging loop reads besides ImgArgs (Nv12Args, PlanarArgs, PackedArgs, YuvArgs; the
-// contiguous RGB source is ImgArgs::img and takes an empty Nv12Args). Y: Src::YUV's Yuv<...>.
+// The chroma samples of columns 2g - 1 .. 2g + 2 of chroma row cy (inside the plane) of a Yuv<layout, 1, sample
+// bytes> source: what the column group 4g needs of that row for bilinear chroma. One read per plane of the
+// window's bytes inside [lo, hi), wherever they start (at g = 0 one sample before the row); then the columns are
+// clamped by index to 0 .. cw - 1 (columns 2g and, with it, one clamped neighbour always lie inside the window),
+// so whatever a read found outside the row — pitch padding, the neighbouring row, the other plane, zeros past the
+// storage — is dropped here.
+template <class Y>
+__device__ __forceinline__ void chroma_window(const YuvBilinearArgs& n, int b, int sy, int cy, int g, int shift,
+                                              int mask, int (&uu)[4], int (&vv)[4]) {
+  constexpr int SB = Y::SB;
+  if constexpr (Y::LAYOUT == YUV_PACKED) {
+    // macropixels 2g - 1 .. 2g + 2 of the luma row: see stage_yuv for the orders
+    const PlaneArg& s = n.pl[0];
+    const int us = n.order == 0 ? 8 : n.order == 1 ? 0 : 24, vs = n.order == 0 ? 24 : n.order == 1 ? 16 : 8;
+    uint32_t w[4];
+    load_bytes<16>(w, reinterpret_cast<uintptr_t>(s.p) + b * s.bs + sy * s.pitch + (2 * g - 1) * 4, s.lo, s.hi);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) uu[k] = int((w[k] >> us) & 255u), vv[k] = int((w[k] >> vs) & 255u);
+  } else if constexpr (Y::LAYOUT == YUV_PLANAR) {
+    const PlaneArg &pu = n.pl[1], &pv = n.pl[2];
+    uint32_t wu[SB], wv[SB];
+    load_bytes<4 * SB>(wu, reinterpret_cast<uintptr_t>(pu.p) + b * pu.bs + cy * pu.pitch + (2 * g - 1) * SB, pu.lo,
+                       pu.hi);
+    load_bytes<4 * SB>(wv, reinterpret_cast<uintptr_t>(pv.p) + b * pv.bs + cy * pv.pitch + (2 * g - 1) * SB, pv.lo,
+                       pv.hi);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) uu[k] = yuv_sample<SB>(wu, k, shift, mask), vv[k] = yuv_sample<SB>(wv, k, shift, mask);
+  } else {
+    const PlaneArg& pc = n.pl[1];
+    uint32_t wc[2 * SB];
+    load_bytes<8 * SB>(wc, reinterpret_cast<uintptr_t>(pc.p) + b * pc.bs + cy * pc.pitch + (2 * g - 1) * 2 * SB, pc.lo,
+                       pc.hi);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int c0 = yuv_sample<SB>(wc, 2 * k, shift, mask), c1 = yuv_sample<SB>(wc, 2 * k + 1, shift, mask);
+      uu[k] = n.order ? c1 : c0, vv[k] = n.order ? c0 : c1;
+    }
+  }
+  // window sample k is column 2g - 1 + k: inside the row for 1 - (g > 0) <= k <= cw - 2g (which is at least 1)
+  const int kmax = n.cw - 2 * g;
+  uu[0] = g ? uu[0] : uu[1], vv[0] = g ? vv[0] : vv[1];
+  uu[2] = kmax >= 2 ? uu[2] : uu[1], vv[2] = kmax >= 2 ? vv[2] : vv[1];
+  uu[3] = kmax >= 3 ? uu[3] : uu[2], vv[3] = kmax >= 3 ? vv[3] : vv[2];
+}
+
+// 4 x the horizontally upsampled samples under the group's four columns, from a row's window c: columns 4g and
+// 4g + 2 take window samples (0, 1) and (1, 2) by the even weights wx[0..1], columns 4g + 1 and 4g + 3 take
+// (1, 2) and (2, 3) by the odd weights wx[2..3]. 24-bit multiplies, as nv12_channel's.
+__device__ __forceinline__ void chroma_row4(const int* wx, const int (&c)[4], int (&h)[4]) {
+  h[0] = __mul24(wx[0], c[0]) + __mul24(wx[1], c[1]);
+  h[1] = __mul24(wx[2], c[1]) + __mul24(wx[3], c[2]);
+  h[2] = __mul24(wx[0], c[1]) + __mul24(wx[1], c[2]);
+  h[3] = __mul24(wx[2], c[2]) + __mul24(wx[3], c[3]);
+}
+
+// stage_yuv with bilinear chroma (hsub = 1): luma position x has i = x >> 1 and takes two chroma samples with
+// weights in quarters — co-sited (4, 0) of C[i], C[i] at an even x and (2, 2) of C[i], C[i + 1] at an odd one,
+// centred (1, 3) of C[i - 1], C[i] and (3, 1) of C[i], C[i + 1] — on each subsampled axis, indices clamped to the
+// plane; the sample is (sum of wy wx C + 8) >> 4, a code of the source's depth that goes through the table as
+// the nearest one does. n.wx / n.wy hold (w of the lower tap, w of the upper) for even, then for odd positions;
+// the lower tap of an even position is C[i - 1] (weight 0 when co-sited). Reads: the luma as stage_yuv, and the
+// chroma window (chroma_window) of one row (4:2:2) or two (4:2:0).
+template <class Y>
+__device__ __forceinline__ void stage_yuv_bilinear(const YuvBilinearArgs& n, int b, int sy, int sx, uint32_t* dst) {
+  constexpr int SB = Y::SB;
+  static_assert(Y::HSUB == 1, "bilinear chroma is for horizontally subsampled sources");
+  const int depth = SB == 1 ? 8 : n.depth, shift = SB == 1 ? 0 : n.shift, mask = SB == 1 ? 255 : n.mask;
+  const int g = sx >> 2;
+  int yy[4];
+  if constexpr (Y::LAYOUT == YUV_PACKED) {
+    const PlaneArg& s = n.pl[0];
+    const int ys = n.order == 1 ? 8 : 0;
+    uint32_t w[2];
+    load_bytes<8>(w, reinterpret_cast<uintptr_t>(s.p) + b * s.bs + sy * s.pitch + sx * 2, s.lo, s.hi);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      yy[2 * i] = int((w[i] >> ys) & 255u), yy[2 * i + 1] = int((w[i] >> (16 + ys)) & 255u);
+  } else {
+    const PlaneArg& py = n.pl[0];
+    uint32_t wy[SB];
+    load_bytes<4 * SB>(wy, reinterpret_cast<uintptr_t>(py.p) + b * py.bs + sy * py.pitch + sx * SB, py.lo, py.hi);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) yy[k] = yuv_sample<SB>(wy, k, shift, mask);
+  }
+  int su[4], sv[4];  // 16 x the upsampled samples
+  int cu[4], cv[4], hu[4], hv[4];
+  if (n.vsub) {
+    // vertically: an even row takes chroma rows (cy - 1, cy), an odd one (cy, cy + 1), clamped by index
+    const int odd = sy & 1, r0 = (sy >> 1) - 1 + odd;
+    const int w0 = odd ? n.wy[2] : n.wy[0], w1 = odd ? n.wy[3] : n.wy[1];
+    chroma_window<Y>(n, b, sy, min(max(r0, 0), n.ch - 1), g, shift, mask, cu, cv);
+    chroma_row4(n.wx, cu, hu), chroma_row4(n.wx, cv, hv);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) su[k] = __mul24(w0, hu[k]), sv[k] = __mul24(w0, hv[k]);
+    chroma_window<Y>(n, b, sy, min(r0 + 1, n.ch - 1), g, shift, mask, cu, cv);
+    chroma_row4(n.wx, cu, hu), chroma_row4(n.wx, cv, hv);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) su[k] += __mul24(w1, hu[k]), sv[k] += __mul24(w1, hv[k]);
+  } else {
+    chroma_window<Y>(n, b, sy, sy, g, shift, mask, cu, cv);
+    chroma_row4(n.wx, cu, hu), chroma_row4(n.wx, cv, hv);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) su[k] = hu[k] << 2, sv[k] = hv[k] << 2;
+  }
+  uint32_t px[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int y = yy[k] - n.tab[9], u = ((su[k] + 8) >> 4) - n.tab[10], v = ((sv[k] + 8) >> 4) - n.tab[11];
+    px[k] = yuv_channel(n.tab, 0, y, u, v, depth) | yuv_channel(n.tab, 1, y, u, v, depth) << 8 |
+            yuv_channel(n.tab, 2, y, u, v, depth) << 16;
+  }
+  store_rgb4(dst, px);
+}
+
+// SrcArgs: what the layout's staging loop reads besides ImgArgs (Nv12Args, PlanarArgs, PackedArgs, YuvArgs or
+// YuvBilinearArgs; the contiguous RGB source is ImgArgs::img and takes an empty Nv12Args). Y: Src::YUV's Yuv<...>.
 template <Src S, class SrcArgs, class Y = NoYuv>
 __device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const SrcArgs& n) {
   constexpr bool GROUPS = S != Src::RGB;
@@ -319,7 +443,8 @@ __device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const 
           yuv_to_rgb4(n.tab, load4(qy, n.y.lo, n.y.hi),
                       [uu, vv](int i, int v) { return ((v ? vv : uu) >> (8 * i)) & 255; }, dst);
         } else if constexpr (S == Src::YUV) {
-          stage_yuv<Y>(n, b, sy, sx, dst);
+          if constexpr (Y::CHROMA == 1) stage_yuv_bilinear<Y>(n, b, sy, sx, dst);
+          else stage_yuv<Y>(n, b, sy, sx, dst);
         } else {
           // 4 pixels of C = 3 or 4 bytes: their 12 or 16 bytes from the row's aligned dwords, then the three
           // colour bytes of each by their offsets in a pixel (a fourth byte is dropped here)
@@ -428,6 +553,12 @@ __global__ __launch_bounds__(256) void image_patch_planes_packed4(ImgArgs a, Pac
 template <class Y>
 __global__ __launch_bounds__(256) void image_patch_planes_yuv(ImgArgs a, YuvArgs n) {
   image_patch_planes_body<Src::YUV, YuvArgs, Y>(a, n);
+}
+
+// the same with bilinear chroma: one instantiation per subsampled (layout, sample bytes)
+template <class Y>
+__global__ __launch_bounds__(256) void image_patch_planes_yuv_bilinear(ImgArgs a, YuvBilinearArgs n) {
+  image_patch_planes_body<Src::YUV, YuvBilinearArgs, Y>(a, n);
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -777,13 +908,19 @@ int nos_image_patch_planes_yuv(const NosYuvSrc* src, void* planes, float* pixels
                 "shift 0 or 16 - depth)");
   if (s.order < 0 || s.order > (packed ? 2 : s.layout == YUV_SEMI ? 1 : 0))
     return fail("image_patch_planes_yuv: unknown order (semi-planar 0 UV / 1 VU; packed 0 YUYV / 1 UYVY / 2 YVYU)");
+  if (s.chroma != 0 && s.chroma != 1)
+    return fail("image_patch_planes_yuv: unknown chroma reconstruction (0 nearest, 1 bilinear)");
+  if (s.siting < 0 || s.siting > 3)
+    return fail("image_patch_planes_yuv: unknown chroma siting (bit 0 horizontally, bit 1 vertically co-sited)");
+  if (s.chroma == 1 && s.hsub == 0)
+    return fail("image_patch_planes_yuv: bilinear chroma takes a subsampled source (4:4:4 is launched as nearest)");
   // rows and row bytes of every plane
   const long long SB = s.sample_bytes, cw = (w + (1LL << s.hsub) - 1) >> s.hsub, ch = (h + (1LL << s.vsub) - 1) >> s.vsub;
   const int np = packed ? 1 : s.layout == YUV_SEMI ? 2 : 3;
   const long long rows[3] = {h, ch, ch};
   const long long rowbytes[3] = {packed ? 4 * ((w + 1LL) / 2) : w * SB, s.layout == YUV_SEMI ? 2 * cw * SB : cw * SB,
                                  cw * SB};
-  YuvArgs n{};
+  YuvBilinearArgs n{};
   for (int i = 0; i < np; ++i) {
     const NosYuvPlane& q = s.plane[i];
     if (!q.p) return fail("image_patch_planes: null operand");
@@ -801,6 +938,25 @@ int nos_image_patch_planes_yuv(const NosYuvSrc* src, void* planes, float* pixels
     n.tab[i] = s.tab[i];
   }
   n.vsub = s.vsub, n.depth = s.depth, n.shift = s.shift, n.mask = (1 << s.depth) - 1, n.order = s.order;
+  // co-sited: (4, 0) of C[i], C[i] at an even position, held as (0, 4) of C[i - 1], C[i], and (2, 2) at an odd one;
+  // centred: (1, 3) and (3, 1)
+  n.cw = int(cw), n.ch = int(ch);
+  static const int cosited[4] = {0, 4, 2, 2}, centred[4] = {1, 3, 3, 1};
+  for (int i = 0; i < 4; ++i)
+    n.wx[i] = (s.siting & 1 ? cosited : centred)[i], n.wy[i] = (s.siting & 2 ? cosited : centred)[i];
+  if (s.chroma == 1) {
+    // hsub is 1; packed sources have one sample size
+    void (*bilinear)(ImgArgs, YuvBilinearArgs) = nullptr;
+    switch (s.layout * 2 + (s.sample_bytes - 1)) {
+      case 0: bilinear = image_patch_planes_yuv_bilinear<Yuv<YUV_PLANAR, 1, 1, 1>>; break;
+      case 1: bilinear = image_patch_planes_yuv_bilinear<Yuv<YUV_PLANAR, 1, 2, 1>>; break;
+      case 2: bilinear = image_patch_planes_yuv_bilinear<Yuv<YUV_SEMI, 1, 1, 1>>; break;
+      case 3: bilinear = image_patch_planes_yuv_bilinear<Yuv<YUV_SEMI, 1, 2, 1>>; break;
+      default: bilinear = image_patch_planes_yuv_bilinear<Yuv<YUV_PACKED, 1, 1, 1>>; break;
+    }
+    hipLaunchKernelGGL(bilinear, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, n);
+    return check("image_patch_planes_yuv");
+  }
   void (*kern)(ImgArgs, YuvArgs) = nullptr;
   switch (s.layout * 4 + s.hsub * 2 + (s.sample_bytes - 1)) {
     case 0: kern = image_patch_planes_yuv<Yuv<YUV_PLANAR, 0, 1>>; break;
@@ -813,7 +969,7 @@ int nos_image_patch_planes_yuv(const NosYuvSrc* src, void* planes, float* pixels
     case 7: kern = image_patch_planes_yuv<Yuv<YUV_SEMI, 1, 2>>; break;
     default: kern = image_patch_planes_yuv<Yuv<YUV_PACKED, 1, 1>>; break;
   }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, n);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, YuvArgs(n));
   return check("image_patch_planes_yuv");
 }
 

@@ -28,6 +28,10 @@ typedef struct NosYuvSrc {
   NosYuvPlane plane[3];  // planar y, u, v; semi-planar y, pairs; packed the one plane (the rest ignored)
   int tab[12];       // ops/image.py's yuv_table: the matrix times 2^(8 + depth) by rows (R, G, B) x (Y, U, V),
                      // each below 2^23 in size, then the offsets taken from Y, U and V (codes of that depth)
+  int chroma;        // 0 nearest: luma (r, c) takes chroma (r >> vsub, c >> hsub) | 1 bilinear (hsub = 1 only): the two
+                     // nearest samples per subsampled axis by weights in quarters, (sum + 8) >> 4, clamped at the edges
+  int siting;        // bilinear: bit 0 chroma is co-sited with the even luma columns (else centred between a pair),
+                     // bit 1 the same for rows: 1 "left" (MPEG-2, H.264), 0 "center" (JPEG), 3 "topleft", 2 "top"
 } NosYuvSrc;
 
 // src, then the arguments of nos_image_patch_planes_u8 from `planes` on.

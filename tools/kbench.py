@@ -19,7 +19,9 @@ planes, alternating: (a) the fused NV12 launch, (b) the RGB kernel alone on the 
 layouts of the same picture (``nv21_*``, ``i420_*``, ``bgr_*``, ``rgba_*``, ``bgra_*``, and ``rgbcrop_*``: RGB
 rows at a padded pitch, read in place against ``.contiguous()`` first) are timed as the same triple, and so are
 the surfaces of ``models/workload/surfaces.py``, one name per kernel instantiation (``i422_*``, ``i444_*``,
-``nv16_*``, ``nv24_*``, ``yuy2_*``, ``p010_*``, ``i010_*``, ``p210_*``, ``i410_*``, ``i012_*``).
+``nv16_*``, ``nv24_*``, ``yuy2_*``, ``p010_*``, ``i010_*``, ``p210_*``, ``i410_*``, ``i012_*``). Four of them
+again with ``chroma="bilinear"`` (``i420_bilinear_*``, ``nv12_bilinear_*``, ``p010_bilinear_*``, ``yuy2_bilinear_*``):
+there (c) interpolates the chroma in torch before the RGB kernel.
 """
 from __future__ import annotations
 
@@ -289,6 +291,12 @@ def image_bench(a) -> int:
             sp = -(-row // 256) * 256
             buf = torch.randint(0, 256, (3 * sp * h,), generator=g, dtype=torch.uint8).cuda()
             layouts[f"{h}x{w}"][fmt] = surfaces.from_buffer(fmt, buf, h, w, sp)
+        # bilinear chroma (siting "left"): the same surfaces, one per layout and sample size, under keys of their own
+        from dataclasses import replace
+        fixed = layouts[f"{h}x{w}"]
+        for fmt, fr in (("i420", fixed["i420"]), ("nv12", frames[f"{h}x{w}"]), ("p010", fixed["p010"]),
+                        ("yuy2", fixed["yuy2"])):
+            fixed[f"{fmt}_bilinear"] = replace(fr, chroma="bilinear")
     results = []
     for prof, label in (("spx_nps1", "spx"), ("cpx_nps1", "cpx")):
         if label not in a.slices.split(","):

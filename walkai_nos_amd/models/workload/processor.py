@@ -13,8 +13,11 @@ pixel mask, because one call runs images of one size.
 
 A video decoder's NV12 surface goes in as :class:`Nv12` wherever an image does: the colour conversion
 (BT.601 or BT.709, limited or full range, in exact integers: ``ops.image.nv12_to_rgb``) is fused into
-the same launch. It takes chroma nearest — luma ``(r, c)`` uses chroma ``(r >> 1, c >> 1)``, as the
-usual one-call library conversions do; bilinear chroma upsampling is not offered. NV21 is the same class
+the same launch. By default it takes chroma nearest — luma ``(r, c)`` uses chroma ``(r >> 1, c >> 1)``, as the
+usual one-call library conversions do. ``chroma="bilinear"`` interpolates it as decoders and scalers do, at the
+stream's ``siting`` (``left``: MPEG-2 / H.264, the default; ``center``: JPEG; ``topleft``: HEVC / BT.2020;
+``top``), in exact integers (``ops.image.chroma_upsample``) and in the same launch; the bottom sitings, and
+bicubic or Lanczos chroma, are not offered. NV21 is the same class
 with ``vu=True``; a software decoder's planar I420 / YV12 surface is :class:`Yuv420p`; OpenCV's BGR, a
 compositor's RGBA / BGRA, and any of them (or RGB) as a crop or with padded rows is :class:`Packed` — a
 non-contiguous RGB view may also be passed as it is. None of them is copied or converted first: every
@@ -91,15 +94,19 @@ class Nv12(Frame):
     matrix: str = "bt601"
     full_range: bool = False
     vu: bool = False
+    chroma: str = "nearest"
+    siting: str = "left"
     PLANES = ("y", "uv")
 
     def __post_init__(self):
         I.nv12_planes(self.y, self.uv)
         I.nv12_table(self.matrix, self.full_range)
+        I._chroma_check(self.chroma, self.siting)
 
     @classmethod
     def from_buffer(cls, buf: Any, h: int, w: int, pitch: Optional[int] = None, matrix: str = "bt601",
-                    full_range: bool = False, vu: bool = False) -> "Nv12":
+                    full_range: bool = False, vu: bool = False, chroma: str = "nearest",
+                    siting: str = "left") -> "Nv12":
         """A decoder's single surface — ``h`` rows of Y, then ``h / 2`` rows of UV, all ``pitch`` bytes
         apart (default ``w``) — as the two planes, without a copy. ``buf``: a contiguous uint8 tensor or
         ndarray of at least ``(3 h / 2 - 1) * pitch + 2 * ((w + 1) // 2)`` bytes."""
@@ -116,7 +123,8 @@ class Nv12(Frame):
             raise ValueError(f"Nv12.from_buffer: {h}x{w} at pitch {pitch} takes {need} bytes, the buffer has {t.numel()}")
         off = t.storage_offset()
         return cls(t.as_strided((h, w), (pitch, 1), off),
-                   t.as_strided((h // 2, cw2 // 2, 2), (pitch, 2, 1), off + h * pitch), matrix, full_range, vu)
+                   t.as_strided((h // 2, cw2 // 2, 2), (pitch, 2, 1), off + h * pitch), matrix, full_range, vu,
+                   chroma, siting)
 
     def batched(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(y [B, h, w], uv [B, ch, cw, 2])`` views."""
@@ -128,11 +136,16 @@ class Nv12(Frame):
 
     def rgb(self) -> torch.Tensor:
         """The frame converted: uint8 ``[B, h, w, 3]`` (``ops.image.nv12_to_rgb``)."""
+        if self.chroma != "nearest":
+            return I.nv12_to_rgb(self.y, self.uv, self.matrix, self.full_range, self.vu, self.chroma, self.siting)
         if self.vu:
             return I.nv12_to_rgb(self.y, self.uv, self.matrix, self.full_range, vu=True)
         return I.nv12_to_rgb(self.y, self.uv, self.matrix, self.full_range)
 
     def patch_planes(self, hw, patch, mean, std, want_pixels=False):
+        if self.chroma != "nearest":    # the general entry's semi-planar 4:2:0 at depth 8
+            return I.yuv_semiplanar_patch_planes(self.y, self.uv, hw, patch, mean, std, "420", 8, False, self.matrix,
+                                                 self.full_range, want_pixels, self.vu, self.chroma, self.siting)
         if self.vu:
             return I.nv12_patch_planes(self.y, self.uv, hw, patch, mean, std, self.matrix, self.full_range,
                                        want_pixels, vu=True)
@@ -149,15 +162,19 @@ class Yuv420p(Frame):
     v: torch.Tensor
     matrix: str = "bt601"
     full_range: bool = False
+    chroma: str = "nearest"
+    siting: str = "left"
     PLANES = ("y", "u", "v")
 
     def __post_init__(self):
         I.yuv420_planes(self.y, self.u, self.v)
         I.nv12_table(self.matrix, self.full_range)
+        I._chroma_check(self.chroma, self.siting)
 
     @classmethod
     def from_buffer(cls, buf: Any, h: int, w: int, pitch: Optional[int] = None, chroma_pitch: Optional[int] = None,
-                    order: str = "i420", matrix: str = "bt601", full_range: bool = False) -> "Yuv420p":
+                    order: str = "i420", matrix: str = "bt601", full_range: bool = False, chroma: str = "nearest",
+                    siting: str = "left") -> "Yuv420p":
         """A software decoder's single surface — ``h`` rows of Y ``pitch`` bytes apart (default ``w``), then
         ``h / 2`` rows of the first chroma plane ``chroma_pitch`` apart (default ``pitch // 2``), then the
         second chroma plane — as the three planes, without a copy. ``order``: ``i420`` has U first, ``yv12``
@@ -183,7 +200,7 @@ class Yuv420p(Frame):
         first = t.as_strided((ch, cw), (cpitch, 1), off + h * pitch)
         second = t.as_strided((ch, cw), (cpitch, 1), off + h * pitch + ch * cpitch)
         u, v = (first, second) if order == "i420" else (second, first)
-        return cls(t.as_strided((h, w), (pitch, 1), off), u, v, matrix, full_range)
+        return cls(t.as_strided((h, w), (pitch, 1), off), u, v, matrix, full_range, chroma, siting)
 
     def batched(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """``(y [B, h, w], u [B, ch, cw], v [B, ch, cw])`` views."""
@@ -195,9 +212,14 @@ class Yuv420p(Frame):
 
     def rgb(self) -> torch.Tensor:
         """The frame converted: uint8 ``[B, h, w, 3]`` (``ops.image.yuv420_to_rgb``)."""
+        if self.chroma != "nearest":
+            return I.yuv420_to_rgb(self.y, self.u, self.v, self.matrix, self.full_range, self.chroma, self.siting)
         return I.yuv420_to_rgb(self.y, self.u, self.v, self.matrix, self.full_range)
 
     def patch_planes(self, hw, patch, mean, std, want_pixels=False):
+        if self.chroma != "nearest":    # the general entry's planar 4:2:0 at depth 8
+            return I.yuv_planar_patch_planes(self.y, self.u, self.v, hw, patch, mean, std, "420", 8, False, self.matrix,
+                                             self.full_range, want_pixels, self.chroma, self.siting)
         return I.yuv420p_patch_planes(self.y, self.u, self.v, hw, patch, mean, std, self.matrix, self.full_range,
                                       want_pixels)
 

@@ -11,9 +11,24 @@ an image goes, and each is read in place by one launch of the image kernel (``op
 equal to the RGB path on :meth:`rgb`. :func:`from_buffer` builds any of them, by name, over a decoder's single
 buffer. BT.601, BT.709 and BT.2020 (non-constant luminance), limited or full range.
 
-Not offered: bilinear chroma upsampling and chroma siting (chroma is taken nearest); HDR transfer functions (PQ /
-HLG code values are converted as if SDR, without tone mapping); 16-bit-deep samples; Y210 / Y410 / AYUV; big-endian
-samples; BT.2020 constant luminance; batches above one on the fused model path and mixed sizes in one call.
+Chroma is taken nearest — luma ``(r, c)`` takes chroma ``(r >> vs, c >> hs)`` — unless a frame says
+``chroma="bilinear"``: then it is interpolated in exact integers (``ops.image.chroma_upsample``), still inside the one
+launch, at the frame's ``siting``:
+
+========= =========== ========= ====================================
+siting    horizontal  vertical  whose
+========= =========== ========= ====================================
+left      co-sited    centred   MPEG-2, H.264 (the default)
+center    centred     centred   JPEG, MPEG-1
+topleft   co-sited    co-sited  HEVC with BT.2020
+top       centred     co-sited
+========= =========== ========= ====================================
+
+On 4:2:2 only the horizontal part applies; on 4:4:4 bilinear is nearest.
+
+Not offered: the bottom sitings; bicubic or Lanczos chroma; HDR transfer functions (PQ / HLG code values are converted
+as if SDR, without tone mapping); 16-bit-deep samples; Y210 / Y410 / AYUV; big-endian samples; BT.2020 constant
+luminance; batches above one on the fused model path and mixed sizes in one call.
 """
 from __future__ import annotations
 
@@ -41,11 +56,14 @@ class YuvPlanar(Frame):
     msb: bool = False
     matrix: str = "bt601"
     full_range: bool = False
+    chroma: str = "nearest"
+    siting: str = "left"
     PLANES = ("y", "u", "v")
 
     def __post_init__(self):
         I.yuv_planes(self.y, self.u, self.v, self.subsampling, self.depth)
         I.yuv_table(self.matrix, self.full_range, self.depth)
+        I._chroma_check(self.chroma, self.siting)
 
     @property
     def shape(self) -> Tuple[int, int, int, int]:
@@ -54,11 +72,11 @@ class YuvPlanar(Frame):
     def rgb(self) -> torch.Tensor:
         """The frame converted: uint8 ``[B, h, w, 3]`` (``ops.image.yuv_to_rgb``)."""
         return I.yuv_to_rgb(self.y, self.u, self.v, self.subsampling, self.depth, self.msb, self.matrix,
-                            self.full_range)
+                            self.full_range, self.chroma, self.siting)
 
     def patch_planes(self, hw, patch, mean, std, want_pixels=False):
         return I.yuv_planar_patch_planes(self.y, self.u, self.v, hw, patch, mean, std, self.subsampling, self.depth,
-                                         self.msb, self.matrix, self.full_range, want_pixels)
+                                         self.msb, self.matrix, self.full_range, want_pixels, self.chroma, self.siting)
 
 
 @dataclass(frozen=True)
@@ -73,11 +91,14 @@ class YuvSemiPlanar(Frame):
     matrix: str = "bt601"
     full_range: bool = False
     vu: bool = False
+    chroma: str = "nearest"
+    siting: str = "left"
     PLANES = ("y", "uv")
 
     def __post_init__(self):
         I.yuv_semiplanar_planes(self.y, self.uv, self.subsampling, self.depth)
         I.yuv_table(self.matrix, self.full_range, self.depth)
+        I._chroma_check(self.chroma, self.siting)
 
     @property
     def shape(self) -> Tuple[int, int, int, int]:
@@ -86,11 +107,12 @@ class YuvSemiPlanar(Frame):
     def rgb(self) -> torch.Tensor:
         """The frame converted: uint8 ``[B, h, w, 3]`` (``ops.image.yuv_semiplanar_to_rgb``)."""
         return I.yuv_semiplanar_to_rgb(self.y, self.uv, self.subsampling, self.depth, self.msb, self.matrix,
-                                       self.full_range, self.vu)
+                                       self.full_range, self.vu, self.chroma, self.siting)
 
     def patch_planes(self, hw, patch, mean, std, want_pixels=False):
         return I.yuv_semiplanar_patch_planes(self.y, self.uv, hw, patch, mean, std, self.subsampling, self.depth,
-                                             self.msb, self.matrix, self.full_range, want_pixels, self.vu)
+                                             self.msb, self.matrix, self.full_range, want_pixels, self.vu, self.chroma,
+                                             self.siting)
 
 
 @dataclass(frozen=True)
@@ -103,11 +125,14 @@ class Yuyv(Frame):
     order: str = "yuyv"
     matrix: str = "bt601"
     full_range: bool = False
+    chroma: str = "nearest"
+    siting: str = "left"
     PLANES = ("data",)
 
     def __post_init__(self):
         I.yuyv_planes(self.data, self.width, self.order)
         I.yuv_table(self.matrix, self.full_range, 8)
+        I._chroma_check(self.chroma, self.siting)
 
     @property
     def shape(self) -> Tuple[int, int, int, int]:
@@ -115,11 +140,11 @@ class Yuyv(Frame):
 
     def rgb(self) -> torch.Tensor:
         """The frame converted: uint8 ``[B, h, width, 3]`` (``ops.image.yuyv_to_rgb``)."""
-        return I.yuyv_to_rgb(self.data, self.width, self.order, self.matrix, self.full_range)
+        return I.yuyv_to_rgb(self.data, self.width, self.order, self.matrix, self.full_range, self.chroma, self.siting)
 
     def patch_planes(self, hw, patch, mean, std, want_pixels=False):
         return I.yuyv_patch_planes(self.data, self.width, self.order, hw, patch, mean, std, self.matrix,
-                                   self.full_range, want_pixels)
+                                   self.full_range, want_pixels, self.chroma, self.siting)
 
 
 #: name -> (layout, subsampling, depth, value in the high bits, second chroma first)
@@ -139,7 +164,8 @@ _YUYV = {"yuy2": "yuyv", "uyvy": "uyvy", "yvyu": "yvyu"}
 
 
 def from_buffer(name: str, buf: Any, h: int, w: int, pitch: Optional[int] = None, chroma_pitch: Optional[int] = None,
-                matrix: str = "bt601", full_range: bool = False) -> Frame:
+                matrix: str = "bt601", full_range: bool = False, chroma: str = "nearest",
+                siting: str = "left") -> Frame:
     """A decoder's or a capture card's single buffer as a frame of format ``name`` (:data:`FORMATS`), without a
     copy. ``buf``: a contiguous uint8 tensor or ndarray that holds all of it. Pitches are in bytes.
 
@@ -150,7 +176,10 @@ def from_buffer(name: str, buf: Any, h: int, w: int, pitch: Optional[int] = None
       Planar: two planes, the second ``rows * chroma_pitch`` after the first, ``chroma_pitch`` by default ``pitch
       // 2`` (``pitch`` for 4:4:4) — in both cases at least a chroma row's bytes (an odd width); ``yv16`` / ``yv24`` have V first, ``nv61`` / ``nv42`` (V, U) pairs.
     * 16-bit formats (``p...``: value in the high bits; ``i...``: in the low bits): little-endian words, so the
-      buffer starts at an even byte and both pitches are even; the planes come out as ``torch.uint16`` views."""
+      buffer starts at an even byte and both pitches are even; the planes come out as ``torch.uint16`` views.
+
+    ``chroma`` and ``siting``: how the frame's chroma is brought to the luma grid (``ops.image.CHROMA`` and
+    ``SITINGS``)."""
     who = f"from_buffer({name!r})"
     if name not in FORMATS:
         raise ValueError(f"{who}: an unknown format; one of {sorted(FORMATS)}")
@@ -174,7 +203,7 @@ def from_buffer(name: str, buf: Any, h: int, w: int, pitch: Optional[int] = None
         need = (h - 1) * pitch + row
         if t.numel() < need:
             raise ValueError(f"{who}: {h}x{w} at pitch {pitch} takes {need} bytes, the buffer has {t.numel()}")
-        return Yuyv(t.as_strided((h, row), (pitch, 1), off), w, _YUYV[name], matrix, full_range)
+        return Yuyv(t.as_strided((h, row), (pitch, 1), off), w, _YUYV[name], matrix, full_range, chroma, siting)
     sb = 1 if depth == 8 else 2
     cw, ch = (w + (1 << hs) - 1) >> hs, h >> vs
     yrow = w * sb
@@ -209,7 +238,8 @@ def from_buffer(name: str, buf: Any, h: int, w: int, pitch: Optional[int] = None
         return e.as_strided(size, stride, eo + byte0 // sb)
     y = plane(0, h, w, pitch)
     if layout == "semiplanar":
-        return YuvSemiPlanar(y, plane(h * pitch, ch, cw, cpitch, (2,)), sub, depth, msb, matrix, full_range, swap)
+        return YuvSemiPlanar(y, plane(h * pitch, ch, cw, cpitch, (2,)), sub, depth, msb, matrix, full_range, swap,
+                             chroma, siting)
     first, second = plane(h * pitch, ch, cw, cpitch), plane(h * pitch + ch * cpitch, ch, cw, cpitch)
     u, v = (second, first) if swap else (first, second)
-    return YuvPlanar(y, u, v, sub, depth, msb, matrix, full_range)
+    return YuvPlanar(y, u, v, sub, depth, msb, matrix, full_range, chroma, siting)

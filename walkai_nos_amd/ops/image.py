@@ -24,8 +24,8 @@ is rounded to uint8 between the two passes, so pixels differ from it by less tha
   the colour conversion happens while the kernel stages a patch's source footprint, so no RGB frame
   is materialised. The conversion is defined in integers (:func:`nv12_table`), so the fused result is
   bit-equal to :func:`image_patch_planes` of :func:`nv12_to_rgb`. Chroma is taken nearest — luma
-  ``(r, c)`` uses chroma ``(r >> 1, c >> 1)``, what the usual one-call library conversions do;
-  bilinear chroma upsampling (and with it chroma siting) is not offered.
+  ``(r, c)`` uses chroma ``(r >> 1, c >> 1)``, what the usual one-call library conversions do —
+  unless ``chroma="bilinear"`` is asked for (below).
 * :func:`yuv420_to_rgb` / :func:`yuv420p_patch_planes` — planar 4:2:0 (I420 / YV12: what a software decoder and
   most JPEG decoders give), three planes with a pitch each; ``nv12_patch_planes(..., vu=True)`` is NV21. The
   planar function is the definition of the conversion: :func:`nv12_to_rgb` is it on the de-interleaved planes.
@@ -36,9 +36,13 @@ is rounded to uint8 between the two passes, so pixels differ from it by less tha
   :func:`yuyv_patch_planes` — the rest of the YUV front end behind one launch descriptor (:class:`NosYuvSrc`):
   4:2:2 and 4:4:4 beside 4:2:0, packed 4:2:2 (YUY2 / UYVY / YVYU), and 10 / 12-bit codes in 16-bit words (P010's
   high bits or ``yuv420p10le``'s low bits; the other bits are ignored), with BT.2020 (non-constant luminance)
-  beside the two older matrices (:func:`yuv_table`). Chroma stays nearest; PQ / HLG code values are converted as
-  if SDR (no transfer function, no tone mapping); 16-bit-deep samples, Y210 / Y410 / AYUV and big-endian words
-  are not offered.
+  beside the two older matrices (:func:`yuv_table`). PQ / HLG code values are converted as if SDR (no transfer
+  function, no tone mapping); 16-bit-deep samples, Y210 / Y410 / AYUV and big-endian words are not offered.
+* :func:`chroma_upsample` — ``chroma="bilinear", siting=...`` on every ``*_to_rgb`` and on the general entry's
+  ``*_patch_planes``: chroma interpolated as decoders and scalers do, honouring where the stream's chroma samples
+  lie (:data:`SITINGS`: ``left``, ``center``, ``topleft``, ``top``), in exact integers — two taps per subsampled
+  axis, weights in quarters, ``(sum + 8) >> 4`` — inside the same launch's staging loop. The default stays
+  ``"nearest"``. The bottom sitings and bicubic / Lanczos chroma are not offered.
 
 Every layout is bit-equal to :func:`image_patch_planes` of the converted or re-ordered contiguous RGB frame,
 which is also what runs on the CPU, with the ``torch`` backend and past a layout's footprint limit.
@@ -379,13 +383,79 @@ def yuv420_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, any_strides
     return y, u, v
 
 
+#: how chroma is brought to the luma grid: ``nearest`` — luma ``(r, c)`` takes chroma ``(r >> vs, c >> hs)`` — or
+#: ``bilinear`` (:func:`chroma_upsample`)
+CHROMA = ("nearest", "bilinear")
+#: where a chroma sample lies (ffmpeg's / H.273's names) -> bit 0: horizontally co-sited with the even luma columns,
+#: bit 1: vertically co-sited with the even luma rows; a clear bit is centred between the pair. ``left`` is MPEG-2's
+#: and H.264's default, ``center`` JPEG's and MPEG-1's, ``topleft`` HEVC's for BT.2020. (``NosYuvSrc.siting``)
+SITINGS = {"left": 1, "center": 0, "topleft": 3, "top": 2}
+
+
+def _chroma_check(chroma: str, siting: str) -> None:
+    if chroma not in CHROMA:
+        raise ValueError(f"yuv: chroma {chroma!r} is none of {CHROMA}")
+    if siting not in SITINGS:
+        raise ValueError(f"yuv: siting {siting!r} is none of {tuple(SITINGS)}")
+
+
+def _chroma_axis(n: int, nc: int, sub: int, cosited: bool, device) -> Tuple[torch.Tensor, ...]:
+    """The two taps of every luma position of one axis: ``(i0, i1, w0, w1)``, indices clamped to the plane,
+    weights in quarters. (Arithmetic on an ``arange``: nothing is copied from the host.)"""
+    x = torch.arange(n, device=device)
+    if not sub:
+        return x, x, torch.full_like(x, 4), torch.zeros_like(x)
+    i, odd = x >> 1, x & 1
+    if cosited:     # even: (4, 0) of C[i], C[i]; odd: (2, 2) of C[i], C[i + 1]
+        i0, i1, w0, w1 = i, i + odd, 4 - 2 * odd, 2 * odd
+    else:           # even: (1, 3) of C[i - 1], C[i]; odd: (3, 1) of C[i], C[i + 1]
+        i0, i1, w0, w1 = i - 1 + odd, i + odd, 1 + 2 * odd, 3 - 2 * odd
+    return i0.clamp(0, nc - 1), i1.clamp(0, nc - 1), w0, w1
+
+
+def chroma_upsample(codes: torch.Tensor, h: int, w: int, hs: int, vs: int, siting: str = "left") -> torch.Tensor:
+    """Bilinear chroma in exact integers: int32 codes ``[B, ch, cw]`` of a plane subsampled by ``2^hs`` x ``2^vs``
+    -> ``[B, h, w]`` codes of the same depth — what the kernel computes with ``chroma="bilinear"``. Per subsampled
+    axis luma position ``x`` has ``i = x >> 1`` and takes two samples with weights in quarters:
+
+    ========== ============================ ==============================
+    the axis   even ``x``                   odd ``x``
+    ========== ============================ ==============================
+    co-sited   ``(4, 0)`` of C[i], C[i]     ``(2, 2)`` of C[i], C[i + 1]
+    centred    ``(1, 3)`` of C[i - 1], C[i] ``(3, 1)`` of C[i], C[i + 1]
+    ========== ============================ ==============================
+
+    with indices clamped to the plane; an axis that is not subsampled has ``(4, 0)`` on the sample itself. The
+    result is ``(sum of wy * wx * C over the 2 x 2 taps + 8) >> 4``, that is ``(wx0 C0 + wx1 C1 + 2) >> 2`` for
+    4:2:2: round-half-up of the linear interpolation at the luma position. ``siting`` (:data:`SITINGS`): ``left``
+    is co-sited horizontally and centred vertically, ``center`` centred on both axes (``F.interpolate``'s
+    ``bilinear`` at scale 2, rounded half up), ``topleft`` co-sited on both, ``top`` centred horizontally."""
+    _chroma_check("bilinear", siting)
+    if codes.dim() != 3 or codes.dtype != torch.int32:
+        raise ValueError("chroma_upsample: int32 codes [B, ch, cw]")
+    ch, cw = codes.shape[1:]
+    if (ch, cw) != ((h + (1 << vs) - 1) >> vs, (w + (1 << hs) - 1) >> hs):
+        raise ValueError(f"chroma_upsample: a {h}x{w} picture subsampled by (2^{hs}, 2^{vs}) has chroma "
+                         f"{((h + (1 << vs) - 1) >> vs, (w + (1 << hs) - 1) >> hs)}, not {(ch, cw)}")
+    bits = SITINGS[siting]
+    y0, y1, wy0, wy1 = _chroma_axis(h, ch, vs, bool(bits & 2), codes.device)
+    x0, x1, wx0, wx1 = _chroma_axis(w, cw, hs, bool(bits & 1), codes.device)
+    # 16 x a 12-bit code is below 2^16: int32 cannot overflow
+    rows = codes[:, y0] * wy0.to(torch.int32)[None, :, None] + codes[:, y1] * wy1.to(torch.int32)[None, :, None]
+    both = rows[:, :, x0] * wx0.to(torch.int32) + rows[:, :, x1] * wx1.to(torch.int32)
+    return (both + 8) >> 4
+
+
 def yuv420_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, matrix: str = "bt601",
-                  full_range: bool = False) -> torch.Tensor:
+                  full_range: bool = False, chroma: str = "nearest", siting: str = "left") -> torch.Tensor:
     """A planar 4:2:0 frame as interleaved RGB, uint8 ``[B, h, w, 3]``: the definition of the conversion (and
     what runs on the CPU, with the ``torch`` backend and past the kernel's limits). Nearest chroma,
-    exact int32 arithmetic on :func:`nv12_table`."""
+    exact int32 arithmetic on :func:`nv12_table`. ``chroma="bilinear"``: :func:`yuv_to_rgb`'s, at ``siting``."""
     y, u, v = yuv420_planes(y, u, v, any_strides=True)
     t = nv12_table(matrix, full_range)
+    _chroma_check(chroma, siting)
+    if chroma == "bilinear":
+        return yuv_to_rgb(y, u, v, "420", 8, False, matrix, full_range, chroma, siting)
     h, w = y.shape[1:]
     rows, cols = torch.arange(h, device=y.device) >> 1, torch.arange(w, device=y.device) >> 1
     # the largest term is below 2^25 (138 438 x 128, 76 309 x 255) and the sum below 2^27: int32 cannot overflow
@@ -397,11 +467,11 @@ def yuv420_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, matrix: str
 
 
 def nv12_to_rgb(y: torch.Tensor, uv: torch.Tensor, matrix: str = "bt601", full_range: bool = False,
-                vu: bool = False) -> torch.Tensor:
+                vu: bool = False, chroma: str = "nearest", siting: str = "left") -> torch.Tensor:
     """An NV12 frame as interleaved RGB, uint8 ``[B, h, w, 3]``: :func:`yuv420_to_rgb` of its de-interleaved
     planes (``vu``: the pairs are (V, U), NV21)."""
     y, uv = nv12_planes(y, uv)
-    return yuv420_to_rgb(y, uv[..., 1 if vu else 0], uv[..., 0 if vu else 1], matrix, full_range)
+    return yuv420_to_rgb(y, uv[..., 1 if vu else 0], uv[..., 0 if vu else 1], matrix, full_range, chroma, siting)
 
 
 def _storage_bounds(t: torch.Tensor) -> Tuple[int, int]:
@@ -636,20 +706,28 @@ def yuv_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, subsampling: s
 
 
 def yuv_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, subsampling: str = "420", depth: int = 8,
-               msb: bool = False, matrix: str = "bt601", full_range: bool = False) -> torch.Tensor:
+               msb: bool = False, matrix: str = "bt601", full_range: bool = False, chroma: str = "nearest",
+               siting: str = "left") -> torch.Tensor:
     """A planar frame of any of the three chroma geometries and sample depths as interleaved RGB, uint8 ``[B, h,
     w, 3]``: the definition of the conversion (and what runs on the CPU, with the ``torch`` backend and past the
     kernel's limits). Nearest chroma — luma ``(r, c)`` takes chroma ``(r >> vs, c >> hs)`` — and exact int32
-    arithmetic on :func:`yuv_table`. For ``"420"`` at depth 8 it equals :func:`yuv420_to_rgb`."""
+    arithmetic on :func:`yuv_table`. For ``"420"`` at depth 8 it equals :func:`yuv420_to_rgb`. With
+    ``chroma="bilinear"`` the chroma codes are :func:`chroma_upsample`'s at ``siting`` instead (codes of the same
+    depth, so the table arithmetic is the same and as far from overflow); on ``"444"`` that is nearest."""
     y, u, v = yuv_planes(y, u, v, subsampling, depth, any_strides=True)
     t = yuv_table(matrix, full_range, depth)
+    _chroma_check(chroma, siting)
     hs, vs = YUV_SUBSAMPLING[subsampling]
     h, w = y.shape[1:]
     rows, cols = torch.arange(h, device=y.device) >> vs, torch.arange(w, device=y.device) >> hs
     # the largest sum is below 5.81e8 at depth 12: int32 cannot overflow
     yy = yuv_codes(y, depth, msb) - t[9]
-    uu = yuv_codes(u, depth, msb)[:, rows][:, :, cols] - t[10]
-    vv = yuv_codes(v, depth, msb)[:, rows][:, :, cols] - t[11]
+    if chroma == "bilinear" and hs:
+        uu = chroma_upsample(yuv_codes(u, depth, msb), h, w, hs, vs, siting) - t[10]
+        vv = chroma_upsample(yuv_codes(v, depth, msb), h, w, hs, vs, siting) - t[11]
+    else:
+        uu = yuv_codes(u, depth, msb)[:, rows][:, :, cols] - t[10]
+        vv = yuv_codes(v, depth, msb)[:, rows][:, :, cols] - t[11]
     out = [(t[3 * k] * yy + t[3 * k + 1] * uu + t[3 * k + 2] * vv + (1 << (7 + depth))) >> (8 + depth)
            for k in range(3)]
     return torch.stack(out, dim=-1).clamp_(0, 255).to(torch.uint8)
@@ -690,19 +768,20 @@ def yuyv_planes(data: torch.Tensor, width: int, order: str = "yuyv") \
 
 
 def yuyv_to_rgb(data: torch.Tensor, width: int, order: str = "yuyv", matrix: str = "bt601",
-                full_range: bool = False) -> torch.Tensor:
+                full_range: bool = False, chroma: str = "nearest", siting: str = "left") -> torch.Tensor:
     """Packed 4:2:2 as interleaved RGB, uint8 ``[B, h, width, 3]``: :func:`yuv_to_rgb` of :func:`yuyv_planes`'
     three views as ``"422"``."""
-    return yuv_to_rgb(*yuyv_planes(data, width, order), "422", 8, False, matrix, full_range)
+    return yuv_to_rgb(*yuyv_planes(data, width, order), "422", 8, False, matrix, full_range, chroma, siting)
 
 
 def yuv_semiplanar_to_rgb(y: torch.Tensor, uv: torch.Tensor, subsampling: str = "420", depth: int = 8,
                           msb: bool = False, matrix: str = "bt601", full_range: bool = False,
-                          vu: bool = False) -> torch.Tensor:
+                          vu: bool = False, chroma: str = "nearest", siting: str = "left") -> torch.Tensor:
     """A semi-planar frame as interleaved RGB: :func:`yuv_to_rgb` of its de-interleaved planes (``vu``: the pairs
     are (V, U))."""
     y, uv = yuv_semiplanar_planes(y, uv, subsampling, depth)
-    return yuv_to_rgb(y, uv[..., 1 if vu else 0], uv[..., 0 if vu else 1], subsampling, depth, msb, matrix, full_range)
+    return yuv_to_rgb(y, uv[..., 1 if vu else 0], uv[..., 0 if vu else 1], subsampling, depth, msb, matrix, full_range,
+                      chroma, siting)
 
 
 class NosYuvPlane(ctypes.Structure):
@@ -715,19 +794,23 @@ class NosYuvSrc(ctypes.Structure):
     """The general YUV entry's source descriptor (``csrc/image_yuv.h``, field for field)."""
     _fields_ = [("size", ctypes.c_int), ("layout", ctypes.c_int), ("hsub", ctypes.c_int), ("vsub", ctypes.c_int),
                 ("sample_bytes", ctypes.c_int), ("depth", ctypes.c_int), ("shift", ctypes.c_int),
-                ("order", ctypes.c_int), ("plane", NosYuvPlane * 3), ("tab", ctypes.c_int * 12)]
+                ("order", ctypes.c_int), ("plane", NosYuvPlane * 3), ("tab", ctypes.c_int * 12),
+                ("chroma", ctypes.c_int), ("siting", ctypes.c_int)]
 
 
 YUV_PLANAR, YUV_SEMIPLANAR, YUV_PACKED = 0, 1, 2
 
 
 def yuv_src(layout: int, planes: Sequence[torch.Tensor], subsampling: str, depth: int, msb: bool, order: int,
-            table: Sequence[int]) -> NosYuvSrc:
+            table: Sequence[int], chroma: str = "nearest", siting: str = "left") -> NosYuvSrc:
     """The descriptor of ``planes`` — views ``[B, rows, row elements]`` of uint8 or 16-bit samples, each read by
-    its own strides inside its own storage."""
+    its own strides inside its own storage. Bilinear chroma of a 4:4:4 source is nearest, and is described so."""
+    _chroma_check(chroma, siting)
     hs, vs = YUV_SUBSAMPLING[subsampling]
+    bilinear = chroma == "bilinear" and hs != 0
     src = NosYuvSrc(size=ctypes.sizeof(NosYuvSrc), layout=layout, hsub=hs, vsub=vs, sample_bytes=1 if depth == 8 else 2,
-                    depth=depth, shift=16 - depth if (msb and depth != 8) else 0, order=order)
+                    depth=depth, shift=16 - depth if (msb and depth != 8) else 0, order=order,
+                    chroma=int(bilinear), siting=SITINGS[siting] if bilinear else 0)
     for i, t in enumerate(planes):
         lo, hi = _storage_bounds(t)
         es = t.element_size()
@@ -759,61 +842,68 @@ def _yuv_launch(src: NosYuvSrc, tabs: tuple, B: int, h: int, w: int, H: int, W: 
 def yuv_planar_patch_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, out_hw: Tuple[int, int], patch: int,
                             mean: Sequence[float], std: Sequence[float], subsampling: str = "420", depth: int = 8,
                             msb: bool = False, matrix: str = "bt601", full_range: bool = False,
-                            want_pixels: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                            want_pixels: bool = False, chroma: str = "nearest", siting: str = "left") \
+        -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """:func:`image_patch_planes` of a planar frame (:func:`yuv_planes`' layout: I422, I444, I010, ``yuv422p10le``
-    ...), bit-equal to ``image_patch_planes(yuv_to_rgb(y, u, v, subsampling, depth, msb, matrix, full_range), ...)``
-    — which is what runs on a CPU tensor, with the ``torch`` backend and past the kernel's limits. On the GPU one
-    HIP launch reads the three planes in place, each by its own strides."""
+    ...), bit-equal to ``image_patch_planes(yuv_to_rgb(y, u, v, subsampling, depth, msb, matrix, full_range, chroma,
+    siting), ...)`` — which is what runs on a CPU tensor, with the ``torch`` backend and past the kernel's limits.
+    On the GPU one HIP launch reads the three planes in place, each by its own strides; with ``chroma="bilinear"``
+    it interpolates the chroma at ``siting`` (:func:`chroma_upsample`) while it stages them."""
     y, u, v = yuv_planes(y, u, v, subsampling, depth)
     table = yuv_table(matrix, full_range, depth)
+    _chroma_check(chroma, siting)
     B, h, w = y.shape
     H, W = int(out_hw[0]), int(out_hw[1])
     tabs = _yuv_fused(y, (h, w), (H, W), patch)
     if tabs is None:
-        return image_patch_planes(yuv_to_rgb(y, u, v, subsampling, depth, msb, matrix, full_range), (H, W), patch,
-                                  mean, std, want_pixels)
-    src = yuv_src(YUV_PLANAR, (y, u, v), subsampling, depth, msb, 0, table)
+        return image_patch_planes(yuv_to_rgb(y, u, v, subsampling, depth, msb, matrix, full_range, chroma, siting),
+                                  (H, W), patch, mean, std, want_pixels)
+    src = yuv_src(YUV_PLANAR, (y, u, v), subsampling, depth, msb, 0, table, chroma, siting)
     return _yuv_launch(src, tabs, B, h, w, H, W, patch, mean, std, want_pixels, y.device, "yuv_planar_patch_planes")
 
 
 def yuv_semiplanar_patch_planes(y: torch.Tensor, uv: torch.Tensor, out_hw: Tuple[int, int], patch: int,
                                 mean: Sequence[float], std: Sequence[float], subsampling: str = "420", depth: int = 8,
                                 msb: bool = False, matrix: str = "bt601", full_range: bool = False,
-                                want_pixels: bool = False, vu: bool = False) \
-        -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """The same of a semi-planar frame (:func:`yuv_semiplanar_planes`' layout: NV16 / NV61, NV24 / NV42, P010, P012,
-    P210, P410), bit-equal to ``image_patch_planes(yuv_semiplanar_to_rgb(...), ...)``. ``vu``: the pairs are
-    (V, U)."""
+                                want_pixels: bool = False, vu: bool = False, chroma: str = "nearest",
+                                siting: str = "left") -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The same of a semi-planar frame (:func:`yuv_semiplanar_planes`' layout: NV12 / NV21, NV16 / NV61, NV24 / NV42,
+    P010, P012, P210, P410), bit-equal to ``image_patch_planes(yuv_semiplanar_to_rgb(...), ...)``. ``vu``: the pairs
+    are (V, U)."""
     y, uv = yuv_semiplanar_planes(y, uv, subsampling, depth)
     table = yuv_table(matrix, full_range, depth)
+    _chroma_check(chroma, siting)
     B, h, w = y.shape
     H, W = int(out_hw[0]), int(out_hw[1])
     tabs = _yuv_fused(y, (h, w), (H, W), patch)
     if tabs is None:
-        rgb = yuv_semiplanar_to_rgb(y, uv, subsampling, depth, msb, matrix, full_range, vu)
+        rgb = yuv_semiplanar_to_rgb(y, uv, subsampling, depth, msb, matrix, full_range, vu, chroma, siting)
         return image_patch_planes(rgb, (H, W), patch, mean, std, want_pixels)
     pairs = uv.as_strided((B, uv.shape[1], 2 * uv.shape[2]), (uv.stride(0), uv.stride(1), 1))   # a view, never a copy
-    src = yuv_src(YUV_SEMIPLANAR, (y, pairs), subsampling, depth, msb, int(bool(vu)), table)
+    src = yuv_src(YUV_SEMIPLANAR, (y, pairs), subsampling, depth, msb, int(bool(vu)), table, chroma, siting)
     return _yuv_launch(src, tabs, B, h, w, H, W, patch, mean, std, want_pixels, y.device,
                        "yuv_semiplanar_patch_planes")
 
 
 def yuyv_patch_planes(data: torch.Tensor, width: int, order: str, out_hw: Tuple[int, int], patch: int,
                       mean: Sequence[float], std: Sequence[float], matrix: str = "bt601", full_range: bool = False,
-                      want_pixels: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                      want_pixels: bool = False, chroma: str = "nearest", siting: str = "left") \
+        -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """The same of packed 4:2:2 (:func:`yuyv_planes`' layout: YUY2, UYVY, YVYU), bit-equal to
-    ``image_patch_planes(yuyv_to_rgb(data, width, order, matrix, full_range), ...)``. On the GPU one HIP launch
-    reads a group's two macropixels in one read, the rows wherever their pitch puts them."""
+    ``image_patch_planes(yuyv_to_rgb(data, width, order, matrix, full_range, chroma, siting), ...)``. On the GPU one
+    HIP launch reads a group's two macropixels in one read (with bilinear chroma the one before and the one after as
+    well), the rows wherever their pitch puts them."""
     yv = yuyv_planes(data, width, order)[0]
+    _chroma_check(chroma, siting)
     data = data if data.dim() == 3 else data[None]
     table = yuv_table(matrix, full_range, 8)
     B, h, w = yv.shape
     H, W = int(out_hw[0]), int(out_hw[1])
     tabs = _yuv_fused(data, (h, w), (H, W), patch)
     if tabs is None:
-        return image_patch_planes(yuyv_to_rgb(data, width, order, matrix, full_range), (H, W), patch, mean, std,
-                                  want_pixels)
-    src = yuv_src(YUV_PACKED, (data,), "422", 8, False, tuple(YUYV_ORDERS).index(order), table)
+        return image_patch_planes(yuyv_to_rgb(data, width, order, matrix, full_range, chroma, siting), (H, W), patch,
+                                  mean, std, want_pixels)
+    src = yuv_src(YUV_PACKED, (data,), "422", 8, False, tuple(YUYV_ORDERS).index(order), table, chroma, siting)
     return _yuv_launch(src, tabs, B, h, w, H, W, patch, mean, std, want_pixels, data.device, "yuyv_patch_planes")
 
 
