@@ -27,6 +27,11 @@
 //  * image_patch_planes_yuv_bilinear<Yuv<layout, 1, sample bytes, 1>> — the same with bilinear chroma at a siting
 //    (stage_yuv_bilinear): five more instantiations, the subsampled layouts; each thread reads its group's chroma
 //    window straight from the planes (no chroma tile in LDS).
+//  * image_patch_planes_yuv_hdr<Yuv<layout, hsub, 2[, 1]>> — 10 / 12-bit sources whose codes are PQ or HLG, tone-mapped
+//    to SDR: the two staging loops again, with hdr_pixel in place of yuv_channel — the R'G'B' codes at the source's
+//    depth through a table, a 3 x 3 integer matrix and a second table (image_yuv.h's NosYuvHdr; the host builds them in
+//    fp64 and the kernel knows no transfer function). Six more instantiations: planar and semi-planar, 4:4:4 and
+//    subsampled with nearest chroma, subsampled with bilinear chroma.
 //  * detections_f32 — softmax over the class logits, the best of the first L classes, the box in
 //    corner format scaled to the original image, and a stable compaction of the rows above the
 //    threshold; one workgroup per image, one wave per row.
@@ -122,6 +127,14 @@ struct YuvBilinearArgs : YuvArgs {
   int cw, ch;
   int wx[4], wy[4];
 };
+// What the HDR instantiations (Hdr<Yuv<...>>) take beside that: the two tables of image_yuv.h's NosYuvHdr (device
+// memory, the same for every thread: they live in L2 and the vector cache), lut1's entries and the gamut matrix by rows.
+struct YuvHdrArgs : YuvBilinearArgs {
+  const uint16_t* lut1;
+  const uint8_t* lut2;
+  int entries;
+  int gamut[9];
+};
 enum { YUV_PLANAR = 0, YUV_SEMI = 1, YUV_PACKED = 2 };
 template <int LAYOUT_, int HSUB_, int SB_, int CHROMA_ = 0>
 struct Yuv {
@@ -130,6 +143,14 @@ struct Yuv {
 struct NoYuv {
   static constexpr int LAYOUT = -1, HSUB = 0, SB = 1, CHROMA = 0;
 };
+// a Yuv<...> whose codes are PQ or HLG: staged through the tables of YuvHdrArgs (a wrapper, so that the names of the
+// older instantiations are what they were)
+template <class Y>
+struct Hdr : Y {};
+template <class Y>
+constexpr bool IS_HDR = false;
+template <class Y>
+constexpr bool IS_HDR<Hdr<Y>> = true;
 
 // four bytes at q, of which those inside [lo, hi) are read: one aligned dword where q allows it
 __device__ __forceinline__ uint32_t load4(uintptr_t q, uintptr_t lo, uintptr_t hi) {
@@ -200,6 +221,31 @@ __device__ __forceinline__ uint32_t yuv_channel(const int* t, int c, int y, int 
   return uint32_t(min(max(s, 0), (1 << (16 + depth)) - 1)) >> (8 + depth);
 }
 
+// One pixel of a PQ or HLG source as R | G << 8 | B << 16 (y, u, v: the codes less the table's offsets). The matrix's
+// sums as in yuv_channel, but cut to codes k of the source's depth (the table is scaled by 2^(8 + depth): clamp to
+// [0, 2^(16 + depth)) after adding 2^15, then shift by 16); l = lut1[k] is tone-mapped linear light, 16383 = SDR
+// white; the gamut matrix in 2^-12 fixed point, clip((sum + 2048) >> 12, 0, 16383); lut2 of that is the sRGB byte.
+// Exact in int32 with 24-bit multiplies: the host checks the gamut (below 2^15), l is below 2^14, the sums below 2^29.
+// The indices cannot leave the tables: k < entries (the host checks entries == 2^depth) and the sum is clipped to
+// lut2's 16384 entries.
+__device__ __forceinline__ uint32_t hdr_pixel(const YuvHdrArgs& n, int y, int u, int v) {
+  int l[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int s = __mul24(n.tab[3 * c], y) + __mul24(n.tab[3 * c + 1], u) + __mul24(n.tab[3 * c + 2], v) + 32768;
+    const int k = int(uint32_t(min(max(s, 0), (1 << (16 + n.depth)) - 1)) >> 16);
+    l[c] = n.lut1[min(k, n.entries - 1)];
+  }
+  uint32_t px = 0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int s = (__mul24(n.gamut[3 * c], l[0]) + __mul24(n.gamut[3 * c + 1], l[1]) +
+                   __mul24(n.gamut[3 * c + 2], l[2]) + 2048) >> 12;
+    px |= uint32_t(n.lut2[min(max(s, 0), 16383)]) << (8 * c);
+  }
+  return px;
+}
+
 // sample k of the dwords w (lowest address first): a byte, or a little-endian 16-bit word's code
 template <int SB>
 __device__ __forceinline__ int yuv_sample(const uint32_t* w, int k, int shift, int mask) {
@@ -211,8 +257,9 @@ __device__ __forceinline__ int yuv_sample(const uint32_t* w, int k, int shift, i
 // tile. Nearest chroma: luma (r, c) takes chroma (r >> vsub, c >> hsub), so the group has 4 >> hsub chroma
 // samples under it. Reads: 4 * SB luma bytes and (4 >> hsub) * SB bytes of each chroma plane (planar), or
 // twice that of the interleaved pairs (semi-planar), or the group's two 4-byte macropixels in one read (packed).
-template <class Y>
-__device__ __forceinline__ void stage_yuv(const YuvArgs& n, int b, int sy, int sx, uint32_t* dst) {
+// A: YuvArgs, or YuvHdrArgs of an Hdr<Yuv<...>>, whose pixels are hdr_pixel's instead (the same reads and chroma).
+template <class Y, class A>
+__device__ __forceinline__ void stage_yuv(const A& n, int b, int sy, int sx, uint32_t* dst) {
   constexpr int SB = Y::SB, HSUB = Y::HSUB, NC = 4 >> HSUB;
   const int depth = SB == 1 ? 8 : n.depth, shift = SB == 1 ? 0 : n.shift, mask = SB == 1 ? 255 : n.mask;
   int yy[4], uu[4], vv[4];
@@ -259,8 +306,11 @@ __device__ __forceinline__ void stage_yuv(const YuvArgs& n, int b, int sy, int s
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int y = yy[k] - n.tab[9], u = uu[k >> HSUB] - n.tab[10], v = vv[k >> HSUB] - n.tab[11];
-    px[k] = yuv_channel(n.tab, 0, y, u, v, depth) | yuv_channel(n.tab, 1, y, u, v, depth) << 8 |
-            yuv_channel(n.tab, 2, y, u, v, depth) << 16;
+    if constexpr (IS_HDR<Y>)
+      px[k] = hdr_pixel(n, y, u, v);
+    else
+      px[k] = yuv_channel(n.tab, 0, y, u, v, depth) | yuv_channel(n.tab, 1, y, u, v, depth) << 8 |
+              yuv_channel(n.tab, 2, y, u, v, depth) << 16;
   }
   store_rgb4(dst, px);
 }
@@ -327,8 +377,9 @@ __device__ __forceinline__ void chroma_row4(const int* wx, const int (&c)[4], in
 // the nearest one does. n.wx / n.wy hold (w of the lower tap, w of the upper) for even, then for odd positions;
 // the lower tap of an even position is C[i - 1] (weight 0 when co-sited). Reads: the luma as stage_yuv, and the
 // chroma window (chroma_window) of one row (4:2:2) or two (4:2:0).
-template <class Y>
-__device__ __forceinline__ void stage_yuv_bilinear(const YuvBilinearArgs& n, int b, int sy, int sx, uint32_t* dst) {
+// A: YuvBilinearArgs, or YuvHdrArgs as in stage_yuv.
+template <class Y, class A>
+__device__ __forceinline__ void stage_yuv_bilinear(const A& n, int b, int sy, int sx, uint32_t* dst) {
   constexpr int SB = Y::SB;
   static_assert(Y::HSUB == 1, "bilinear chroma is for horizontally subsampled sources");
   const int depth = SB == 1 ? 8 : n.depth, shift = SB == 1 ? 0 : n.shift, mask = SB == 1 ? 255 : n.mask;
@@ -373,14 +424,17 @@ __device__ __forceinline__ void stage_yuv_bilinear(const YuvBilinearArgs& n, int
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int y = yy[k] - n.tab[9], u = ((su[k] + 8) >> 4) - n.tab[10], v = ((sv[k] + 8) >> 4) - n.tab[11];
-    px[k] = yuv_channel(n.tab, 0, y, u, v, depth) | yuv_channel(n.tab, 1, y, u, v, depth) << 8 |
-            yuv_channel(n.tab, 2, y, u, v, depth) << 16;
+    if constexpr (IS_HDR<Y>)
+      px[k] = hdr_pixel(n, y, u, v);
+    else
+      px[k] = yuv_channel(n.tab, 0, y, u, v, depth) | yuv_channel(n.tab, 1, y, u, v, depth) << 8 |
+              yuv_channel(n.tab, 2, y, u, v, depth) << 16;
   }
   store_rgb4(dst, px);
 }
 
-// SrcArgs: what the layout's staging loop reads besides ImgArgs (Nv12Args, PlanarArgs, PackedArgs, YuvArgs or
-// YuvBilinearArgs; the contiguous RGB source is ImgArgs::img and takes an empty Nv12Args). Y: Src::YUV's Yuv<...>.
+// SrcArgs: what the layout's staging loop reads besides ImgArgs (Nv12Args, PlanarArgs, PackedArgs, YuvArgs,
+// YuvBilinearArgs or YuvHdrArgs; the contiguous RGB source is ImgArgs::img and takes an empty Nv12Args). Y: Src::YUV's Yuv<...>.
 template <Src S, class SrcArgs, class Y = NoYuv>
 __device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const SrcArgs& n) {
   constexpr bool GROUPS = S != Src::RGB;
@@ -561,6 +615,13 @@ __global__ __launch_bounds__(256) void image_patch_planes_yuv_bilinear(ImgArgs a
   image_patch_planes_body<Src::YUV, YuvBilinearArgs, Y>(a, n);
 }
 
+// PQ and HLG sources, through the tables: one instantiation per (layout, hsub) of 16-bit samples with nearest chroma,
+// and per layout with bilinear chroma (hsub = 1)
+template <class Y>
+__global__ __launch_bounds__(256) void image_patch_planes_yuv_hdr(ImgArgs a, YuvHdrArgs n) {
+  image_patch_planes_body<Src::YUV, YuvHdrArgs, Hdr<Y>>(a, n);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -738,6 +799,72 @@ int patch_planes_semiplanar(const void* y, const void* y_lo, const void* y_hi, c
                      reinterpret_cast<hipStream_t>(stream), k, n);
   return check(vu ? "image_patch_planes_nv21" : "image_patch_planes_nv12");
 }
+// What both entries of the general YUV front end check and fill: every check of the descriptor and of the common
+// arguments, then the kernel's arguments k and n and the workgroups to launch.
+int yuv_args(const NosYuvSrc* src, ImgArgs& k, int& grid, YuvBilinearArgs& n, void* planes, float* pixels,
+             const int* yidx, const float* ywt, const int* xidx, const float* xwt, int ytab, int xtab, int taps,
+             int max_fh, int max_fw, const float* a, const float* b, int B, int h, int w, int H, int W, int p, int gh,
+             int gw, int wgs) {
+  if (!src) return fail("image_patch_planes: null operand");
+  if (src->size != int(sizeof(NosYuvSrc)))
+    return fail("image_patch_planes_yuv: descriptor size mismatch (NosYuvSrc of another build)");
+  const NosYuvSrc& s = *src;
+  if (const int rc = image_args(k, grid, planes, pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a, b,
+                                B, h, w, H, W, p, gh, gw, wgs))
+    return rc;
+  if (max_fw > YUV_FMAX_W) return fail("image_patch_planes_yuv: a patch's source footprint exceeds 69 columns");
+  // the known combinations
+  const bool packed = s.layout == YUV_PACKED;
+  if (s.layout != YUV_PLANAR && s.layout != YUV_SEMI && !packed)
+    return fail("image_patch_planes_yuv: unknown layout (0 planar, 1 semi-planar, 2 packed 4:2:2)");
+  if (!((s.hsub == 1 && s.vsub == 1) || (s.hsub == 1 && s.vsub == 0) || (s.hsub == 0 && s.vsub == 0)))
+    return fail("image_patch_planes_yuv: unknown subsampling (hsub, vsub): (1, 1), (1, 0) or (0, 0)");
+  if (packed && (s.hsub != 1 || s.vsub != 0 || s.sample_bytes != 1))
+    return fail("image_patch_planes_yuv: packed sources are 4:2:2 with 8-bit samples");
+  if (s.sample_bytes == 1 ? (s.depth != 8 || s.shift != 0)
+                          : (s.sample_bytes != 2 || (s.depth != 10 && s.depth != 12) ||
+                             (s.shift != 0 && s.shift != 16 - s.depth)))
+    return fail("image_patch_planes_yuv: unknown sample format (1 byte: depth 8, shift 0; 2 bytes: depth 10 or 12, "
+                "shift 0 or 16 - depth)");
+  if (s.order < 0 || s.order > (packed ? 2 : s.layout == YUV_SEMI ? 1 : 0))
+    return fail("image_patch_planes_yuv: unknown order (semi-planar 0 UV / 1 VU; packed 0 YUYV / 1 UYVY / 2 YVYU)");
+  if (s.chroma != 0 && s.chroma != 1)
+    return fail("image_patch_planes_yuv: unknown chroma reconstruction (0 nearest, 1 bilinear)");
+  if (s.siting < 0 || s.siting > 3)
+    return fail("image_patch_planes_yuv: unknown chroma siting (bit 0 horizontally, bit 1 vertically co-sited)");
+  if (s.chroma == 1 && s.hsub == 0)
+    return fail("image_patch_planes_yuv: bilinear chroma takes a subsampled source (4:4:4 is launched as nearest)");
+  // rows and row bytes of every plane
+  const long long SB = s.sample_bytes, cw = (w + (1LL << s.hsub) - 1) >> s.hsub, ch = (h + (1LL << s.vsub) - 1) >> s.vsub;
+  const int np = packed ? 1 : s.layout == YUV_SEMI ? 2 : 3;
+  const long long rows[3] = {h, ch, ch};
+  const long long rowbytes[3] = {packed ? 4 * ((w + 1LL) / 2) : w * SB, s.layout == YUV_SEMI ? 2 * cw * SB : cw * SB,
+                                 cw * SB};
+  for (int i = 0; i < np; ++i) {
+    const NosYuvPlane& q = s.plane[i];
+    if (!q.p) return fail("image_patch_planes: null operand");
+    if (q.pitch < rowbytes[i]) return fail("image_patch_planes_yuv: a plane's pitch is smaller than its row's bytes");
+    if (!stride_range(q.pitch, q.bstride)) return fail("image_patch_planes_yuv: pitch or batch stride out of range");
+    if (SB == 2 && ((reinterpret_cast<uintptr_t>(q.p) | uintptr_t(q.pitch) | uintptr_t(q.bstride)) & 1))
+      return fail("image_patch_planes_yuv: 16-bit planes lie at an even address with an even pitch and batch stride");
+    if (!inside(B, q.p, q.lo, q.hi, q.bstride, rows[i], q.pitch, rowbytes[i]))
+      return fail("image_patch_planes_yuv: a plane does not lie inside its storage bounds");
+    n.pl[i] = plane_arg(q.p, q.lo, q.hi, q.pitch, q.bstride);
+  }
+  for (int i = 0; i < 12; ++i) {
+    if (i < 9 ? std::abs(s.tab[i]) >= (1 << 23) : (s.tab[i] < 0 || s.tab[i] >= (1 << s.depth)))
+      return fail("image_patch_planes_yuv: colour table: coefficients below 2^23 in size, offsets below 2^depth");
+    n.tab[i] = s.tab[i];
+  }
+  n.vsub = s.vsub, n.depth = s.depth, n.shift = s.shift, n.mask = (1 << s.depth) - 1, n.order = s.order;
+  // co-sited: (4, 0) of C[i], C[i] at an even position, held as (0, 4) of C[i - 1], C[i], and (2, 2) at an odd one;
+  // centred: (1, 3) and (3, 1)
+  n.cw = int(cw), n.ch = int(ch);
+  static const int cosited[4] = {0, 4, 2, 2}, centred[4] = {1, 3, 3, 1};
+  for (int i = 0; i < 4; ++i)
+    n.wx[i] = (s.siting & 1 ? cosited : centred)[i], n.wy[i] = (s.siting & 2 ? cosited : centred)[i];
+  return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -883,67 +1010,13 @@ int nos_image_patch_planes_yuv(const NosYuvSrc* src, void* planes, float* pixels
                                const int* xidx, const float* xwt, int ytab, int xtab, int taps, int max_fh, int max_fw,
                                const float* a, const float* b, int B, int h, int w, int H, int W, int p, int gh, int gw,
                                int wgs, void* stream) {
-  if (!src) return fail("image_patch_planes: null operand");
-  if (src->size != int(sizeof(NosYuvSrc)))
-    return fail("image_patch_planes_yuv: descriptor size mismatch (NosYuvSrc of another build)");
-  const NosYuvSrc& s = *src;
   ImgArgs k{};
   int grid = 0;
-  if (const int rc = image_args(k, grid, planes, pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a, b,
-                                B, h, w, H, W, p, gh, gw, wgs))
-    return rc;
-  if (max_fw > YUV_FMAX_W) return fail("image_patch_planes_yuv: a patch's source footprint exceeds 69 columns");
-  // the known combinations
-  const bool packed = s.layout == YUV_PACKED;
-  if (s.layout != YUV_PLANAR && s.layout != YUV_SEMI && !packed)
-    return fail("image_patch_planes_yuv: unknown layout (0 planar, 1 semi-planar, 2 packed 4:2:2)");
-  if (!((s.hsub == 1 && s.vsub == 1) || (s.hsub == 1 && s.vsub == 0) || (s.hsub == 0 && s.vsub == 0)))
-    return fail("image_patch_planes_yuv: unknown subsampling (hsub, vsub): (1, 1), (1, 0) or (0, 0)");
-  if (packed && (s.hsub != 1 || s.vsub != 0 || s.sample_bytes != 1))
-    return fail("image_patch_planes_yuv: packed sources are 4:2:2 with 8-bit samples");
-  if (s.sample_bytes == 1 ? (s.depth != 8 || s.shift != 0)
-                          : (s.sample_bytes != 2 || (s.depth != 10 && s.depth != 12) ||
-                             (s.shift != 0 && s.shift != 16 - s.depth)))
-    return fail("image_patch_planes_yuv: unknown sample format (1 byte: depth 8, shift 0; 2 bytes: depth 10 or 12, "
-                "shift 0 or 16 - depth)");
-  if (s.order < 0 || s.order > (packed ? 2 : s.layout == YUV_SEMI ? 1 : 0))
-    return fail("image_patch_planes_yuv: unknown order (semi-planar 0 UV / 1 VU; packed 0 YUYV / 1 UYVY / 2 YVYU)");
-  if (s.chroma != 0 && s.chroma != 1)
-    return fail("image_patch_planes_yuv: unknown chroma reconstruction (0 nearest, 1 bilinear)");
-  if (s.siting < 0 || s.siting > 3)
-    return fail("image_patch_planes_yuv: unknown chroma siting (bit 0 horizontally, bit 1 vertically co-sited)");
-  if (s.chroma == 1 && s.hsub == 0)
-    return fail("image_patch_planes_yuv: bilinear chroma takes a subsampled source (4:4:4 is launched as nearest)");
-  // rows and row bytes of every plane
-  const long long SB = s.sample_bytes, cw = (w + (1LL << s.hsub) - 1) >> s.hsub, ch = (h + (1LL << s.vsub) - 1) >> s.vsub;
-  const int np = packed ? 1 : s.layout == YUV_SEMI ? 2 : 3;
-  const long long rows[3] = {h, ch, ch};
-  const long long rowbytes[3] = {packed ? 4 * ((w + 1LL) / 2) : w * SB, s.layout == YUV_SEMI ? 2 * cw * SB : cw * SB,
-                                 cw * SB};
   YuvBilinearArgs n{};
-  for (int i = 0; i < np; ++i) {
-    const NosYuvPlane& q = s.plane[i];
-    if (!q.p) return fail("image_patch_planes: null operand");
-    if (q.pitch < rowbytes[i]) return fail("image_patch_planes_yuv: a plane's pitch is smaller than its row's bytes");
-    if (!stride_range(q.pitch, q.bstride)) return fail("image_patch_planes_yuv: pitch or batch stride out of range");
-    if (SB == 2 && ((reinterpret_cast<uintptr_t>(q.p) | uintptr_t(q.pitch) | uintptr_t(q.bstride)) & 1))
-      return fail("image_patch_planes_yuv: 16-bit planes lie at an even address with an even pitch and batch stride");
-    if (!inside(B, q.p, q.lo, q.hi, q.bstride, rows[i], q.pitch, rowbytes[i]))
-      return fail("image_patch_planes_yuv: a plane does not lie inside its storage bounds");
-    n.pl[i] = plane_arg(q.p, q.lo, q.hi, q.pitch, q.bstride);
-  }
-  for (int i = 0; i < 12; ++i) {
-    if (i < 9 ? std::abs(s.tab[i]) >= (1 << 23) : (s.tab[i] < 0 || s.tab[i] >= (1 << s.depth)))
-      return fail("image_patch_planes_yuv: colour table: coefficients below 2^23 in size, offsets below 2^depth");
-    n.tab[i] = s.tab[i];
-  }
-  n.vsub = s.vsub, n.depth = s.depth, n.shift = s.shift, n.mask = (1 << s.depth) - 1, n.order = s.order;
-  // co-sited: (4, 0) of C[i], C[i] at an even position, held as (0, 4) of C[i - 1], C[i], and (2, 2) at an odd one;
-  // centred: (1, 3) and (3, 1)
-  n.cw = int(cw), n.ch = int(ch);
-  static const int cosited[4] = {0, 4, 2, 2}, centred[4] = {1, 3, 3, 1};
-  for (int i = 0; i < 4; ++i)
-    n.wx[i] = (s.siting & 1 ? cosited : centred)[i], n.wy[i] = (s.siting & 2 ? cosited : centred)[i];
+  if (const int rc = yuv_args(src, k, grid, n, planes, pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a,
+                              b, B, h, w, H, W, p, gh, gw, wgs))
+    return rc;
+  const NosYuvSrc& s = *src;
   if (s.chroma == 1) {
     // hsub is 1; packed sources have one sample size
     void (*bilinear)(ImgArgs, YuvBilinearArgs) = nullptr;
@@ -971,6 +1044,47 @@ int nos_image_patch_planes_yuv(const NosYuvSrc* src, void* planes, float* pixels
   }
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, YuvArgs(n));
   return check("image_patch_planes_yuv");
+}
+
+// The same of a source whose codes are PQ or HLG, through the tables NosYuvHdr (image_yuv.h) points to: 10 / 12-bit
+// codes in 16-bit words, planar or semi-planar, nearest or bilinear chroma. Every check of nos_image_patch_planes_yuv,
+// then those of the tables; nothing is launched unless all pass.
+int nos_image_patch_planes_yuv_hdr(const NosYuvSrc* src, const NosYuvHdr* hdr, void* planes, float* pixels,
+                                   const int* yidx, const float* ywt, const int* xidx, const float* xwt, int ytab,
+                                   int xtab, int taps, int max_fh, int max_fw, const float* a, const float* b, int B,
+                                   int h, int w, int H, int W, int p, int gh, int gw, int wgs, void* stream) {
+  if (!hdr) return fail("image_patch_planes: null operand");
+  if (hdr->size != int(sizeof(NosYuvHdr)))
+    return fail("image_patch_planes_yuv_hdr: table descriptor size mismatch (NosYuvHdr of another build)");
+  ImgArgs k{};
+  int grid = 0;
+  YuvHdrArgs n{};
+  if (const int rc = yuv_args(src, k, grid, n, planes, pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a,
+                              b, B, h, w, H, W, p, gh, gw, wgs))
+    return rc;
+  const NosYuvSrc& s = *src;
+  if (s.sample_bytes != 2 || s.layout == YUV_PACKED)
+    return fail("image_patch_planes_yuv_hdr: a source of 16-bit samples (depth 10 or 12), planar or semi-planar");
+  if (hdr->entries != 1 << s.depth) return fail("image_patch_planes_yuv_hdr: lut1 has 2^depth entries");
+  if (!hdr->lut1 || !hdr->lut2) return fail("image_patch_planes_yuv_hdr: null table");
+  for (int i = 0; i < 9; ++i) {
+    if (std::abs(hdr->gamut[i]) >= (1 << 15))
+      return fail("image_patch_planes_yuv_hdr: gamut coefficients below 2^15 in size");
+    n.gamut[i] = hdr->gamut[i];
+  }
+  n.lut1 = static_cast<const uint16_t*>(hdr->lut1), n.lut2 = static_cast<const uint8_t*>(hdr->lut2);
+  n.entries = hdr->entries;
+  void (*kern)(ImgArgs, YuvHdrArgs) = nullptr;
+  switch ((s.layout == YUV_SEMI ? 3 : 0) + (s.chroma == 1 ? 2 : s.hsub)) {
+    case 0: kern = image_patch_planes_yuv_hdr<Yuv<YUV_PLANAR, 0, 2>>; break;
+    case 1: kern = image_patch_planes_yuv_hdr<Yuv<YUV_PLANAR, 1, 2>>; break;
+    case 2: kern = image_patch_planes_yuv_hdr<Yuv<YUV_PLANAR, 1, 2, 1>>; break;
+    case 3: kern = image_patch_planes_yuv_hdr<Yuv<YUV_SEMI, 0, 2>>; break;
+    case 4: kern = image_patch_planes_yuv_hdr<Yuv<YUV_SEMI, 1, 2>>; break;
+    default: kern = image_patch_planes_yuv_hdr<Yuv<YUV_SEMI, 1, 2, 1>>; break;
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, n);
+  return check("image_patch_planes_yuv_hdr");
 }
 
 // logits [B][M][C] fp32, boxes [B][M][4] fp32, target [B][2] fp32 (height, width), all on the device ->

@@ -42,6 +42,25 @@ int nos_image_patch_planes_yuv(const NosYuvSrc* src, void* planes, float* pixels
 
 int nos_image_yuv_max_footprint(void);
 
+// The tables of a PQ or HLG source (ops/image.py's hdr_tables, on the device): the source's R'G'B' codes are not cut
+// to 8 bits but taken, at the source's depth, through lut1 (tone-mapped linear light, 16383 = SDR white), the gamut
+// matrix in 2^-12 fixed point, clip((sum + 2048) >> 12, 0, 16383), and lut2 (the sRGB byte). The kernel knows no
+// transfer function. A descriptor of its own: NosYuvSrc is as it was.
+typedef struct NosYuvHdr {
+  int size;          // sizeof(NosYuvHdr): checked first, a mismatch is an error
+  int entries;       // of lut1: 1 << depth of the source
+  const void* lut1;  // uint16 [entries], device memory: values up to 16383
+  const void* lut2;  // uint8 [16384], device memory
+  int gamut[9];      // by rows (R, G, B out) x (R, G, B in), each below 2^15 in size
+} NosYuvHdr;
+
+// nos_image_patch_planes_yuv of such a source: 16-bit samples, planar or semi-planar. Every check of that entry, then
+// those of the tables; nothing is launched unless all pass.
+int nos_image_patch_planes_yuv_hdr(const NosYuvSrc* src, const NosYuvHdr* hdr, void* planes, float* pixels,
+                                   const int* yidx, const float* ywt, const int* xidx, const float* xwt, int ytab,
+                                   int xtab, int taps, int max_fh, int max_fw, const float* a, const float* b, int B,
+                                   int h, int w, int H, int W, int p, int gh, int gw, int wgs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,10 @@ rows at a padded pitch, read in place against ``.contiguous()`` first) are timed
 the surfaces of ``models/workload/surfaces.py``, one name per kernel instantiation (``i422_*``, ``i444_*``,
 ``nv16_*``, ``nv24_*``, ``yuy2_*``, ``p010_*``, ``i010_*``, ``p210_*``, ``i410_*``, ``i012_*``). Four of them
 again with ``chroma="bilinear"`` (``i420_bilinear_*``, ``nv12_bilinear_*``, ``p010_bilinear_*``, ``yuy2_bilinear_*``):
-there (c) interpolates the chroma in torch before the RGB kernel.
+there (c) interpolates the chroma in torch before the RGB kernel. Three more are the 10-bit surfaces as HDR frames
+(BT.2020, peak 1000 nits: ``p010_pq_*``, ``p010_hlg_*``, ``i010_pq_bilinear_*``): (a) the fused launch through the
+tables, (b) the same surface's nearest-chroma ``transfer="sdr"`` fused launch as the floor (``*_sdr_fused_us``), (c)
+the frame's ``rgb()`` in torch on the GPU (table look-ups and the gamut matrix as tensor ops), then the RGB kernel.
 """
 from __future__ import annotations
 
@@ -247,12 +250,12 @@ def image_bench(a) -> int:
         r[f"{name}_torch_us"] = round(statistics.median(t["torch"]), 1)
         r[f"{name}_rounds_us"] = {k: [round(v, 1) for v in vs] for k, vs in t.items()}
 
-    def triple(r, name, out, fused, rgb_only, convert_then_rgb, s, iters):
+    def triple(r, name, out, fused, rgb_only, convert_then_rgb, s, iters, second="rgb_kernel"):
         # five alternations: the spread of (b) within the run is what a difference (a) - (b) is read against
-        t = {"fused": [], "rgb_kernel": [], "convert_then_rgb": []}
+        t = {"fused": [], second: [], "convert_then_rgb": []}
         for _ in range(5):
             t["fused"].append(timeit(fused, s, iters))
-            t["rgb_kernel"].append(timeit(rgb_only, s, iters))
+            t[second].append(timeit(rgb_only, s, iters))
             t["convert_then_rgb"].append(timeit(convert_then_rgb, s, iters))
         r[f"{name}_target_hw"] = list(out)
         for k, vs in t.items():
@@ -297,6 +300,10 @@ def image_bench(a) -> int:
         for fmt, fr in (("i420", fixed["i420"]), ("nv12", frames[f"{h}x{w}"]), ("p010", fixed["p010"]),
                         ("yuy2", fixed["yuy2"])):
             fixed[f"{fmt}_bilinear"] = replace(fr, chroma="bilinear")
+        # PQ and HLG (BT.2020, peak 1000 nits): the 10-bit surfaces again, as HDR frames
+        for key, fmt, kw in (("p010_pq", "p010", {"transfer": "pq"}), ("p010_hlg", "p010", {"transfer": "hlg"}),
+                             ("i010_pq_bilinear", "i010", {"transfer": "pq", "chroma": "bilinear"})):
+            fixed[key] = replace(fixed[fmt], matrix="bt2020", **kw)
     results = []
     for prof, label in (("spx_nps1", "spx"), ("cpx_nps1", "cpx")):
         if label not in a.slices.split(","):
@@ -319,6 +326,14 @@ def image_bench(a) -> int:
                        lambda: I.image_patch_planes(I.nv12_to_rgb(f.y, f.uv), out, 16, IMAGENET_MEAN, IMAGENET_STD),
                        s, a.iters)
                 for layout, fr in layouts[name].items():
+                    if getattr(fr, "transfer", "sdr") != "sdr":
+                        floor = replace(fr, transfer="sdr", chroma="nearest")
+                        triple(r, f"{layout}_{name}", out,
+                               lambda: fr.patch_planes(out, 16, IMAGENET_MEAN, IMAGENET_STD),
+                               lambda: floor.patch_planes(out, 16, IMAGENET_MEAN, IMAGENET_STD),
+                               lambda: I.image_patch_planes(fr.rgb(), out, 16, IMAGENET_MEAN, IMAGENET_STD),
+                               s, a.iters, second="sdr_fused")
+                        continue
                     conv = fr.rgb()
                     triple(r, f"{layout}_{name}", out,
                            lambda: fr.patch_planes(out, 16, IMAGENET_MEAN, IMAGENET_STD),

@@ -23,7 +23,8 @@ half of it); ``bgr``, ``rgba`` and ``bgra`` packed pixels as OpenCV or a composi
 applies to every format (for the packed ones and ``rgb`` it is the bytes between rows of a padded buffer).
 The names of ``models/workload/surfaces.py`` — ``i422``, ``nv16``, ``i444``, ``nv24``, ``yuy2`` / ``uyvy``, a 10-bit
 decoder's ``p010`` / ``p210`` / ``p410``, ``i010`` (``yuv420p10le``) and their 12-bit forms — go the same way, and
-``--matrix bt601|bt709|bt2020`` and ``--full-range`` say how any YUV format's codes are read.
+``--matrix bt601|bt709|bt2020`` and ``--full-range`` say how any YUV format's codes are read, and ``--transfer
+pq|hlg`` (with ``--peak-nits``) that a 10- or 12-bit format's codes are HDR and are tone-mapped to SDR in that launch.
 """
 from __future__ import annotations
 
@@ -70,6 +71,10 @@ SURFACES = ("i422", "yv16", "i444", "yv24", "nv16", "nv61", "nv24", "nv42", "yuy
             "p010", "p012", "p210", "p410", "i010", "i012", "i210", "i410")
 
 
+#: those of them with 10- or 12-bit samples: the ones that take --transfer pq|hlg
+DEEP = tuple(n for n in SURFACES if n[1:] in ("010", "012", "210", "410"))
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser("nos pod client")
     ap.add_argument("--seconds", type=float, default=10.0)
@@ -93,7 +98,17 @@ def main(argv=None) -> int:
     ap.add_argument("--matrix", choices=("bt601", "bt709", "bt2020"), default="bt601",
                     help="--end-to-end: the YUV formats' colour matrix (bt2020 with the surfaces.py formats only)")
     ap.add_argument("--full-range", action="store_true", help="--end-to-end: full-range YUV codes (default: limited)")
+    ap.add_argument("--transfer", choices=("sdr", "pq", "hlg"), default="sdr",
+                    help="--end-to-end: the codes' transfer function; pq and hlg (10- and 12-bit formats only) are "
+                         "tone-mapped to SDR")
+    ap.add_argument("--peak-nits", type=float, default=1000.0,
+                    help="--end-to-end: with --transfer pq|hlg, the luminance that is mapped to SDR white (above 203)")
     args = ap.parse_args(argv)
+    if args.transfer != "sdr" and args.pixel_format not in DEEP:
+        ap.error(f"--transfer {args.transfer} takes a 10- or 12-bit --pixel-format ({', '.join(DEEP)}), "
+                 f"not {args.pixel_format}")
+    if not args.peak_nits > 203.0:
+        ap.error(f"--peak-nits {args.peak_nits:g} must exceed 203, the reference white")
     t_boot = time.perf_counter()
     import torch
 
@@ -120,7 +135,8 @@ def main(argv=None) -> int:
                 ap.error(f"--pitch {pitch} is smaller than a row of {iw} {fmt} pixels ({row} bytes)")
             # luma rows, then at most twice as many bytes of chroma (4:4:4)
             buf = torch.randint(0, 256, (3 * pitch * ih,), generator=gen, dtype=torch.uint8).to(dev)
-            img = surfaces.from_buffer(fmt, buf, ih, iw, pitch, matrix=args.matrix, full_range=args.full_range)
+            img = surfaces.from_buffer(fmt, buf, ih, iw, pitch, matrix=args.matrix, full_range=args.full_range,
+                                       transfer=args.transfer, peak_nits=args.peak_nits)
         elif fmt in ("nv12", "nv21", "i420", "yv12"):
             if args.matrix == "bt2020":
                 ap.error(f"--matrix bt2020 is not offered for {fmt}")
@@ -209,6 +225,7 @@ def main(argv=None) -> int:
         out["end_to_end"] = True
         out["input_hw"] = list(hw)
         out["pixel_format"] = args.pixel_format
+        out["transfer"] = args.transfer
         out["detections"] = int(res["count"].sum().item())   # of the last inference
     if census is not None:
         out["census"] = census

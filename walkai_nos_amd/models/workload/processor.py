@@ -96,12 +96,14 @@ class Nv12(Frame):
     vu: bool = False
     chroma: str = "nearest"
     siting: str = "left"
+    transfer: str = "sdr"       # 8-bit samples: the only one (the field is there to refuse the others by name)
     PLANES = ("y", "uv")
 
     def __post_init__(self):
         I.nv12_planes(self.y, self.uv)
         I.nv12_table(self.matrix, self.full_range)
         I._chroma_check(self.chroma, self.siting)
+        I._transfer_check(self.transfer, 1000.0, 8)
 
     @classmethod
     def from_buffer(cls, buf: Any, h: int, w: int, pitch: Optional[int] = None, matrix: str = "bt601",
@@ -164,12 +166,14 @@ class Yuv420p(Frame):
     full_range: bool = False
     chroma: str = "nearest"
     siting: str = "left"
+    transfer: str = "sdr"       # 8-bit samples: the only one (the field is there to refuse the others by name)
     PLANES = ("y", "u", "v")
 
     def __post_init__(self):
         I.yuv420_planes(self.y, self.u, self.v)
         I.nv12_table(self.matrix, self.full_range)
         I._chroma_check(self.chroma, self.siting)
+        I._transfer_check(self.transfer, 1000.0, 8)
 
     @classmethod
     def from_buffer(cls, buf: Any, h: int, w: int, pitch: Optional[int] = None, chroma_pitch: Optional[int] = None,

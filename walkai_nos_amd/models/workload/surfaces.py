@@ -26,9 +26,15 @@ top       centred     co-sited
 
 On 4:2:2 only the horizontal part applies; on 4:4:4 bilinear is nearest.
 
-Not offered: the bottom sitings; bicubic or Lanczos chroma; HDR transfer functions (PQ / HLG code values are converted
-as if SDR, without tone mapping); 16-bit-deep samples; Y210 / Y410 / AYUV; big-endian samples; BT.2020 constant
-luminance; batches above one on the fused model path and mixed sizes in one call.
+A 10 / 12-bit planar or semi-planar frame whose codes are PQ (HDR10) or HLG says ``transfer="pq"`` or ``"hlg"`` and,
+if it knows it, the stream's ``peak_nits`` (default 1000): its R'G'B' codes are then not cut to 8 bits but tone-mapped
+to sRGB bytes — transfer function, an extended Reinhard curve per channel from that peak to SDR white (203 nits in),
+BT.2020 to BT.709 primaries, the sRGB OETF — by two tables and an integer matrix (``ops.image.hdr_tables``), still
+inside the one launch. The default, ``"sdr"``, reads the codes as they are.
+
+Not offered: the bottom sitings; bicubic or Lanczos chroma; luminance-based or BT.2390 tone mapping; dynamic metadata
+(HDR10+, Dolby Vision); 8-bit HLG; linear or float surfaces; 16-bit-deep samples; Y210 / Y410 / AYUV; big-endian
+samples; BT.2020 constant luminance; batches above one on the fused model path and mixed sizes in one call.
 """
 from __future__ import annotations
 
@@ -58,12 +64,15 @@ class YuvPlanar(Frame):
     full_range: bool = False
     chroma: str = "nearest"
     siting: str = "left"
+    transfer: str = "sdr"
+    peak_nits: float = 1000.0
     PLANES = ("y", "u", "v")
 
     def __post_init__(self):
         I.yuv_planes(self.y, self.u, self.v, self.subsampling, self.depth)
         I.yuv_table(self.matrix, self.full_range, self.depth)
         I._chroma_check(self.chroma, self.siting)
+        I._transfer_check(self.transfer, self.peak_nits, self.depth)
 
     @property
     def shape(self) -> Tuple[int, int, int, int]:
@@ -72,11 +81,12 @@ class YuvPlanar(Frame):
     def rgb(self) -> torch.Tensor:
         """The frame converted: uint8 ``[B, h, w, 3]`` (``ops.image.yuv_to_rgb``)."""
         return I.yuv_to_rgb(self.y, self.u, self.v, self.subsampling, self.depth, self.msb, self.matrix,
-                            self.full_range, self.chroma, self.siting)
+                            self.full_range, self.chroma, self.siting, self.transfer, self.peak_nits)
 
     def patch_planes(self, hw, patch, mean, std, want_pixels=False):
         return I.yuv_planar_patch_planes(self.y, self.u, self.v, hw, patch, mean, std, self.subsampling, self.depth,
-                                         self.msb, self.matrix, self.full_range, want_pixels, self.chroma, self.siting)
+                                         self.msb, self.matrix, self.full_range, want_pixels, self.chroma, self.siting,
+                                         self.transfer, self.peak_nits)
 
 
 @dataclass(frozen=True)
@@ -93,12 +103,15 @@ class YuvSemiPlanar(Frame):
     vu: bool = False
     chroma: str = "nearest"
     siting: str = "left"
+    transfer: str = "sdr"
+    peak_nits: float = 1000.0
     PLANES = ("y", "uv")
 
     def __post_init__(self):
         I.yuv_semiplanar_planes(self.y, self.uv, self.subsampling, self.depth)
         I.yuv_table(self.matrix, self.full_range, self.depth)
         I._chroma_check(self.chroma, self.siting)
+        I._transfer_check(self.transfer, self.peak_nits, self.depth)
 
     @property
     def shape(self) -> Tuple[int, int, int, int]:
@@ -107,12 +120,13 @@ class YuvSemiPlanar(Frame):
     def rgb(self) -> torch.Tensor:
         """The frame converted: uint8 ``[B, h, w, 3]`` (``ops.image.yuv_semiplanar_to_rgb``)."""
         return I.yuv_semiplanar_to_rgb(self.y, self.uv, self.subsampling, self.depth, self.msb, self.matrix,
-                                       self.full_range, self.vu, self.chroma, self.siting)
+                                       self.full_range, self.vu, self.chroma, self.siting, self.transfer,
+                                       self.peak_nits)
 
     def patch_planes(self, hw, patch, mean, std, want_pixels=False):
         return I.yuv_semiplanar_patch_planes(self.y, self.uv, hw, patch, mean, std, self.subsampling, self.depth,
                                              self.msb, self.matrix, self.full_range, want_pixels, self.vu, self.chroma,
-                                             self.siting)
+                                             self.siting, self.transfer, self.peak_nits)
 
 
 @dataclass(frozen=True)
@@ -127,12 +141,14 @@ class Yuyv(Frame):
     full_range: bool = False
     chroma: str = "nearest"
     siting: str = "left"
+    transfer: str = "sdr"       # 8-bit samples: the only one (the field is there to refuse the others by name)
     PLANES = ("data",)
 
     def __post_init__(self):
         I.yuyv_planes(self.data, self.width, self.order)
         I.yuv_table(self.matrix, self.full_range, 8)
         I._chroma_check(self.chroma, self.siting)
+        I._transfer_check(self.transfer, 1000.0, 8)
 
     @property
     def shape(self) -> Tuple[int, int, int, int]:
@@ -165,7 +181,7 @@ _YUYV = {"yuy2": "yuyv", "uyvy": "uyvy", "yvyu": "yvyu"}
 
 def from_buffer(name: str, buf: Any, h: int, w: int, pitch: Optional[int] = None, chroma_pitch: Optional[int] = None,
                 matrix: str = "bt601", full_range: bool = False, chroma: str = "nearest",
-                siting: str = "left") -> Frame:
+                siting: str = "left", transfer: str = "sdr", peak_nits: float = 1000.0) -> Frame:
     """A decoder's or a capture card's single buffer as a frame of format ``name`` (:data:`FORMATS`), without a
     copy. ``buf``: a contiguous uint8 tensor or ndarray that holds all of it. Pitches are in bytes.
 
@@ -179,11 +195,13 @@ def from_buffer(name: str, buf: Any, h: int, w: int, pitch: Optional[int] = None
       buffer starts at an even byte and both pitches are even; the planes come out as ``torch.uint16`` views.
 
     ``chroma`` and ``siting``: how the frame's chroma is brought to the luma grid (``ops.image.CHROMA`` and
-    ``SITINGS``)."""
+    ``SITINGS``). ``transfer`` (``ops.image.TRANSFERS``) and ``peak_nits``: a 10 / 12-bit format's codes are PQ or HLG
+    and are tone-mapped to SDR from that peak."""
     who = f"from_buffer({name!r})"
     if name not in FORMATS:
         raise ValueError(f"{who}: an unknown format; one of {sorted(FORMATS)}")
     layout, sub, depth, msb, swap = FORMATS[name]
+    I._transfer_check(transfer, peak_nits, depth)
     t = torch.from_numpy(buf) if isinstance(buf, np.ndarray) else buf
     if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous():
         raise ValueError(f"{who}: a contiguous uint8 tensor or ndarray")
@@ -239,7 +257,7 @@ def from_buffer(name: str, buf: Any, h: int, w: int, pitch: Optional[int] = None
     y = plane(0, h, w, pitch)
     if layout == "semiplanar":
         return YuvSemiPlanar(y, plane(h * pitch, ch, cw, cpitch, (2,)), sub, depth, msb, matrix, full_range, swap,
-                             chroma, siting)
+                             chroma, siting, transfer, peak_nits)
     first, second = plane(h * pitch, ch, cw, cpitch), plane(h * pitch + ch * cpitch, ch, cw, cpitch)
     u, v = (second, first) if swap else (first, second)
-    return YuvPlanar(y, u, v, sub, depth, msb, matrix, full_range, chroma, siting)
+    return YuvPlanar(y, u, v, sub, depth, msb, matrix, full_range, chroma, siting, transfer, peak_nits)

@@ -36,8 +36,14 @@ is rounded to uint8 between the two passes, so pixels differ from it by less tha
   :func:`yuyv_patch_planes` — the rest of the YUV front end behind one launch descriptor (:class:`NosYuvSrc`):
   4:2:2 and 4:4:4 beside 4:2:0, packed 4:2:2 (YUY2 / UYVY / YVYU), and 10 / 12-bit codes in 16-bit words (P010's
   high bits or ``yuv420p10le``'s low bits; the other bits are ignored), with BT.2020 (non-constant luminance)
-  beside the two older matrices (:func:`yuv_table`). PQ / HLG code values are converted as if SDR (no transfer
-  function, no tone mapping); 16-bit-deep samples, Y210 / Y410 / AYUV and big-endian words are not offered.
+  beside the two older matrices (:func:`yuv_table`). 16-bit-deep samples, Y210 / Y410 / AYUV and big-endian words
+  are not offered.
+* :func:`hdr_tables` / :func:`hdr_to_sdr` — ``transfer="pq"`` or ``"hlg"`` (:data:`TRANSFERS`) on a 10 / 12-bit planar
+  or semi-planar frame: the R'G'B' codes at the source's depth go through a table (transfer function and an extended
+  Reinhard curve from ``peak_nits`` to SDR white, per channel), a 3 x 3 integer gamut matrix (BT.2020 to BT.709
+  primaries) and a second table (the sRGB OETF), all built in fp64 on the host and cached on the device; the kernel's
+  staging loop knows only the tables. The default stays ``"sdr"``. Luminance-based or BT.2390 tone mapping, dynamic
+  metadata, 8-bit HLG and linear or float surfaces are not offered.
 * :func:`chroma_upsample` — ``chroma="bilinear", siting=...`` on every ``*_to_rgb`` and on the general entry's
   ``*_patch_planes``: chroma interpolated as decoders and scalers do, honouring where the stream's chroma samples
   lie (:data:`SITINGS`: ``left``, ``center``, ``topleft``, ``top``), in exact integers — two taps per subsampled
@@ -106,6 +112,8 @@ def _L() -> ctypes.CDLL:
             L.nos_image_patch_planes_packed.argtypes = [vp, vp, vp, i64, i64, ctypes.c_char_p] + \
                 L.nos_image_patch_planes_u8.argtypes[1:]
             L.nos_image_patch_planes_yuv.argtypes = [ctypes.POINTER(NosYuvSrc)] + \
+                L.nos_image_patch_planes_u8.argtypes[1:]
+            L.nos_image_patch_planes_yuv_hdr.argtypes = [ctypes.POINTER(NosYuvSrc), ctypes.POINTER(NosYuvHdr)] + \
                 L.nos_image_patch_planes_u8.argtypes[1:]
             L.nos_detections_f32.argtypes = [vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, vp, vp]
             L.nos_image_last_error.restype = ctypes.c_char_p
@@ -213,8 +221,9 @@ _tables = GraphCache(16)
 
 
 def invalidate_cache() -> None:
-    """Drop every cached tap table, also those a captured graph holds: capture such graphs again."""
+    """Drop every cached tap table and HDR table, also those a captured graph holds: capture such graphs again."""
     _tables.clear()
+    _hdr_tables.clear()
 
 
 def _make_tables(h: int, w: int, H: int, W: int, p: int, device: torch.device) -> Optional[tuple]:
@@ -705,18 +714,170 @@ def yuv_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, subsampling: s
     return y, u, v
 
 
+# ---- PQ and HLG frames, tone-mapped to SDR ----------------------------------------------------------
+#: how a frame's R'G'B' codes are read: ``sdr`` — cut to 8 bits, as they are — or an HDR transfer function of a 10 /
+#: 12-bit frame, ``pq`` (SMPTE ST 2084, HDR10) or ``hlg`` (BT.2100), tone-mapped to sRGB bytes (:func:`hdr_tables`)
+TRANSFERS = ("sdr", "pq", "hlg")
+#: linear light in ``lut1`` and behind the gamut matrix: SDR white; ``lut2`` has one entry more
+HDR_WHITE = 16383
+#: BT.2408's reference white in nits: what SDR white is mapped from
+HDR_REFERENCE_WHITE = 203.0
+#: the gamut matrix is in 2^-12 fixed point
+HDR_GAMUT_ONE = 4096
+#: CIE xy of the red, green and blue primaries; both sets have D65 as white
+_PRIMARIES = {"bt709": ((0.640, 0.330), (0.300, 0.600), (0.150, 0.060)),
+              "bt2020": ((0.708, 0.292), (0.170, 0.797), (0.131, 0.046))}
+_D65 = (0.3127, 0.3290)
+
+
+def _transfer_check(transfer: str, peak_nits: float, depth: int) -> None:
+    if transfer not in TRANSFERS:
+        raise ValueError(f"yuv: transfer {transfer!r} is none of {TRANSFERS}")
+    if not float(peak_nits) > HDR_REFERENCE_WHITE:
+        raise ValueError(f"yuv: peak_nits {peak_nits!r} must exceed the reference white, {HDR_REFERENCE_WHITE:g} nits")
+    if transfer != "sdr" and depth not in (10, 12):
+        raise ValueError(f"yuv: transfer {transfer!r} takes a frame of depth 10 or 12, not {depth!r} "
+                         "(8-bit and packed sources are read as sdr)")
+
+
+def _rgb_to_xyz(primaries: str) -> np.ndarray:
+    """Linear RGB of a set of primaries to CIE XYZ, white D65 at Y = 1, in fp64."""
+    m = np.array([[x / y, 1.0, (1.0 - x - y) / y] for x, y in _PRIMARIES[primaries]], dtype=np.float64).T
+    white = np.array([_D65[0] / _D65[1], 1.0, (1.0 - _D65[0] - _D65[1]) / _D65[1]], dtype=np.float64)
+    return m * np.linalg.solve(m, white)[None, :]
+
+
+def hdr_gamut(matrix: str) -> np.ndarray:
+    """The gamut step of :func:`hdr_to_sdr` as int32 ``[3, 3]`` in 2^-12 fixed point: BT.2020 to BT.709 primaries
+    in linear light for ``matrix == "bt2020"`` — derived in fp64 from the two sets of primaries and D65, rounded —
+    else ``4096 I`` (a BT.601 / BT.709 stream is taken to be in BT.709 primaries). Every row sums to 4096."""
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"yuv: matrix {matrix!r} is none of {sorted(YUV_MATRICES)}")
+    if matrix != "bt2020":
+        return np.eye(3, dtype=np.int32) * HDR_GAMUT_ONE
+    m = np.linalg.solve(_rgb_to_xyz("bt709"), _rgb_to_xyz("bt2020"))
+    return np.rint(m * HDR_GAMUT_ONE).astype(np.int32)
+
+
+def hdr_nits(transfer: str, e: np.ndarray) -> np.ndarray:
+    """Display light in nits of the non-linear signal ``e`` in 0..1, fp64. ``pq``: the ST 2084 EOTF. ``hlg``: BT.2100's
+    inverse OETF and the OOTF per component, gamma 1.2, for a 1000-nit display."""
+    e = np.asarray(e, dtype=np.float64)
+    if transfer == "pq":
+        m1, m2 = 2610.0 / 16384.0, 2523.0 / 4096.0 * 128.0
+        c1, c2, c3 = 3424.0 / 4096.0, 2413.0 / 4096.0 * 32.0, 2392.0 / 4096.0 * 32.0
+        p = e ** (1.0 / m2)
+        return 10000.0 * (np.maximum(p - c1, 0.0) / (c2 - c3 * p)) ** (1.0 / m1)
+    if transfer == "hlg":
+        a = 0.17883277
+        b, c = 1.0 - 4.0 * a, 0.5 - a * np.log(4.0 * a)
+        scene = np.where(e <= 0.5, e * e / 3.0, (np.exp((e - c) / a) + b) / 12.0)
+        return 1000.0 * scene ** 1.2
+    raise ValueError(f"yuv: transfer {transfer!r} has no light of its own (one of {TRANSFERS[1:]})")
+
+
+def hdr_tone_map(nits: np.ndarray, peak_nits: float = 1000.0) -> np.ndarray:
+    """The extended Reinhard curve on nits, fp64: ``x = N / 203``, ``p = peak_nits / 203``, ``clip(x (1 + x / p^2) /
+    (1 + x), 0, 1)`` — 1 is SDR white, reached at ``peak_nits``."""
+    x, p = np.asarray(nits, dtype=np.float64) / HDR_REFERENCE_WHITE, float(peak_nits) / HDR_REFERENCE_WHITE
+    return np.clip(x * (1.0 + x / (p * p)) / (1.0 + x), 0.0, 1.0)
+
+
+_hdr_host: dict = {}
+
+
+def hdr_tables(transfer: str, depth: int, matrix: str, peak_nits: float = 1000.0) \
+        -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``(lut1, gamut, lut2)``: everything :func:`hdr_to_sdr` and the kernel know of an HDR transfer, built in fp64.
+
+    * ``lut1`` uint16 ``[2^depth]``: code ``k`` of an R'G'B' channel at the source's depth stands for ``E' = min(k /
+      (255 * 2^(depth-8)), 1)``; ``lut1[k] = rint(16383 T(N(E')))`` is its tone-mapped linear light, 16383 = SDR
+      white (:func:`hdr_nits`, :func:`hdr_tone_map`).
+    * ``gamut`` int32 ``[3, 3]``: :func:`hdr_gamut`.
+    * ``lut2`` uint8 ``[16384]``: ``rint(255 sRGB_OETF(s / 16383))`` by IEC 61966-2-1.
+
+    Tone mapping is per channel, in the source's primaries, before the gamut step. The arrays are shared and
+    read-only."""
+    _transfer_check(transfer, peak_nits, depth)
+    if transfer == "sdr":
+        raise ValueError("yuv: transfer 'sdr' has no tables (the codes are cut to 8 bits as they are)")
+    key = (transfer, int(depth), matrix, float(peak_nits))
+    hit = _hdr_host.get(key)
+    if hit is None:
+        gamut = hdr_gamut(matrix)
+        e = np.minimum(np.arange(1 << depth, dtype=np.float64) / (255.0 * (1 << (depth - 8))), 1.0)
+        lut1 = np.rint(HDR_WHITE * hdr_tone_map(hdr_nits(transfer, e), peak_nits)).astype(np.uint16)
+        lin = np.arange(HDR_WHITE + 1, dtype=np.float64) / HDR_WHITE
+        srgb = np.where(lin < 0.0031308, 12.92 * lin, 1.055 * lin ** (1.0 / 2.4) - 0.055)
+        lut2 = np.rint(255.0 * srgb).astype(np.uint8)
+        for t in (lut1, gamut, lut2):
+            t.setflags(write=False)
+        if len(_hdr_host) >= 16:
+            _hdr_host.pop(next(iter(_hdr_host)))
+        hit = _hdr_host[key] = (lut1, gamut, lut2)
+    return hit
+
+
+def _hdr_lut(t, device: torch.device) -> torch.Tensor:
+    """A table as a tensor on ``device`` (an ndarray is widened to int32 first: no uint16 arithmetic in torch)."""
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(t.astype(np.int32))
+    return t.to(device)
+
+
+def hdr_to_sdr(codes: torch.Tensor, tables: Sequence) -> torch.Tensor:
+    """Steps 2 to 4 of the HDR conversion on int32 R'G'B' codes ``[..., 3]`` of the source's depth, in exact
+    integers: ``l_j = lut1[k_j]``, ``s_c = clip((sum_j gamut[c][j] l_j + 2048) >> 12, 0, 16383)``, ``lut2[s_c]`` —
+    uint8 sRGB ``[..., 3]``. ``tables``: :func:`hdr_tables`' result (the tables as ndarrays, or as integer tensors on
+    the codes' device, the gamut's nine integers by rows or flat). Operands fit 24-bit multiplies (below 2^15 and 2^14) and the sums stay below 2^29."""
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.int32 or codes.dim() < 1 or codes.shape[-1] != 3:
+        raise ValueError("hdr_to_sdr: int32 codes [..., 3]")
+    lut1, gamut, lut2 = tables
+    lut1, lut2 = _hdr_lut(lut1, codes.device), _hdr_lut(lut2, codes.device)
+    g = np.asarray(gamut, dtype=np.int64).reshape(3, 3).tolist()    # nine integers, by rows or flat
+    light = lut1[codes.clamp(0, lut1.numel() - 1).long()].to(torch.int32)
+    out = [((g[c][0] * light[..., 0] + g[c][1] * light[..., 1] + g[c][2] * light[..., 2] + HDR_GAMUT_ONE // 2) >> 12)
+           .clamp_(0, HDR_WHITE) for c in range(3)]
+    return lut2[torch.stack(out, dim=-1).long()].to(torch.uint8)
+
+
+#: the device copies of the HDR tables per ``(transfer, depth, matrix, peak_nits, device)``: as the tap tables, a
+#: launch recorded in a graph reads them by address, so an entry handed out under capture stays until
+#: :func:`invalidate_cache` (34 to 40 KB each)
+_hdr_tables = GraphCache(8)
+
+
+def _make_hdr_tables(transfer: str, depth: int, matrix: str, peak_nits: float, device: torch.device) -> tuple:
+    lut1, gamut, lut2 = hdr_tables(transfer, depth, matrix, peak_nits)
+    # (16383 fits int16, which torch handles everywhere: the same bits the kernel reads as uint16)
+    return (torch.from_numpy(lut1.astype(np.int16)).to(device), tuple(int(c) for c in gamut.reshape(-1)),
+            torch.from_numpy(lut2.copy()).to(device))
+
+
+def _hdr_device_tables(transfer: str, depth: int, matrix: str, peak_nits: float, device: torch.device) -> tuple:
+    """``(lut1 int16 [2^depth], gamut (9 integers), lut2 uint8 [16384])`` with the tables on ``device``, cached
+    (:data:`_hdr_tables`)."""
+    key = (transfer, int(depth), matrix, float(peak_nits), str(device))
+    return _hdr_tables.get(key, lambda: _make_hdr_tables(transfer, depth, matrix, peak_nits, device))
+
+
 def yuv_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, subsampling: str = "420", depth: int = 8,
                msb: bool = False, matrix: str = "bt601", full_range: bool = False, chroma: str = "nearest",
-               siting: str = "left") -> torch.Tensor:
+               siting: str = "left", transfer: str = "sdr", peak_nits: float = 1000.0) -> torch.Tensor:
     """A planar frame of any of the three chroma geometries and sample depths as interleaved RGB, uint8 ``[B, h,
     w, 3]``: the definition of the conversion (and what runs on the CPU, with the ``torch`` backend and past the
     kernel's limits). Nearest chroma — luma ``(r, c)`` takes chroma ``(r >> vs, c >> hs)`` — and exact int32
     arithmetic on :func:`yuv_table`. For ``"420"`` at depth 8 it equals :func:`yuv420_to_rgb`. With
     ``chroma="bilinear"`` the chroma codes are :func:`chroma_upsample`'s at ``siting`` instead (codes of the same
-    depth, so the table arithmetic is the same and as far from overflow); on ``"444"`` that is nearest."""
+    depth, so the table arithmetic is the same and as far from overflow); on ``"444"`` that is nearest.
+
+    ``transfer="pq"`` or ``"hlg"`` (depth 10 or 12): the colour matrix's sums are not cut to 8 bits but to codes of
+    the source's depth, ``k_c = clip(sum + 2^15, 0, 2^(16+depth) - 1) >> 16`` — the 8-bit value times ``2^(depth-8)``
+    — which go through :func:`hdr_to_sdr` on :func:`hdr_tables` ``(transfer, depth, matrix, peak_nits)``."""
     y, u, v = yuv_planes(y, u, v, subsampling, depth, any_strides=True)
     t = yuv_table(matrix, full_range, depth)
     _chroma_check(chroma, siting)
+    _transfer_check(transfer, peak_nits, depth)
     hs, vs = YUV_SUBSAMPLING[subsampling]
     h, w = y.shape[1:]
     rows, cols = torch.arange(h, device=y.device) >> vs, torch.arange(w, device=y.device) >> hs
@@ -728,6 +889,13 @@ def yuv_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, subsampling: s
     else:
         uu = yuv_codes(u, depth, msb)[:, rows][:, :, cols] - t[10]
         vv = yuv_codes(v, depth, msb)[:, rows][:, :, cols] - t[11]
+    if transfer != "sdr":
+        # the same sums plus 2^15: still below 5.82e8
+        codes = [(t[3 * k] * yy + t[3 * k + 1] * uu + t[3 * k + 2] * vv + 32768).clamp_(0, (1 << (16 + depth)) - 1) >> 16
+                 for k in range(3)]
+        tables = _hdr_device_tables(transfer, depth, matrix, peak_nits, y.device) if y.is_cuda else \
+            hdr_tables(transfer, depth, matrix, peak_nits)
+        return hdr_to_sdr(torch.stack(codes, dim=-1), tables)
     out = [(t[3 * k] * yy + t[3 * k + 1] * uu + t[3 * k + 2] * vv + (1 << (7 + depth))) >> (8 + depth)
            for k in range(3)]
     return torch.stack(out, dim=-1).clamp_(0, 255).to(torch.uint8)
@@ -776,12 +944,13 @@ def yuyv_to_rgb(data: torch.Tensor, width: int, order: str = "yuyv", matrix: str
 
 def yuv_semiplanar_to_rgb(y: torch.Tensor, uv: torch.Tensor, subsampling: str = "420", depth: int = 8,
                           msb: bool = False, matrix: str = "bt601", full_range: bool = False,
-                          vu: bool = False, chroma: str = "nearest", siting: str = "left") -> torch.Tensor:
+                          vu: bool = False, chroma: str = "nearest", siting: str = "left", transfer: str = "sdr",
+                          peak_nits: float = 1000.0) -> torch.Tensor:
     """A semi-planar frame as interleaved RGB: :func:`yuv_to_rgb` of its de-interleaved planes (``vu``: the pairs
     are (V, U))."""
     y, uv = yuv_semiplanar_planes(y, uv, subsampling, depth)
     return yuv_to_rgb(y, uv[..., 1 if vu else 0], uv[..., 0 if vu else 1], subsampling, depth, msb, matrix, full_range,
-                      chroma, siting)
+                      chroma, siting, transfer, peak_nits)
 
 
 class NosYuvPlane(ctypes.Structure):
@@ -796,6 +965,13 @@ class NosYuvSrc(ctypes.Structure):
                 ("sample_bytes", ctypes.c_int), ("depth", ctypes.c_int), ("shift", ctypes.c_int),
                 ("order", ctypes.c_int), ("plane", NosYuvPlane * 3), ("tab", ctypes.c_int * 12),
                 ("chroma", ctypes.c_int), ("siting", ctypes.c_int)]
+
+
+class NosYuvHdr(ctypes.Structure):
+    """The HDR entry's tables (``csrc/image_yuv.h``, field for field): device pointers to ``lut1`` (uint16 ``[entries]``)
+    and ``lut2`` (uint8 ``[16384]``), and the gamut matrix by rows."""
+    _fields_ = [("size", ctypes.c_int), ("entries", ctypes.c_int), ("lut1", ctypes.c_void_p),
+                ("lut2", ctypes.c_void_p), ("gamut", ctypes.c_int * 9)]
 
 
 YUV_PLANAR, YUV_SEMIPLANAR, YUV_PACKED = 0, 1, 2
@@ -830,11 +1006,23 @@ def _yuv_fused(first: torch.Tensor, hw: Tuple[int, int], out_hw: Tuple[int, int]
     return None if tabs is None or tabs[5] > YUV_MAX_FOOTPRINT else tabs
 
 
+def yuv_hdr(lut1: torch.Tensor, gamut: Sequence[int], lut2: torch.Tensor) -> NosYuvHdr:
+    """The descriptor of HDR tables on the device (:func:`_hdr_device_tables`' three)."""
+    return NosYuvHdr(size=ctypes.sizeof(NosYuvHdr), entries=lut1.numel(), lut1=lut1.data_ptr(), lut2=lut2.data_ptr(),
+                     gamut=(ctypes.c_int * 9)(*gamut))
+
+
 def _yuv_launch(src: NosYuvSrc, tabs: tuple, B: int, h: int, w: int, H: int, W: int, patch: int, mean, std,
-                want_pixels: bool, device: torch.device, what: str):
+                want_pixels: bool, device: torch.device, what: str, hdr: Optional[tuple] = None):
+    """``hdr``: ``(transfer, depth, matrix, peak_nits)`` of a frame that is not ``sdr``; its launch reads the cached
+    device tables."""
     planes, pixels, gh, gw = _outputs(B, H, W, patch, want_pixels, device)
-    rc = _L().nos_image_patch_planes_yuv(ctypes.byref(src),
-                                         *_tail_args(tabs, planes, pixels, mean, std, B, h, w, H, W, patch, gh, gw))
+    tail = _tail_args(tabs, planes, pixels, mean, std, B, h, w, H, W, patch, gh, gw)
+    if hdr is None:
+        rc = _L().nos_image_patch_planes_yuv(ctypes.byref(src), *tail)
+    else:
+        rc = _L().nos_image_patch_planes_yuv_hdr(ctypes.byref(src),
+                                                 ctypes.byref(yuv_hdr(*_hdr_device_tables(*hdr, device))), *tail)
     _check(rc, what)
     return planes, pixels
 
@@ -842,47 +1030,54 @@ def _yuv_launch(src: NosYuvSrc, tabs: tuple, B: int, h: int, w: int, H: int, W: 
 def yuv_planar_patch_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, out_hw: Tuple[int, int], patch: int,
                             mean: Sequence[float], std: Sequence[float], subsampling: str = "420", depth: int = 8,
                             msb: bool = False, matrix: str = "bt601", full_range: bool = False,
-                            want_pixels: bool = False, chroma: str = "nearest", siting: str = "left") \
+                            want_pixels: bool = False, chroma: str = "nearest", siting: str = "left",
+                            transfer: str = "sdr", peak_nits: float = 1000.0) \
         -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """:func:`image_patch_planes` of a planar frame (:func:`yuv_planes`' layout: I422, I444, I010, ``yuv422p10le``
     ...), bit-equal to ``image_patch_planes(yuv_to_rgb(y, u, v, subsampling, depth, msb, matrix, full_range, chroma,
     siting), ...)`` — which is what runs on a CPU tensor, with the ``torch`` backend and past the kernel's limits.
     On the GPU one HIP launch reads the three planes in place, each by its own strides; with ``chroma="bilinear"``
-    it interpolates the chroma at ``siting`` (:func:`chroma_upsample`) while it stages them."""
+    it interpolates the chroma at ``siting`` (:func:`chroma_upsample`) while it stages them, and with ``transfer``
+    ``"pq"`` or ``"hlg"`` it takes the codes through the HDR tables (:func:`hdr_to_sdr`) there as well."""
     y, u, v = yuv_planes(y, u, v, subsampling, depth)
     table = yuv_table(matrix, full_range, depth)
     _chroma_check(chroma, siting)
+    _transfer_check(transfer, peak_nits, depth)
     B, h, w = y.shape
     H, W = int(out_hw[0]), int(out_hw[1])
     tabs = _yuv_fused(y, (h, w), (H, W), patch)
     if tabs is None:
-        return image_patch_planes(yuv_to_rgb(y, u, v, subsampling, depth, msb, matrix, full_range, chroma, siting),
-                                  (H, W), patch, mean, std, want_pixels)
+        return image_patch_planes(yuv_to_rgb(y, u, v, subsampling, depth, msb, matrix, full_range, chroma, siting,
+                                             transfer, peak_nits), (H, W), patch, mean, std, want_pixels)
     src = yuv_src(YUV_PLANAR, (y, u, v), subsampling, depth, msb, 0, table, chroma, siting)
-    return _yuv_launch(src, tabs, B, h, w, H, W, patch, mean, std, want_pixels, y.device, "yuv_planar_patch_planes")
+    return _yuv_launch(src, tabs, B, h, w, H, W, patch, mean, std, want_pixels, y.device, "yuv_planar_patch_planes",
+                       None if transfer == "sdr" else (transfer, depth, matrix, peak_nits))
 
 
 def yuv_semiplanar_patch_planes(y: torch.Tensor, uv: torch.Tensor, out_hw: Tuple[int, int], patch: int,
                                 mean: Sequence[float], std: Sequence[float], subsampling: str = "420", depth: int = 8,
                                 msb: bool = False, matrix: str = "bt601", full_range: bool = False,
                                 want_pixels: bool = False, vu: bool = False, chroma: str = "nearest",
-                                siting: str = "left") -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                                siting: str = "left", transfer: str = "sdr", peak_nits: float = 1000.0) \
+        -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """The same of a semi-planar frame (:func:`yuv_semiplanar_planes`' layout: NV12 / NV21, NV16 / NV61, NV24 / NV42,
     P010, P012, P210, P410), bit-equal to ``image_patch_planes(yuv_semiplanar_to_rgb(...), ...)``. ``vu``: the pairs
     are (V, U)."""
     y, uv = yuv_semiplanar_planes(y, uv, subsampling, depth)
     table = yuv_table(matrix, full_range, depth)
     _chroma_check(chroma, siting)
+    _transfer_check(transfer, peak_nits, depth)
     B, h, w = y.shape
     H, W = int(out_hw[0]), int(out_hw[1])
     tabs = _yuv_fused(y, (h, w), (H, W), patch)
     if tabs is None:
-        rgb = yuv_semiplanar_to_rgb(y, uv, subsampling, depth, msb, matrix, full_range, vu, chroma, siting)
+        rgb = yuv_semiplanar_to_rgb(y, uv, subsampling, depth, msb, matrix, full_range, vu, chroma, siting, transfer,
+                                    peak_nits)
         return image_patch_planes(rgb, (H, W), patch, mean, std, want_pixels)
     pairs = uv.as_strided((B, uv.shape[1], 2 * uv.shape[2]), (uv.stride(0), uv.stride(1), 1))   # a view, never a copy
     src = yuv_src(YUV_SEMIPLANAR, (y, pairs), subsampling, depth, msb, int(bool(vu)), table, chroma, siting)
     return _yuv_launch(src, tabs, B, h, w, H, W, patch, mean, std, want_pixels, y.device,
-                       "yuv_semiplanar_patch_planes")
+                       "yuv_semiplanar_patch_planes", None if transfer == "sdr" else (transfer, depth, matrix, peak_nits))
 
 
 def yuyv_patch_planes(data: torch.Tensor, width: int, order: str, out_hw: Tuple[int, int], patch: int,
