@@ -32,9 +32,15 @@
 //    depth through a table, a 3 x 3 integer matrix and a second table (image_yuv.h's NosYuvHdr; the host builds them in
 //    fp64 and the kernel knows no transfer function). Six more instantiations: planar and semi-planar, 4:4:4 and
 //    subsampled with nearest chroma, subsampled with bilinear chroma.
+//  * image_patch_planes_tiles3 / _tiles4 — the packed staging loops over B tiles of one frame: tile b starts at a byte
+//    offset read from a device table (tile origins on a 2-D grid are not one batch stride); [lo, hi) stays the frame's
+//    storage. Bit-equal to the packed entries on the B crops stacked.
 //  * detections_f32 — softmax over the class logits, the best of the first L classes, the box in
 //    corner format scaled to the original image, and a stable compaction of the rows above the
 //    threshold; one workgroup per image, one wave per row.
+//  * merge_detections_f32 — the detections of B overlapping tiles of one frame as one list: scores as above, boxes in
+//    frame pixels, the candidates ordered by score (a rank count in LDS), duplicates of another tile's kept box
+//    suppressed greedily (one pivot per barrier), the kept rows compacted in that order; one workgroup.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -101,6 +107,13 @@ struct PackedArgs {
   int r, g, b;
 };
 
+// B tiles of one packed frame: tile b's first byte is s.p + origin[b] (a device table of byte offsets the host
+// built from the tile origins) instead of s.p + b * s.bs. A type of its own, so that the packed kernels' arguments
+// are what they were.
+struct PackedTileArgs : PackedArgs {
+  const long long* origin;  // [B]
+};
+
 // The source layouts, one instantiation of the body (and one __global__ entry) each. RGB: contiguous
 // [B][h][w][3], staged as whole rows of aligned dwords, footprints of up to FMAX = 72 columns. Every other
 // layout stages columns in groups of 4 (for 4:2:0 one dword of luma and the two chroma samples under it, for
@@ -108,7 +121,7 @@ struct PackedArgs {
 // any GROUP_FMAX_W = 69 columns lie inside 18 consecutive groups wherever they start, so these layouts
 // cover footprints of up to 69 columns (scale 4 at patch 16); the host falls back past that.
 // YUV is the general front end (image_yuv.h): its staging loop is instantiated per Yuv<layout, hsub, sample bytes>.
-enum class Src { RGB, NV12, NV21, YUV420P, PACKED3, PACKED4, YUV };
+enum class Src { RGB, NV12, NV21, YUV420P, PACKED3, PACKED4, YUV, TILES3, TILES4 };
 constexpr int NG = RS / 12, GROUP_FMAX_W = NG * 4 - 3;
 constexpr int NV12_FMAX_W = GROUP_FMAX_W, YUV420P_FMAX_W = GROUP_FMAX_W, PACKED_FMAX_W = GROUP_FMAX_W;
 constexpr int YUV_FMAX_W = GROUP_FMAX_W;
@@ -502,10 +515,12 @@ __device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const 
         } else {
           // 4 pixels of C = 3 or 4 bytes: their 12 or 16 bytes from the row's aligned dwords, then the three
           // colour bytes of each by their offsets in a pixel (a fourth byte is dropped here)
-          constexpr int C = S == Src::PACKED4 ? 4 : 3;
+          constexpr int C = S == Src::PACKED4 || S == Src::TILES4 ? 4 : 3;
           uint32_t w[C], px[4];
-          load_bytes<4 * C>(w, reinterpret_cast<uintptr_t>(n.s.p) + b * n.s.bs + sy * n.s.pitch + sx * C, n.s.lo,
-                            n.s.hi);
+          long long first;  // of image b: by the batch stride, or (tiles of one frame) from the origin table
+          if constexpr (S == Src::TILES3 || S == Src::TILES4) first = n.origin[b];
+          else first = b * n.s.bs;
+          load_bytes<4 * C>(w, reinterpret_cast<uintptr_t>(n.s.p) + first + sy * n.s.pitch + sx * C, n.s.lo, n.s.hi);
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             uint32_t q;  // pixel k's bytes from bit 0
@@ -601,6 +616,14 @@ __global__ __launch_bounds__(256) void image_patch_planes_packed3(ImgArgs a, Pac
 
 __global__ __launch_bounds__(256) void image_patch_planes_packed4(ImgArgs a, PackedArgs n) {
   image_patch_planes_body<Src::PACKED4>(a, n);
+}
+
+__global__ __launch_bounds__(256) void image_patch_planes_tiles3(ImgArgs a, PackedTileArgs n) {
+  image_patch_planes_body<Src::TILES3>(a, n);
+}
+
+__global__ __launch_bounds__(256) void image_patch_planes_tiles4(ImgArgs a, PackedTileArgs n) {
+  image_patch_planes_body<Src::TILES4>(a, n);
 }
 
 // the general YUV front end: one instantiation per (layout, hsub, sample bytes) the host launches
@@ -702,6 +725,132 @@ __global__ __launch_bounds__(DT) void detections_f32(const float* __restrict__ l
     out_boxes[slot * 4 + 3] = 0.f;
   }
   if (tid == 0) count[b] = base;
+}
+
+// overlap of two corner boxes: inter / min(area) (iou = 0, "intersection over smaller") or inter / union (iou = 1);
+// a denominator that is not positive counts as overlap 0
+__device__ __forceinline__ float box_overlap(const float* a, const float* b, int iou) {
+  const float iw = fmaxf(fminf(a[2], b[2]) - fmaxf(a[0], b[0]), 0.f);
+  const float ih = fmaxf(fminf(a[3], b[3]) - fmaxf(a[1], b[1]), 0.f);
+  const float inter = iw * ih;
+  const float aa = (a[2] - a[0]) * (a[3] - a[1]), ab = (b[2] - b[0]) * (b[3] - b[1]);
+  const float den = iou ? aa + ab - inter : fminf(aa, ab);
+  return den > 0.f ? inter / den : 0.f;
+}
+
+// logits [B][M][C] and boxes [B][M][4] of B tiles of th x tw pixels whose first pixel is origins[b] = (y0, x0) of one
+// frame -> the rows with score > thr as one list in frame pixels, ordered by score descending (ties: row b * M + m
+// ascending), less every row that an earlier kept row of the same label from another tile overlaps by more than mt;
+// the kept rows at the front of scores / labels / out_boxes / tile [B*M], zeros behind them, their number in count[0].
+// One workgroup, N = B * M <= MMAX. Static LDS: 10 tables of MMAX words = 40 KB.
+__global__ __launch_bounds__(DT) void merge_detections_f32(const float* __restrict__ logits,
+                                                            const float* __restrict__ boxes,
+                                                            const int* __restrict__ origins, float th, float tw,
+                                                            float thr, float mt, int iou, int N, int M, int C,
+                                                            float* __restrict__ scores, int* __restrict__ labels,
+                                                            float* __restrict__ out_boxes, int* __restrict__ tile,
+                                                            int* __restrict__ count) {
+  __shared__ float s_score[MMAX];   // by row
+  __shared__ int s_label[MMAX];
+  __shared__ float q_score[MMAX];   // by rank among the candidates
+  __shared__ int q_label[MMAX], q_tile[MMAX], q_keep[MMAX];
+  __shared__ float q_box[MMAX * 4];
+  __shared__ int s_wave[DW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, L = C - 1;
+  // scores and labels as detections_f32 computes them: one wave per row
+  for (int row = wave; row < N; row += DW) {
+    const float* x = logits + size_t(row) * C;
+    const float x0 = lane < C ? x[lane] : -INFINITY, x1 = lane + 64 < C ? x[lane + 64] : -INFINITY;
+    const float m = wave_max(fmaxf(x0, x1));
+    const float e0 = lane < C ? expf(x0 - m) : 0.f, e1 = lane + 64 < C ? expf(x1 - m) : 0.f;
+    const float sum = wave_sum(e0 + e1);
+    float best = lane < L ? e0 / sum : -1.f;
+    int idx = lane;
+    const float p1 = lane + 64 < L ? e1 / sum : -1.f;
+    if (p1 > best) best = p1, idx = lane + 64;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ob = __shfl_xor(best, o);
+      const int oi = __shfl_xor(idx, o);
+      if (ob > best || (ob == best && oi < idx)) best = ob, idx = oi;
+    }
+    if (lane == 0) {
+      s_score[row] = best;
+      s_label[row] = idx;
+    }
+  }
+  __syncthreads();
+  // the order: thread i counts the candidates that precede row i (a strict total order, so ranks are distinct and
+  // below the number of candidates, which every thread counts as well)
+  const float si = tid < N ? s_score[tid] : 0.f;
+  const bool cand = tid < N && si > thr;
+  int rank = 0, ncand = 0;
+  for (int j = 0; j < N; ++j) {
+    const float sj = s_score[j];
+    const bool cj = sj > thr;
+    ncand += cj;
+    rank += cj && (sj > si || (sj == si && j < tid));
+  }
+  if (cand) {
+    const int b = tid / M;
+    const float* bx = boxes + size_t(tid) * 4;
+    const float cx = bx[0], cy = bx[1], hw = 0.5f * bx[2], hh = 0.5f * bx[3];
+    const float oy = float(origins[2 * b]), ox = float(origins[2 * b + 1]);
+    q_score[rank] = si;
+    q_label[rank] = s_label[tid];
+    q_tile[rank] = b;
+    q_keep[rank] = 1;
+    q_box[rank * 4 + 0] = (cx - hw) * tw + ox;
+    q_box[rank * 4 + 1] = (cy - hh) * th + oy;
+    q_box[rank * 4 + 2] = (cx + hw) * tw + ox;
+    q_box[rank * 4 + 3] = (cy + hh) * th + oy;
+  }
+  __syncthreads();
+  // the greedy pass: thread k owns candidate k; pivot p, when still kept, drops the later candidates it matches.
+  // q_keep[k] is written by thread k alone and read as a pivot only after the barrier of a later iteration.
+  const int k = tid;
+  bool keep = k < ncand;
+  float mine[4] = {0.f, 0.f, 0.f, 0.f};
+  int lab = -1, tl = -1;
+  if (keep) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) mine[c] = q_box[k * 4 + c];
+    lab = q_label[k], tl = q_tile[k];
+  }
+  for (int p = 0; p + 1 < ncand; ++p) {
+    __syncthreads();
+    if (!q_keep[p]) continue;  // the same in every thread
+    if (keep && k > p && q_label[p] == lab && q_tile[p] != tl && box_overlap(q_box + p * 4, mine, iou) > mt) {
+      keep = false;
+      q_keep[k] = 0;
+    }
+  }
+  __syncthreads();
+  // the kept candidates, in order, to the front
+  const unsigned long long mask = __ballot(keep);
+  if (lane == 0) s_wave[wave] = __popcll(mask);
+  __syncthreads();
+  int off = 0, total = 0;
+  for (int w = 0; w < DW; ++w) {
+    off += w < wave ? s_wave[w] : 0;
+    total += s_wave[w];
+  }
+  if (keep) {
+    const int slot = off + __popcll(mask & ((1ull << lane) - 1ull));
+    scores[slot] = q_score[k];
+    labels[slot] = lab;
+    tile[slot] = tl;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) out_boxes[slot * 4 + c] = mine[c];
+  }
+  for (int z = total + tid; z < N; z += DT) {
+    scores[z] = 0.f;
+    labels[z] = 0;
+    tile[z] = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) out_boxes[z * 4 + c] = 0.f;
+  }
+  if (tid == 0) count[0] = total;
 }
 
 int check(const char* what) {
@@ -1001,6 +1150,50 @@ int nos_image_patch_planes_packed(const void* img, const void* lo, const void* h
   return check("image_patch_planes_packed");
 }
 
+// B tiles of tile_h x tile_w pixels (h and w of the common arguments) of one packed frame img [frame_h][frame_w][C]
+// (order, pitch, [lo, hi) as in nos_image_patch_planes_packed), as that entry gives for the B crops stacked. origins:
+// host array [B][2] of every tile's first row and column; table: device array [B] of int64 byte offsets from img,
+// origins[b][0] * pitch + origins[b][1] * C (the host built both from one plan; a graph holds the table). Nothing is
+// launched unless the frame lies inside its storage and every tile inside the frame; the kernel reads no byte outside
+// [lo, hi) whatever the table holds.
+int nos_image_patch_planes_tiles(const void* img, const void* lo, const void* hi, long long pitch, const char* order,
+                                 const int* origins, const long long* table, int frame_h, int frame_w, void* planes,
+                                 float* pixels, const int* yidx, const float* ywt, const int* xidx, const float* xwt,
+                                 int ytab, int xtab, int taps, int max_fh, int max_fw, const float* a, const float* b,
+                                 int B, int h, int w, int H, int W, int p, int gh, int gw, int wgs, void* stream) {
+  if (!img || !order) return fail("image_patch_planes: null operand");
+  if (!origins || !table) return fail("image_patch_planes_tiles: null origin table");
+  const std::string o(order);
+  if (o != "rgb" && o != "bgr" && o != "rgba" && o != "bgra")
+    return fail("image_patch_planes_tiles: unknown channel order (rgb, bgr, rgba or bgra)");
+  const int C = int(o.size());
+  ImgArgs k{};
+  int grid = 0;
+  if (const int rc = image_args(k, grid, planes, pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a, b,
+                                B, h, w, H, W, p, gh, gw, wgs))
+    return rc;
+  if (max_fw > PACKED_FMAX_W) return fail("image_patch_planes_tiles: a patch's source footprint exceeds 69 columns");
+  if (frame_h <= 0 || frame_w <= 0) return fail("image_patch_planes_tiles: the frame's sizes must be positive");
+  if (pitch < (long long)frame_w * C) return fail("image_patch_planes_tiles: the row pitch is smaller than a row's bytes");
+  if (!stride_range(pitch, 0)) return fail("image_patch_planes_tiles: pitch out of range");
+  if (!inside(1, img, lo, hi, 0, frame_h, pitch, (long long)frame_w * C))
+    return fail("image_patch_planes_tiles: the frame does not lie inside its storage bounds");
+  for (int t = 0; t < B; ++t) {
+    const long long y0 = origins[2 * t], x0 = origins[2 * t + 1];
+    if (y0 < 0 || x0 < 0 || y0 + h > frame_h || x0 + w > frame_w)
+      return fail("image_patch_planes_tiles: a tile does not lie inside the frame");
+  }
+  PackedTileArgs n{};
+  n.s = plane_arg(img, lo, hi, pitch, 0);
+  n.r = o[0] == 'r' ? 0 : 2, n.g = 1, n.b = 2 - n.r;
+  n.origin = table;
+  if (C == 4)
+    hipLaunchKernelGGL(image_patch_planes_tiles4, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, n);
+  else
+    hipLaunchKernelGGL(image_patch_planes_tiles3, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, n);
+  return check("image_patch_planes_tiles");
+}
+
 int nos_image_yuv_max_footprint() { return YUV_FMAX_W; }
 
 // The same from any YUV surface NosYuvSrc (image_yuv.h) describes: planar, semi-planar or packed 4:2:2; 4:2:0,
@@ -1098,6 +1291,24 @@ int nos_detections_f32(const float* logits, const float* boxes, const float* tar
   hipLaunchKernelGGL(detections_f32, dim3(B), dim3(DT), 0, reinterpret_cast<hipStream_t>(stream), logits, boxes,
                      target, threshold, M, C, scores, labels, out_boxes, count);
   return check("detections_f32");
+}
+
+// The detections of B tiles of one frame merged (merge_detections_f32): logits [B][M][C] fp32, boxes [B][M][4] fp32,
+// origins [B][2] int32 (first row, first column of tile b), all on the device; tile_h, tile_w: the tiles' size in
+// pixels; iou: 0 compares inter / min(area) with match_threshold, 1 inter / union -> count [1] int32, scores [B*M] fp32,
+// labels [B*M] int32, out_boxes [B*M][4] fp32 (frame pixels), tile [B*M] int32
+int nos_merge_detections_f32(const float* logits, const float* boxes, const int* origins, float tile_h, float tile_w,
+                             float threshold, float match_threshold, int iou, int B, int M, int C, int* count,
+                             float* scores, int* labels, float* out_boxes, int* tile, void* stream) {
+  if (!logits || !boxes || !origins || !count || !scores || !labels || !out_boxes || !tile)
+    return fail("merge_detections: null operand");
+  if (B <= 0 || M <= 0 || (long long)B * M > MMAX || C < 2 || C > CMAX)
+    return fail("merge_detections: 0 < B * M <= 1024, 2 <= classes (with \"no object\") <= 128");
+  if (iou != 0 && iou != 1) return fail("merge_detections: the match is 0 (ios) or 1 (iou)");
+  hipLaunchKernelGGL(merge_detections_f32, dim3(1), dim3(DT), 0, reinterpret_cast<hipStream_t>(stream), logits, boxes,
+                     origins, tile_h, tile_w, threshold, match_threshold, iou, B * M, M, C, scores, labels, out_boxes,
+                     tile, count);
+  return check("merge_detections_f32");
 }
 
 }  // extern "C"

@@ -25,6 +25,11 @@ there (c) interpolates the chroma in torch before the RGB kernel. Three more are
 (BT.2020, peak 1000 nits: ``p010_pq_*``, ``p010_hlg_*``, ``i010_pq_bilinear_*``): (a) the fused launch through the
 tables, (b) the same surface's nearest-chroma ``transfer="sdr"`` fused launch as the floor (``*_sdr_fused_us``), (c)
 the frame's ``rgb()`` in torch on the GPU (table look-ups and the gamut matrix as tensor ops), then the RGB kernel.
+Three rows time tiled detection (``--rows tiles`` runs them alone) on a 2160x3840 RGB frame at ``(2, 2)`` tiles, overlap
+0.2 — tiles of 1200x2134 resized to 736x1328: ``tiles_planes_*``, the one tile launch against four
+``packed_patch_planes`` launches on the crop views; ``merge_n400_*`` / ``merge_n900_*``, ``merge_detections`` of 4 and 9
+tiles of 100 rows against its torch reference; and, on the whole GPU only, ``detect_tiled_ms`` against four
+``detect_image`` calls on the crops (``detect_image_x4_ms``).
 """
 from __future__ import annotations
 
@@ -73,6 +78,7 @@ def main() -> int:
     ap.add_argument("--out", default="gpurun_out/kbench.json")
     ap.add_argument("--only", choices=("all", "attn", "gemm", "model", "modes", "image"), default="all")
     ap.add_argument("--slices", default="spx,dpx,qpx,cpx")
+    ap.add_argument("--rows", choices=("all", "tiles"), default="all", help="image: every row, or the tiled-detection rows alone")
     ap.add_argument("--partitions", type=int, default=0, help="modes: run only this many partitions of each mode")
     ap.add_argument("--free-s", type=float, default=0.0,
                     help="modes: serve free-running (one thread per pod, as the bench) for this many seconds "
@@ -264,7 +270,10 @@ def image_bench(a) -> int:
 
     from walkai_nos_amd.models.workload.processor import Nv12, Packed, Yuv420p
     frames, layouts = {}, {}
-    for h, w in ((480, 640), (1080, 1920)):
+    full = a.rows == "all"
+    if not full:
+        imgs = {}
+    for h, w in ((480, 640), (1080, 1920)) if full else ():
         pitch = -(-w // 256) * 256
         surface = torch.randint(0, 256, (pitch * h * 3 // 2,), generator=g, dtype=torch.uint8).cuda()
         frames[f"{h}x{w}"] = Nv12.from_buffer(surface, h, w, pitch)
@@ -340,6 +349,11 @@ def image_bench(a) -> int:
                            lambda: I.image_patch_planes(conv, out, 16, IMAGENET_MEAN, IMAGENET_STD),
                            lambda: I.image_patch_planes(fr.rgb(), out, 16, IMAGENET_MEAN, IMAGENET_STD),
                            s, a.iters)
+            tiles_rows(r, pair, s, a.iters, rounds, whole_gpu=cus is None)
+            if not full:
+                print(json.dumps(r), flush=True)
+                results.append(r)
+                continue
             pair(r, "detections", lambda: I.detections(logits, boxes, target, 0.5),
                  lambda: I.detections_reference(logits, boxes, target, 0.5), s, a.iters)
             with torch.cuda.stream(s), torch.no_grad():
@@ -361,6 +375,50 @@ def image_bench(a) -> int:
     with open(a.out, "w") as f:
         json.dump(results, f, indent=1)
     return 0
+
+
+def tiles_rows(r, pair, s, iters, rounds, whole_gpu):
+    """Tiled detection of a 2160x3840 RGB frame at (2, 2) tiles, overlap 0.2 (see the module docstring): the pairs go
+    into ``r`` as ``*_hip_us`` (the new launch) and ``*_torch_us`` (what it replaces)."""
+    import statistics
+
+    from walkai_nos_amd.models.workload.processor import IMAGENET_MEAN, IMAGENET_STD
+    from walkai_nos_amd.models.workload.yolos import YolosSmall
+    from walkai_nos_amd.ops import image as I
+    g = torch.Generator().manual_seed(1)
+    frame = torch.randint(0, 256, (2160, 3840, 3), generator=g, dtype=torch.uint8).cuda()
+    th, tw, origins = I.tile_plan(2160, 3840, (2, 2), 0.2)
+    out = I.resize_size((th, tw), 800, 1333)
+    r["tiles"] = {"frame_hw": [2160, 3840], "tile_hw": [th, tw], "target_hw": list(out), "origins": origins}
+    crops = [frame[None, y:y + th, x:x + tw] for y, x in origins]        # views: read in place
+    pair(r, "tiles_planes", lambda: I.tiled_patch_planes(frame, "rgb", origins, (th, tw), out, 16, IMAGENET_MEAN,
+                                                         IMAGENET_STD),
+         lambda: [I.packed_patch_planes(c, "rgb", out, 16, IMAGENET_MEAN, IMAGENET_STD) for c in crops], s, iters)
+    for B in (4, 9):
+        lg = 3.0 * torch.randn(B, 100, 92, generator=g).cuda()
+        bx = (0.2 + 0.6 * torch.rand(B, 100, 4, generator=g)).cuda()
+        org = [(300 * (b // 3), 400 * (b % 3)) for b in range(B)]
+        # (the reference is B * 100 steps of three launches: fewer calls per graph)
+        t = {"hip": [], "torch": []}
+        for _ in range(rounds):
+            t["hip"].append(timeit(lambda: I.merge_detections(lg, bx, org, (th, tw), 0.1), s, iters))
+            t["torch"].append(timeit(lambda: I.merge_detections_reference(lg, bx, org, (th, tw), 0.1), s, 2))
+        r[f"merge_n{B * 100}_hip_us"] = round(statistics.median(t["hip"]), 1)
+        r[f"merge_n{B * 100}_torch_us"] = round(statistics.median(t["torch"]), 1)
+        r[f"merge_n{B * 100}_rounds_us"] = {k: [round(v, 1) for v in vs] for k, vs in t.items()}
+        r[f"merge_n{B * 100}_kept"] = int(I.merge_detections(lg, bx, org, (th, tw), 0.1)[0].item())
+    if not whole_gpu:
+        return
+    with torch.cuda.stream(s), torch.no_grad():
+        m = YolosSmall().cuda().eval()
+        it = max(2, iters // 5)
+        t = {"detect_tiled": [], "detect_image_x4": []}
+        for _ in range(rounds):
+            t["detect_tiled"].append(timeit(lambda: m.detect_tiled(frame, (2, 2), 0.2), s, it))
+            t["detect_image_x4"].append(timeit(lambda: [m.detect_image(c) for c in crops], s, it))
+    r["detect_tiled_ms"] = round(statistics.median(t["detect_tiled"]) / 1000.0, 3)
+    r["detect_image_x4_ms"] = round(statistics.median(t["detect_image_x4"]) / 1000.0, 3)
+    r["tiles_model_rounds_ms"] = {k: [round(v / 1000.0, 3) for v in vs] for k, vs in t.items()}
 
 
 def free_running(slots, seconds: float) -> int:

@@ -25,6 +25,9 @@ The names of ``models/workload/surfaces.py`` — ``i422``, ``nv16``, ``i444``, `
 decoder's ``p010`` / ``p210`` / ``p410``, ``i010`` (``yuv420p10le``) and their 12-bit forms — go the same way, and
 ``--matrix bt601|bt709|bt2020`` and ``--full-range`` say how any YUV format's codes are read, and ``--transfer
 pq|hlg`` (with ``--peak-nits``) that a 10- or 12-bit format's codes are HDR and are tone-mapped to SDR in that launch.
+``--tiles R,C`` runs a large frame as ``R x C`` overlapping tiles in one batch (``YolosSmall.detect_tiled``;
+``--tile-overlap``, ``--match ios|iou``, ``--match-threshold``): the JSON line then carries ``"tiles"``, the tile count,
+and ``"detections"`` counts the merged boxes.
 """
 from __future__ import annotations
 
@@ -103,7 +106,23 @@ def main(argv=None) -> int:
                          "tone-mapped to SDR")
     ap.add_argument("--peak-nits", type=float, default=1000.0,
                     help="--end-to-end: with --transfer pq|hlg, the luminance that is mapped to SDR white (above 203)")
+    ap.add_argument("--tiles", default="", help="--end-to-end: R,C overlapping tiles of the frame, run as one batch and merged")
+    ap.add_argument("--tile-overlap", type=float, default=0.2, help="--tiles: the overlap of neighbouring tiles, of a tile")
+    ap.add_argument("--match", choices=("ios", "iou"), default="ios",
+                    help="--tiles: how two tiles' boxes are compared: intersection over the smaller area, or over the union")
+    ap.add_argument("--match-threshold", type=float, default=0.5,
+                    help="--tiles: a box is dropped when a kept box of the same label from another tile overlaps it by more")
     args = ap.parse_args(argv)
+    tiles = None
+    if args.tiles:
+        if not args.end_to_end:
+            ap.error("--tiles takes --end-to-end")
+        try:
+            tiles = tuple(int(v) for v in args.tiles.split(","))
+        except ValueError:
+            tiles = ()
+        if len(tiles) != 2 or min(tiles) < 1:
+            ap.error(f"--tiles {args.tiles!r} is not R,C with R, C >= 1")
     if args.transfer != "sdr" and args.pixel_format not in DEEP:
         ap.error(f"--transfer {args.transfer} takes a 10- or 12-bit --pixel-format ({', '.join(DEEP)}), "
                  f"not {args.pixel_format}")
@@ -157,8 +176,13 @@ def main(argv=None) -> int:
             buf = torch.randint(0, 256, (ih * pitch,), generator=gen, dtype=torch.uint8).to(dev)
             img = Packed(buf.as_strided((ih, iw, C), (pitch, C, 1)), fmt)
         hw = model.processor.size((ih, iw))
+        if tiles is not None:
+            th, tw, origins = model.processor.tile_plan((ih, iw), tiles, args.tile_overlap, model.c.num_detection_tokens)
+            hw = model.processor.size((th, tw))
 
         def infer():
+            if tiles is not None:
+                return model.detect_tiled(img, tiles, args.tile_overlap, args.threshold, args.match, args.match_threshold)
             return model.detect_image(img, args.threshold)
     else:
         x = demo_input(1, hw, dev, seed=seed)
@@ -226,6 +250,9 @@ def main(argv=None) -> int:
         out["input_hw"] = list(hw)
         out["pixel_format"] = args.pixel_format
         out["transfer"] = args.transfer
+        if tiles is not None:
+            out["tiles"] = len(origins)
+            out["tile_hw"] = [th, tw]
         out["detections"] = int(res["count"].sum().item())   # of the last inference
     if census is not None:
         out["census"] = census

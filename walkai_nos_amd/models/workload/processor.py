@@ -316,10 +316,41 @@ class YolosProcessor:
         return I.image_patch_planes(img, hw, patch, self.mean, self.std, want_pixels)
 
     @staticmethod
+    def tile_plan(hw: Tuple[int, int], tiles: Tuple[int, int] = (2, 2), overlap: float = 0.2,
+                  num_detection_tokens: int = 100) -> Tuple[int, int, list]:
+        """``(th, tw, origins)`` of an ``(h, w)`` frame cut into ``tiles = (R, C)`` overlapping tiles of one size
+        (``ops.image.tile_plan``); one call then runs one model size, ``size((th, tw))``."""
+        return I.tile_plan(hw[0], hw[1], tiles, overlap, num_detection_tokens)
+
+    @staticmethod
+    def as_packed(img: Any) -> Tuple[torch.Tensor, str]:
+        """``(data [1, h, w, C], order)`` of :meth:`as_batch`'s result for the tile launch: a tensor or a
+        :class:`Packed` frame as it lies; any other :class:`Frame` (NV12, P010 and the rest) converted once by its
+        ``rgb()`` — the YUV staging loops take no tile origins."""
+        if isinstance(img, Packed):
+            data, order = img.batched(), img.order
+        else:
+            data, order = (img.rgb() if isinstance(img, Frame) else img), "rgb"
+        if data.shape[0] != 1:
+            raise ValueError(f"tiles are cut from one frame, not from a batch of {data.shape[0]}")
+        return data, order
+
+    def tile_planes(self, data: torch.Tensor, order: str, origins, tile_hw: Tuple[int, int], hw: Tuple[int, int],
+                    want_pixels: bool = False, patch: Optional[int] = None) \
+            -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """:meth:`patch_planes` of the tiles of one packed frame (:meth:`as_packed`), each ``tile_hw`` large at its
+        ``(y0, x0)`` of ``origins`` and resized to ``hw``, by one launch (``ops.image.tiled_patch_planes``)."""
+        return I.tiled_patch_planes(data, order, origins, tile_hw, hw, self.patch if patch is None else patch,
+                                    self.mean, self.std, want_pixels)
+
+    @staticmethod
     def results(count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor) \
             -> List[Dict[str, torch.Tensor]]:
         """The compacted device tensors of ``ops.image.detections`` as ``transformers`` returns them:
-        one ``{"scores", "labels", "boxes"}`` per image (this reads ``count`` on the host)."""
+        one ``{"scores", "labels", "boxes"}`` per image (this reads ``count`` on the host). The merged tensors of
+        ``ops.image.merge_detections`` (one list for the frame: ``scores [N]``) give one entry."""
+        if scores.dim() == 1:
+            scores, labels, boxes = scores[None], labels[None], boxes[None]
         return [{"scores": scores[i, :n], "labels": labels[i, :n].long(), "boxes": boxes[i, :n]}
                 for i, n in enumerate(count.tolist())]
 

@@ -19,6 +19,9 @@ DETR-style MLP heads) built for the MI355X inference path:
 * ``encode_image`` / ``detect_image`` take a uint8 photo instead of ready pixels: the processor's
   resize and normalisation fused with the patch GEMM's x3 split, and the post-process, one HIP
   launch each (:mod:`walkai_nos_amd.ops.image`, :mod:`.processor`);
+* ``detect_tiled`` runs a frame too large for one input as ``R x C`` overlapping tiles in one batch — one tile-staging
+  launch, one patch GEMM, the fused heads on all ``B x nd`` rows — and merges the tiles' detections in frame pixels by
+  one more launch (``ops.image.tiled_patch_planes`` / ``merge_detections``), still without a host synchronisation;
 * the last block runs on the detection rows only ("detection tail"). ``detect`` reads nothing but
   the last ``nd`` = 100 rows, and a row of a block's output depends on the other rows only through K
   and V: so in the last block the attention queries, the projection, LN2, fc1, GELU and fc2 of the
@@ -403,6 +406,59 @@ class YolosSmall(nn.Module):
         count, scores, labels, xyxy = I.detections(logits, boxes, self._target_sizes(img), threshold)
         return {"logits": logits, "pred_boxes": boxes, "count": count, "scores": scores, "labels": labels,
                 "boxes": xyxy}
+
+    def detect_tiled(self, image_u8, tiles: Tuple[int, int] = (2, 2), overlap: float = 0.2, threshold: float = 0.5,
+                     match: str = "ios", match_threshold: float = 0.5) -> Dict[str, object]:
+        """Tiled ("sliced") detection of one large frame, with no host synchronisation (capturable as one graph, which
+        reads the frame's buffer by address as :meth:`detect_image`'s does): the frame is cut into ``tiles = (R, C)``
+        overlapping tiles of one size (``processor.tile_plan``), the ``B = R * C`` tiles run as one batch at the
+        model size ``processor.size(tile_hw)``, and their detections are mapped to frame pixels and merged
+        (``ops.image.merge_detections``: a box is dropped when a kept box of the same label from *another* tile
+        overlaps it by more than ``match_threshold``, ``match`` ``"ios"`` or ``"iou"``). Returns ``logits [B, nd, L+1]``
+        and ``pred_boxes [B, nd, 4]`` per tile, ``origins [B, 2]`` int32 ``(y0, x0)`` on the device, ``tile_hw``, and
+        the merged ``count [1]``, ``scores``, ``labels``, ``boxes`` (frame pixels) and ``tile`` ``[B * nd]``, kept rows
+        first by score; ``self.processor.results(count, scores, labels, boxes)`` gives the list.
+
+        On the GPU in x3 mode, for a resize the kernel takes, the tiles are staged by one launch
+        (``ops.image.tiled_patch_planes``), one patch GEMM at ``M = B * P`` writes a temporary (bias and the position
+        rows fused, broadcast over the tiles) that one copy puts into the patch rows of ``B`` token templates, the
+        blocks run with the detection tail, and the final LayerNorm and both heads run fused on the ``B * nd`` rows.
+        Elsewhere it is ``detect(encode_detection(processor.preprocess(stacked crops)))`` and the merge. A
+        ``processor.Frame`` other than ``Packed`` is converted once by its ``rgb()`` and then tiled."""
+        img = self.processor.as_batch(image_u8, self.pos_embed.device)
+        data, order = self.processor.as_packed(img)
+        nd, p = self.c.num_detection_tokens, self.c.patch_size
+        th, tw, origins = self.processor.tile_plan(tuple(data.shape[1:3]), tiles, overlap, nd)
+        hw = self.processor.size((th, tw))
+        B = len(origins)
+        if (data.is_cuda and K.x3_active(self.pos_embed) and self.c.num_channels == 3 and (3 * p * p) % 32 == 0
+                and I.fusable((th, tw), hw, p)):
+            from ...ops.gemm import gemm_x3
+            pe, mid = self.position_embeddings(hw)
+            P = (hw[0] // p) * (hw[1] // p)
+            planes, _ = self.processor.tile_planes(data, order, origins, (th, tw), hw, patch=p)
+            rows = gemm_x3(planes, self.patch.weight.reshape(self.patch.weight.shape[0], -1), self.patch.bias,
+                           residual2=pe[0, 1:1 + P])
+            x = self.token_template(hw).repeat(B, 1, 1)
+            x[:, 1:1 + P] = rows.view(B, P, -1)
+            det = self._run_blocks(x, mid, det_only=True).contiguous()
+            if self.heads_fusable():
+                logits, boxes = K.detection_heads(det.view(B * nd, -1), self.ln_f, self.cls_head.layers,
+                                                  self.box_head.layers)
+                logits, boxes = logits.view(B, nd, -1), boxes.view(B, nd, -1)
+            else:
+                det = K.layernorm(det, self.ln_f.weight, self.ln_f.bias, self.c.layer_norm_eps)
+                logits, boxes = self.cls_head(det), torch.sigmoid(self.box_head(det))
+        else:
+            crops = I.tile_crops(data, origins, (th, tw))
+            if order != "rgb":
+                crops = I.packed_to_rgb(crops, order)
+            logits, boxes = self.detect(self.encode_detection(self.processor.preprocess(crops)))
+        org = I.origin_tensor(origins, data.device)
+        count, scores, labels, xyxy, tile = I.merge_detections(logits, boxes, org, (th, tw), threshold, match,
+                                                               match_threshold)
+        return {"logits": logits, "pred_boxes": boxes, "origins": org.clone(), "tile_hw": (th, tw), "count": count,
+                "scores": scores, "labels": labels, "boxes": xyxy, "tile": tile}
 
     def _target_sizes(self, img: torch.Tensor) -> torch.Tensor:
         """``[B, 2]`` fp32 (height, width) of the original images on their device, cached: a captured

@@ -52,10 +52,19 @@ is rounded to uint8 between the two passes, so pixels differ from it by less tha
 
 Every layout is bit-equal to :func:`image_patch_planes` of the converted or re-ordered contiguous RGB frame,
 which is also what runs on the CPU, with the ``torch`` backend and past a layout's footprint limit.
+
+* :func:`tile_plan` / :func:`tiled_patch_planes` / :func:`merge_detections` — tiled ("sliced") detection of a frame
+  too large to shrink to one model input: ``R x C`` overlapping tiles of one size, staged as one batch by one launch
+  (the packed staging loops with a per-tile byte offset from a cached device table), and the tiles' detections mapped
+  to frame pixels and merged by one launch — ordered by score, a box dropped when a kept box of the same label from
+  *another* tile overlaps it by more than ``match_threshold`` (``inter / min(area)`` by default, or IoU). Tiles of
+  unequal size, merging boxes instead of suppressing, YUV tiles staged without ``rgb()`` and more than 1024 rows are
+  not offered.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 import threading
 from typing import Optional, Sequence, Tuple
 
@@ -116,6 +125,10 @@ def _L() -> ctypes.CDLL:
             L.nos_image_patch_planes_yuv_hdr.argtypes = [ctypes.POINTER(NosYuvSrc), ctypes.POINTER(NosYuvHdr)] + \
                 L.nos_image_patch_planes_u8.argtypes[1:]
             L.nos_detections_f32.argtypes = [vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, vp, vp]
+            L.nos_image_patch_planes_tiles.argtypes = [vp, vp, vp, i64, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int),
+                                                       vp, i32, i32] + L.nos_image_patch_planes_u8.argtypes[1:]
+            L.nos_merge_detections_f32.argtypes = [vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, i32, vp, vp, vp, vp,
+                                                   vp, vp]
             L.nos_image_last_error.restype = ctypes.c_char_p
             if (L.nos_image_taps(), L.nos_image_max_footprint(), L.nos_image_max_patch(),
                     L.nos_image_nv12_max_footprint(), L.nos_image_yuv420p_max_footprint(),
@@ -216,12 +229,15 @@ def resample_reference(img: torch.Tensor, out_hw: Tuple[int, int]) -> torch.Tens
 #: the tap tables per ``(h, w, H, W, p, device)``. A launch recorded in a graph reads them by address, so
 #: an entry handed out under capture stays until :func:`invalidate_cache`; of the sizes only seen
 #: eagerly the 16 most recently used are kept (about 44 bytes per output row and column each: 80 KB
-#: at 800 x 1056, so the bound is on the number of stale sizes, not on memory that matters)
+#: at 800 x 1056, so the bound is on the number of stale sizes, not on memory that matters). The tile-origin tables
+#: of :func:`tiled_patch_planes` and :func:`origin_tensor` (a few dozen bytes each) live here too, under keys that
+#: begin with ``"tiles"`` / ``"origins"``
 _tables = GraphCache(16)
 
 
 def invalidate_cache() -> None:
-    """Drop every cached tap table and HDR table, also those a captured graph holds: capture such graphs again."""
+    """Drop every cached tap table, tile-origin table and HDR table, also those a captured graph holds: capture such
+    graphs again."""
     _tables.clear()
     _hdr_tables.clear()
 
@@ -617,6 +633,105 @@ def packed_patch_planes(img: torch.Tensor, order: str, out_hw: Tuple[int, int], 
                                             order.encode(),
                                             *_tail_args(tabs, planes, pixels, mean, std, B, h, w, H, W, patch, gh, gw))
     _check(rc, "packed_patch_planes")
+    return planes, pixels
+
+
+# ---- tiles of one frame ---------------------------------------------------------------------------
+def _axis_plan(n: int, k: int, overlap: float) -> Tuple[int, list]:
+    if k == 1:
+        return n, [0]
+    t = min(n, int(math.ceil(n / (k - (k - 1) * overlap))))
+    return t, [(2 * i * (n - t) + (k - 1)) // (2 * (k - 1)) for i in range(k)]
+
+
+def tile_plan(h: int, w: int, tiles: Tuple[int, int] = (2, 2), overlap: float = 0.2,
+              num_detection_tokens: int = 100) -> Tuple[int, int, list]:
+    """``(th, tw, origins)``: an ``h x w`` frame cut into ``tiles = (R, C)`` tiles of one size that overlap their
+    neighbours by about ``overlap`` of a tile; ``origins`` is the row-major list of ``(y0, x0)``, ``R * C`` long. Per
+    axis of length ``n`` cut into ``k``: ``k == 1`` is the axis itself; otherwise ``t = min(n, ceil(n / (k - (k - 1)
+    overlap)))`` and ``origin_i = i (n - t) / (k - 1)`` rounded half up, so the first tile starts at 0, the last ends
+    at ``n`` and consecutive tiles touch or overlap. ``R * C * num_detection_tokens`` rows must fit
+    :func:`merge_detections` (:data:`MAX_ROWS`)."""
+    R, C = int(tiles[0]), int(tiles[1])
+    if not 0.0 <= overlap < 1.0:
+        raise ValueError(f"tile_plan: overlap {overlap!r} is not in [0, 1)")
+    if R < 1 or C < 1:
+        raise ValueError(f"tile_plan: at least one tile per axis, not {(R, C)}")
+    if R * C * int(num_detection_tokens) > MAX_ROWS:
+        raise ValueError(f"tile_plan: {R} x {C} tiles of {num_detection_tokens} detection tokens are more than "
+                         f"{MAX_ROWS} rows")
+    if h < 1 or w < 1:
+        raise ValueError("tile_plan: a frame of at least one pixel")
+    th, ys = _axis_plan(int(h), R, float(overlap))
+    tw, xs = _axis_plan(int(w), C, float(overlap))
+    return th, tw, [(y, x) for y in ys for x in xs]
+
+
+def _tile_origins(origins, th: int, tw: int, h: int, w: int, who: str) -> Tuple[Tuple[int, int], ...]:
+    out = tuple((int(y), int(x)) for y, x in origins)
+    if not out:
+        raise ValueError(f"{who}: at least one tile")
+    if th < 1 or tw < 1 or any(y < 0 or x < 0 or y + th > h or x + tw > w for y, x in out):
+        raise ValueError(f"{who}: every {th}x{tw} tile lies inside the {h}x{w} frame")
+    return out
+
+
+def tile_crops(img: torch.Tensor, origins, tile_hw: Tuple[int, int]) -> torch.Tensor:
+    """The tiles of ``img`` ``[1, h, w, C]`` stacked: contiguous ``[B, th, tw, C]`` (slices stacked: nothing is copied
+    from the host, so it can be captured)."""
+    th, tw = int(tile_hw[0]), int(tile_hw[1])
+    return torch.stack([img[0, y:y + th, x:x + tw] for y, x in origins])
+
+
+def origin_tensor(origins, device: torch.device) -> torch.Tensor:
+    """``[B, 2]`` int32 ``(y0, x0)`` on ``device``, cached beside the tap tables (a captured graph holds it); a tensor
+    already there is used as it is."""
+    if isinstance(origins, torch.Tensor):
+        return origins.to(device=device, dtype=torch.int32).reshape(-1, 2).contiguous()
+    key = ("origins", tuple((int(y), int(x)) for y, x in origins), str(device))
+    return _tables.get(key, lambda: torch.tensor(key[1], dtype=torch.int32).reshape(-1, 2).to(device))
+
+
+def tiled_patch_planes(img: torch.Tensor, order: str, origins, tile_hw: Tuple[int, int], out_hw: Tuple[int, int],
+                       patch: int, mean: Sequence[float], std: Sequence[float], want_pixels: bool = False) \
+        -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """:func:`packed_patch_planes` of ``B`` tiles of one frame without stacking them: ``img`` uint8 ``[h, w, C]`` or
+    ``[1, h, w, C]`` packed pixels in ``order`` (any row pitch, a crop view: :func:`packed_patch_planes`' contract),
+    ``origins`` the ``(y0, x0)`` of the tiles, each ``tile_hw`` large and resized to ``out_hw`` -> ``(planes [3,
+    B*gh*gw, 3*p*p], pixels [B, 3, H, W] or None)``, bit-equal to ``packed_patch_planes(tile_crops(img, origins,
+    tile_hw), order, ...)`` — which is what runs on a CPU tensor, with the ``torch`` backend and past the kernel's
+    limits. On the GPU one HIP launch reads every tile in place: tile ``b`` starts at a byte offset the kernel reads
+    from a device table (built here, cached beside the tap tables, dropped by :func:`invalidate_cache`)."""
+    if order not in PACKED_ORDERS:
+        raise ValueError(f"tiled: channel order {order!r} is none of {sorted(PACKED_ORDERS)}")
+    C = PACKED_ORDERS[order][0]
+    if isinstance(img, torch.Tensor) and img.dim() == 3:
+        img = img[None]
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() != 4 or img.shape[0] != 1 \
+            or img.shape[3] != C or 0 in img.shape:
+        raise ValueError(f"tiled: {order} takes one uint8 [h, w, {C}] (or [1, h, w, {C}]) frame")
+    if not _packed_strides(img):
+        raise ValueError("tiled: rows may be pitched, but the bytes of a row are contiguous "
+                         f"(stride(3) == 1, stride(2) == {C}, stride(1) >= {C} * w)")
+    _, h, w, _ = img.shape
+    th, tw = int(tile_hw[0]), int(tile_hw[1])
+    origins = _tile_origins(origins, th, tw, h, w, "tiled")
+    B = len(origins)
+    H, W = int(out_hw[0]), int(out_hw[1])
+    tabs = None
+    if _use_hip(img) and fusable((th, tw), (H, W), patch):
+        tabs = _device_tables(th, tw, H, W, patch, img.device)
+    if tabs is None or tabs[5] > PACKED_MAX_FOOTPRINT:
+        return packed_patch_planes(tile_crops(img, origins, (th, tw)), order, (H, W), patch, mean, std, want_pixels)
+    pitch = img.stride(1) if h > 1 else w * C
+    table = _tables.get(("tiles", origins, pitch, C, str(img.device)),
+                        lambda: torch.tensor([y * pitch + x * C for y, x in origins], dtype=torch.int64).to(img.device))
+    planes, pixels, gh, gw = _outputs(B, H, W, patch, want_pixels, img.device)
+    flat = (ctypes.c_int * (2 * B))(*[v for o in origins for v in o])
+    rc = _L().nos_image_patch_planes_tiles(img.data_ptr(), *_storage_bounds(img), pitch, order.encode(), flat,
+                                           table.data_ptr(), h, w,
+                                           *_tail_args(tabs, planes, pixels, mean, std, B, th, tw, H, W, patch, gh, gw))
+    _check(rc, "tiled_patch_planes")
     return planes, pixels
 
 
@@ -1156,3 +1271,109 @@ def detections(logits: torch.Tensor, boxes: torch.Tensor, target_sizes, threshol
                                  torch.cuda.current_stream().cuda_stream)
     _check(rc, "detections")
     return count, scores, labels, xyxy
+
+
+# ---- the detections of a frame's tiles, merged ------------------------------------------------------
+#: how two boxes' overlap is measured: ``ios`` — intersection over the smaller area (an object cut by a tile border
+#: gives a partial box inside the fuller one: IoS near 1, IoU small) — or ``iou`` (``nos_merge_detections_f32``'s flag)
+MATCHES = {"ios": 0, "iou": 1}
+
+
+def _merge_check(match: str, match_threshold: float) -> None:
+    if match not in MATCHES:
+        raise ValueError(f"merge_detections: match {match!r} is none of {tuple(MATCHES)}")
+    if not match_threshold >= 0.0:
+        raise ValueError(f"merge_detections: match_threshold {match_threshold!r} is not a number from 0 up")
+
+
+def pair_overlap(a: torch.Tensor, b: torch.Tensor, match: str = "ios") -> torch.Tensor:
+    """The overlap of corner boxes ``a [..., 4]`` and ``b [..., 4]`` (broadcast): ``inter / min(area_a, area_b)`` for
+    ``"ios"``, ``inter / union`` for ``"iou"``; a denominator that is not positive counts as overlap 0."""
+    iw = (torch.minimum(a[..., 2], b[..., 2]) - torch.maximum(a[..., 0], b[..., 0])).clamp_min(0)
+    ih = (torch.minimum(a[..., 3], b[..., 3]) - torch.maximum(a[..., 1], b[..., 1])).clamp_min(0)
+    inter = iw * ih
+    aa = (a[..., 2] - a[..., 0]) * (a[..., 3] - a[..., 1])
+    ab = (b[..., 2] - b[..., 0]) * (b[..., 3] - b[..., 1])
+    den = aa + ab - inter if match == "iou" else torch.minimum(aa, ab)
+    ok = den > 0
+    return torch.where(ok, inter / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den))
+
+
+def merge_detections_reference(logits: torch.Tensor, boxes: torch.Tensor, origins, tile_hw: Tuple[int, int],
+                               threshold: float, match: str = "ios", match_threshold: float = 0.5) \
+        -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The torch composition of :func:`merge_detections` in the inputs' precision, without a host sync (the greedy
+    pass is a loop of ``B * M`` steps on the device, each over one row of the pairwise match matrix)."""
+    _merge_check(match, match_threshold)
+    B, M, _ = logits.shape
+    N = B * M
+    dev = logits.device
+    org = origin_tensor(origins, dev)
+    if org.shape[0] != B:
+        raise ValueError("merge_detections: as many origins as tiles")
+    th, tw = float(tile_hw[0]), float(tile_hw[1])
+    prob = torch.softmax(logits, -1)
+    scores, labels = prob[..., :-1].max(-1)
+    cx, cy, bw, bh = boxes.unbind(-1)
+    oy, ox = org[:, :1].to(boxes.dtype), org[:, 1:].to(boxes.dtype)
+    xyxy = torch.stack(((cx - 0.5 * bw) * tw + ox, (cy - 0.5 * bh) * th + oy, (cx + 0.5 * bw) * tw + ox,
+                        (cy + 0.5 * bh) * th + oy), dim=-1).reshape(N, 4)
+    scores, labels = scores.reshape(N), labels.reshape(N)
+    tile = torch.arange(B, device=dev).repeat_interleave(M)
+    cand = scores > threshold
+    # candidates first, by score descending; the stable sort leaves ties in row (tile, then token) order
+    order = torch.sort(torch.where(cand, -scores, torch.full_like(scores, math.inf)), stable=True).indices
+    scores, labels, tile, xyxy, cand = scores[order], labels[order], tile[order], xyxy[order], cand[order]
+    ov = pair_overlap(xyxy[:, None, :], xyxy[None, :, :], match)
+    idx = torch.arange(N, device=dev)
+    # hit[p, k]: a kept p drops the later k
+    hit = (ov > match_threshold) & (labels[:, None] == labels[None, :]) & (tile[:, None] != tile[None, :]) \
+        & (idx[:, None] < idx[None, :]) & cand[:, None] & cand[None, :]
+    keep = cand.clone()
+    for p in range(N - 1):
+        keep &= ~(hit[p] & keep[p])
+    count = keep.sum().to(torch.int32).reshape(1)
+    front = torch.sort((~keep).to(torch.int8), stable=True).indices     # kept rows first, in order
+    live = idx < count
+    return (count, scores[front] * live, (labels[front] * live).to(torch.int32), xyxy[front] * live[:, None],
+            (tile[front] * live).to(torch.int32))
+
+
+def merge_detections(logits: torch.Tensor, boxes: torch.Tensor, origins, tile_hw: Tuple[int, int], threshold: float,
+                     match: str = "ios", match_threshold: float = 0.5) \
+        -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The detections of ``B`` tiles of one frame as one list, with no host synchronisation: ``logits [B, M, L+1]``,
+    ``boxes [B, M, 4]`` (centre format, 0..1 of a tile), ``origins`` the tiles' ``(y0, x0)`` in the frame (a list, or
+    an int32 ``[B, 2]`` tensor on the device), ``tile_hw`` their size -> ``(count [1] int32, scores [B*M], labels [B*M]
+    int32, boxes_xyxy [B*M, 4], tile [B*M] int32)``.
+
+    A row is a candidate when its score — :func:`detections`' — exceeds ``threshold``; its box in frame pixels is
+    ``((cx - w/2) tw + x0, (cy - h/2) th + y0, (cx + w/2) tw + x0, (cy + h/2) th + y0)``, not clipped. Candidates are
+    ordered by score descending (ties: tile, then token, ascending) and passed greedily: one is dropped when an earlier
+    *kept* one has the same label, comes from a *different* tile and overlaps it by more than ``match_threshold``
+    (:func:`pair_overlap`, ``match`` of :data:`MATCHES`). Boxes of one tile never suppress each other, so one tile
+    yields :func:`detections`' survivors stably sorted by score. The kept rows stand first in that order, zeros behind
+    them. One HIP launch (one workgroup) up to ``B * M`` = 1024 rows and 128 classes; past that, on the CPU and with
+    the ``torch`` backend :func:`merge_detections_reference`."""
+    _merge_check(match, match_threshold)
+    B, M, C = logits.shape
+    if not _use_hip(logits) or logits.dtype != torch.float32 or boxes.dtype != torch.float32 \
+            or B * M > MAX_ROWS or C > MAX_CLASSES or C < 2:
+        return merge_detections_reference(logits, boxes, origins, tile_hw, threshold, match, match_threshold)
+    dev = logits.device
+    org = origin_tensor(origins, dev)
+    if org.shape[0] != B:
+        raise ValueError("merge_detections: as many origins as tiles")
+    logits, boxes = logits.contiguous(), boxes.contiguous()
+    N = B * M
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    scores = torch.empty(N, dtype=torch.float32, device=dev)
+    labels = torch.empty(N, dtype=torch.int32, device=dev)
+    xyxy = torch.empty(N, 4, dtype=torch.float32, device=dev)
+    tile = torch.empty(N, dtype=torch.int32, device=dev)
+    rc = _L().nos_merge_detections_f32(logits.data_ptr(), boxes.data_ptr(), org.data_ptr(), float(tile_hw[0]),
+                                       float(tile_hw[1]), float(threshold), float(match_threshold), MATCHES[match],
+                                       B, M, C, count.data_ptr(), scores.data_ptr(), labels.data_ptr(),
+                                       xyxy.data_ptr(), tile.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    _check(rc, "merge_detections")
+    return count, scores, labels, xyxy, tile
