@@ -35,6 +35,10 @@
 //  * image_patch_planes_tiles3 / _tiles4 — the packed staging loops over B tiles of one frame: tile b starts at a byte
 //    offset read from a device table (tile origins on a 2-D grid are not one batch stride); [lo, hi) stays the frame's
 //    storage. Bit-equal to the packed entries on the B crops stacked.
+//  * image_patch_planes_yuv_tiles / _yuv_bilinear_tiles / _yuv_hdr_tiles<Yuv<...>> — the three YUV front ends over B
+//    tiles of one frame, the same instantiations: tile b's (first row, first column) is read from a device table (the
+//    one merge_detections_f32 reads) and moves the patch's footprint into the frame before the column groups are laid
+//    out, so the staging loops run unchanged on frame coordinates. Bit-equal to the tiles3 entry on the converted frame.
 //  * detections_f32 — softmax over the class logits, the best of the first L classes, the box in
 //    corner format scaled to the original image, and a stable compaction of the rows above the
 //    threshold; one workgroup per image, one wave per row.
@@ -121,7 +125,7 @@ struct PackedTileArgs : PackedArgs {
 // any GROUP_FMAX_W = 69 columns lie inside 18 consecutive groups wherever they start, so these layouts
 // cover footprints of up to 69 columns (scale 4 at patch 16); the host falls back past that.
 // YUV is the general front end (image_yuv.h): its staging loop is instantiated per Yuv<layout, hsub, sample bytes>.
-enum class Src { RGB, NV12, NV21, YUV420P, PACKED3, PACKED4, YUV, TILES3, TILES4 };
+enum class Src { RGB, NV12, NV21, YUV420P, PACKED3, PACKED4, YUV, TILES3, TILES4, YUV_TILES };
 constexpr int NG = RS / 12, GROUP_FMAX_W = NG * 4 - 3;
 constexpr int NV12_FMAX_W = GROUP_FMAX_W, YUV420P_FMAX_W = GROUP_FMAX_W, PACKED_FMAX_W = GROUP_FMAX_W;
 constexpr int YUV_FMAX_W = GROUP_FMAX_W;
@@ -147,6 +151,23 @@ struct YuvHdrArgs : YuvBilinearArgs {
   const uint8_t* lut2;
   int entries;
   int gamut[9];
+};
+// B tiles of one YUV frame (Src::YUV_TILES): tile b's first row and column are origin[2 * b] and origin[2 * b + 1], a
+// device table a graph replays, so it is trusted for nothing: h and w are the frame's, and a patch whose footprint,
+// shifted by the origin, does not lie inside them is skipped. The planes are one frame's (batch element 0). Types of
+// their own, so that the untiled kernels' arguments are what they were.
+struct TileFrame {
+  const int* origin;  // [B][2]
+  int h, w;
+};
+struct YuvTileArgs : YuvArgs {
+  TileFrame f;
+};
+struct YuvBilinearTileArgs : YuvBilinearArgs {
+  TileFrame f;
+};
+struct YuvHdrTileArgs : YuvHdrArgs {
+  TileFrame f;
 };
 enum { YUV_PLANAR = 0, YUV_SEMI = 1, YUV_PACKED = 2 };
 template <int LAYOUT_, int HSUB_, int SB_, int CHROMA_ = 0>
@@ -447,7 +468,12 @@ __device__ __forceinline__ void stage_yuv_bilinear(const A& n, int b, int sy, in
 }
 
 // SrcArgs: what the layout's staging loop reads besides ImgArgs (Nv12Args, PlanarArgs, PackedArgs, YuvArgs,
-// YuvBilinearArgs or YuvHdrArgs; the contiguous RGB source is ImgArgs::img and takes an empty Nv12Args). Y: Src::YUV's Yuv<...>.
+// YuvBilinearArgs or YuvHdrArgs, or their ...TileArgs; the contiguous RGB source is ImgArgs::img and takes an empty
+// Nv12Args). Y: Src::YUV's and Src::YUV_TILES' Yuv<...>.
+// Src::YUV_TILES: ImgArgs' h x w is the tile, the tap tables are the tile's, and the footprint they give is moved by
+// the tile's origin into the frame before the column groups are laid out: the groups are the frame's (whatever the
+// parity of the origin, a chroma pair lies under its luma as in the untiled launch), and the staging loops run on
+// frame coordinates with batch element 0, so bilinear chroma clamps at the frame's edge, not at the tile's.
 template <Src S, class SrcArgs, class Y = NoYuv>
 __device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const SrcArgs& n) {
   constexpr bool GROUPS = S != Src::RGB;
@@ -469,8 +495,18 @@ __device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const 
     const int fh = fy1 - fy0, fw = fx1 - fx0;
     // the host checked the tables against these limits; a table that breaks them reads nothing
     if (fy0 < 0 || fx0 < 0 || fy1 > a.h || fx1 > a.w || fh <= 0 || fw <= 0 || fh > FMAX || fw > FMAX) continue;
+    // tiles of a YUV frame: the tile's origin, read once per patch (b is the block's, so every lane reads the same
+    // pair; readfirstlane says so to the compiler, which keeps what follows from it in scalar registers); a footprint
+    // that it does not leave inside the frame reads nothing (fy1 and fx1 are positive: no overflow)
+    int oy = 0, ox = 0;
+    if constexpr (S == Src::YUV_TILES) {
+      oy = __builtin_amdgcn_readfirstlane(n.f.origin[2 * b]);
+      ox = __builtin_amdgcn_readfirstlane(n.f.origin[2 * b + 1]);
+      if (oy < 0 || ox < 0 || oy > n.f.h - fy1 || ox > n.f.w - fx1) continue;
+    }
     // all but RGB: column groups of 4, the first one holding fx0; lead bytes of a row in LDS, groups per row
-    const int gx0 = fx0 >> 2, lead = (fx0 & 3) * 3, ng = ((fx1 - 1) >> 2) - gx0 + 1;
+    const int sx0 = fx0 + ox, sx1 = fx1 + ox, sy0 = fy0 + oy;  // the footprint in the source's coordinates
+    const int gx0 = sx0 >> 2, lead = (sx0 & 3) * 3, ng = ((sx1 - 1) >> 2) - gx0 + 1;
     if (GROUPS && ng > NG) continue;
     __syncthreads();  // the previous tile's readers are done with the LDS
     if (tid < ny * TAPS) wys[tid] = a.ywt[size_t(y0) * TAPS + tid];
@@ -490,7 +526,7 @@ __device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const 
       for (int e = tid; e < fh * NG; e += 256) {
         const int r = e / NG, g = e % NG;
         if (g >= ng) continue;
-        const int sy = fy0 + r, sx = (gx0 + g) * 4;
+        const int sy = sy0 + r, sx = (gx0 + g) * 4;
         uint32_t* dst = reinterpret_cast<uint32_t*>(src + r * RS + g * 12);
         if constexpr (S == Src::NV12 || S == Src::NV21) {
           // 4 luma bytes and the 2 chroma pairs under them; NV21 has V in a pair's first byte
@@ -512,6 +548,9 @@ __device__ __forceinline__ void image_patch_planes_body(const ImgArgs& a, const 
         } else if constexpr (S == Src::YUV) {
           if constexpr (Y::CHROMA == 1) stage_yuv_bilinear<Y>(n, b, sy, sx, dst);
           else stage_yuv<Y>(n, b, sy, sx, dst);
+        } else if constexpr (S == Src::YUV_TILES) {
+          if constexpr (Y::CHROMA == 1) stage_yuv_bilinear<Y>(n, 0, sy, sx, dst);
+          else stage_yuv<Y>(n, 0, sy, sx, dst);
         } else {
           // 4 pixels of C = 3 or 4 bytes: their 12 or 16 bytes from the row's aligned dwords, then the three
           // colour bytes of each by their offsets in a pixel (a fourth byte is dropped here)
@@ -643,6 +682,22 @@ __global__ __launch_bounds__(256) void image_patch_planes_yuv_bilinear(ImgArgs a
 template <class Y>
 __global__ __launch_bounds__(256) void image_patch_planes_yuv_hdr(ImgArgs a, YuvHdrArgs n) {
   image_patch_planes_body<Src::YUV, YuvHdrArgs, Hdr<Y>>(a, n);
+}
+
+// B tiles of one frame through the same three front ends: the same instantiations, the tile's origin from a table
+template <class Y>
+__global__ __launch_bounds__(256) void image_patch_planes_yuv_tiles(ImgArgs a, YuvTileArgs n) {
+  image_patch_planes_body<Src::YUV_TILES, YuvTileArgs, Y>(a, n);
+}
+
+template <class Y>
+__global__ __launch_bounds__(256) void image_patch_planes_yuv_bilinear_tiles(ImgArgs a, YuvBilinearTileArgs n) {
+  image_patch_planes_body<Src::YUV_TILES, YuvBilinearTileArgs, Y>(a, n);
+}
+
+template <class Y>
+__global__ __launch_bounds__(256) void image_patch_planes_yuv_hdr_tiles(ImgArgs a, YuvHdrTileArgs n) {
+  image_patch_planes_body<Src::YUV_TILES, YuvHdrTileArgs, Hdr<Y>>(a, n);
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -948,12 +1003,13 @@ int patch_planes_semiplanar(const void* y, const void* y_lo, const void* y_hi, c
                      reinterpret_cast<hipStream_t>(stream), k, n);
   return check(vu ? "image_patch_planes_nv21" : "image_patch_planes_nv12");
 }
-// What both entries of the general YUV front end check and fill: every check of the descriptor and of the common
-// arguments, then the kernel's arguments k and n and the workgroups to launch.
+// What the entries of the general YUV front end check and fill: every check of the descriptor and of the common
+// arguments, then the kernel's arguments k and n and the workgroups to launch. sB x sh x sw: the batch and the size
+// of the source the descriptor's planes hold — B x h x w itself, or the one frame that B tiles of h x w are cut from.
 int yuv_args(const NosYuvSrc* src, ImgArgs& k, int& grid, YuvBilinearArgs& n, void* planes, float* pixels,
              const int* yidx, const float* ywt, const int* xidx, const float* xwt, int ytab, int xtab, int taps,
              int max_fh, int max_fw, const float* a, const float* b, int B, int h, int w, int H, int W, int p, int gh,
-             int gw, int wgs) {
+             int gw, int wgs, int sB, int sh, int sw) {
   if (!src) return fail("image_patch_planes: null operand");
   if (src->size != int(sizeof(NosYuvSrc)))
     return fail("image_patch_planes_yuv: descriptor size mismatch (NosYuvSrc of another build)");
@@ -984,10 +1040,11 @@ int yuv_args(const NosYuvSrc* src, ImgArgs& k, int& grid, YuvBilinearArgs& n, vo
   if (s.chroma == 1 && s.hsub == 0)
     return fail("image_patch_planes_yuv: bilinear chroma takes a subsampled source (4:4:4 is launched as nearest)");
   // rows and row bytes of every plane
-  const long long SB = s.sample_bytes, cw = (w + (1LL << s.hsub) - 1) >> s.hsub, ch = (h + (1LL << s.vsub) - 1) >> s.vsub;
+  const long long SB = s.sample_bytes, cw = (sw + (1LL << s.hsub) - 1) >> s.hsub,
+                  ch = (sh + (1LL << s.vsub) - 1) >> s.vsub;
   const int np = packed ? 1 : s.layout == YUV_SEMI ? 2 : 3;
-  const long long rows[3] = {h, ch, ch};
-  const long long rowbytes[3] = {packed ? 4 * ((w + 1LL) / 2) : w * SB, s.layout == YUV_SEMI ? 2 * cw * SB : cw * SB,
+  const long long rows[3] = {sh, ch, ch};
+  const long long rowbytes[3] = {packed ? 4 * ((sw + 1LL) / 2) : sw * SB, s.layout == YUV_SEMI ? 2 * cw * SB : cw * SB,
                                  cw * SB};
   for (int i = 0; i < np; ++i) {
     const NosYuvPlane& q = s.plane[i];
@@ -996,7 +1053,7 @@ int yuv_args(const NosYuvSrc* src, ImgArgs& k, int& grid, YuvBilinearArgs& n, vo
     if (!stride_range(q.pitch, q.bstride)) return fail("image_patch_planes_yuv: pitch or batch stride out of range");
     if (SB == 2 && ((reinterpret_cast<uintptr_t>(q.p) | uintptr_t(q.pitch) | uintptr_t(q.bstride)) & 1))
       return fail("image_patch_planes_yuv: 16-bit planes lie at an even address with an even pitch and batch stride");
-    if (!inside(B, q.p, q.lo, q.hi, q.bstride, rows[i], q.pitch, rowbytes[i]))
+    if (!inside(sB, q.p, q.lo, q.hi, q.bstride, rows[i], q.pitch, rowbytes[i]))
       return fail("image_patch_planes_yuv: a plane does not lie inside its storage bounds");
     n.pl[i] = plane_arg(q.p, q.lo, q.hi, q.pitch, q.bstride);
   }
@@ -1012,6 +1069,22 @@ int yuv_args(const NosYuvSrc* src, ImgArgs& k, int& grid, YuvBilinearArgs& n, vo
   static const int cosited[4] = {0, 4, 2, 2}, centred[4] = {1, 3, 3, 1};
   for (int i = 0; i < 4; ++i)
     n.wx[i] = (s.siting & 1 ? cosited : centred)[i], n.wy[i] = (s.siting & 2 ? cosited : centred)[i];
+  return 0;
+}
+
+// What both HDR entries check of the tables (after yuv_args) and fill of n.
+int hdr_args(const NosYuvSrc& s, const NosYuvHdr& hdr, YuvHdrArgs& n) {
+  if (s.sample_bytes != 2 || s.layout == YUV_PACKED)
+    return fail("image_patch_planes_yuv_hdr: a source of 16-bit samples (depth 10 or 12), planar or semi-planar");
+  if (hdr.entries != 1 << s.depth) return fail("image_patch_planes_yuv_hdr: lut1 has 2^depth entries");
+  if (!hdr.lut1 || !hdr.lut2) return fail("image_patch_planes_yuv_hdr: null table");
+  for (int i = 0; i < 9; ++i) {
+    if (std::abs(hdr.gamut[i]) >= (1 << 15))
+      return fail("image_patch_planes_yuv_hdr: gamut coefficients below 2^15 in size");
+    n.gamut[i] = hdr.gamut[i];
+  }
+  n.lut1 = static_cast<const uint16_t*>(hdr.lut1), n.lut2 = static_cast<const uint8_t*>(hdr.lut2);
+  n.entries = hdr.entries;
   return 0;
 }
 }  // namespace
@@ -1207,7 +1280,7 @@ int nos_image_patch_planes_yuv(const NosYuvSrc* src, void* planes, float* pixels
   int grid = 0;
   YuvBilinearArgs n{};
   if (const int rc = yuv_args(src, k, grid, n, planes, pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a,
-                              b, B, h, w, H, W, p, gh, gw, wgs))
+                              b, B, h, w, H, W, p, gh, gw, wgs, B, h, w))
     return rc;
   const NosYuvSrc& s = *src;
   if (s.chroma == 1) {
@@ -1253,20 +1326,10 @@ int nos_image_patch_planes_yuv_hdr(const NosYuvSrc* src, const NosYuvHdr* hdr, v
   int grid = 0;
   YuvHdrArgs n{};
   if (const int rc = yuv_args(src, k, grid, n, planes, pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a,
-                              b, B, h, w, H, W, p, gh, gw, wgs))
+                              b, B, h, w, H, W, p, gh, gw, wgs, B, h, w))
     return rc;
   const NosYuvSrc& s = *src;
-  if (s.sample_bytes != 2 || s.layout == YUV_PACKED)
-    return fail("image_patch_planes_yuv_hdr: a source of 16-bit samples (depth 10 or 12), planar or semi-planar");
-  if (hdr->entries != 1 << s.depth) return fail("image_patch_planes_yuv_hdr: lut1 has 2^depth entries");
-  if (!hdr->lut1 || !hdr->lut2) return fail("image_patch_planes_yuv_hdr: null table");
-  for (int i = 0; i < 9; ++i) {
-    if (std::abs(hdr->gamut[i]) >= (1 << 15))
-      return fail("image_patch_planes_yuv_hdr: gamut coefficients below 2^15 in size");
-    n.gamut[i] = hdr->gamut[i];
-  }
-  n.lut1 = static_cast<const uint16_t*>(hdr->lut1), n.lut2 = static_cast<const uint8_t*>(hdr->lut2);
-  n.entries = hdr->entries;
+  if (const int rc = hdr_args(s, *hdr, n)) return rc;
   void (*kern)(ImgArgs, YuvHdrArgs) = nullptr;
   switch ((s.layout == YUV_SEMI ? 3 : 0) + (s.chroma == 1 ? 2 : s.hsub)) {
     case 0: kern = image_patch_planes_yuv_hdr<Yuv<YUV_PLANAR, 0, 2>>; break;
@@ -1278,6 +1341,86 @@ int nos_image_patch_planes_yuv_hdr(const NosYuvSrc* src, const NosYuvHdr* hdr, v
   }
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k, n);
   return check("image_patch_planes_yuv_hdr");
+}
+
+// B tiles of tile_h x tile_w pixels (h and w of the common arguments) of one YUV frame of frame_h x frame_w, as
+// nos_image_patch_planes_yuv (hdr null) or nos_image_patch_planes_yuv_hdr gives for the B crops of the converted frame
+// stacked. src describes the frame's planes; frames is the batch they hold, which must be 1. origins: host array
+// [B][2] of every tile's first row and column; table: the same as a device array of int32 (a graph holds it; it is
+// the one nos_merge_detections_f32 reads). Every check of those entries against the frame's size; nothing is launched
+// unless they pass and every tile lies inside the frame. The kernel skips a patch that the table moves out of the
+// frame, and reads no byte outside a plane's [lo, hi) whatever the table holds.
+int nos_image_patch_planes_yuv_tiles(const NosYuvSrc* src, const NosYuvHdr* hdr, const int* origins, const int* table,
+                                     int frame_h, int frame_w, int frames, void* planes, float* pixels,
+                                     const int* yidx, const float* ywt, const int* xidx, const float* xwt, int ytab,
+                                     int xtab, int taps, int max_fh, int max_fw, const float* a, const float* b, int B,
+                                     int h, int w, int H, int W, int p, int gh, int gw, int wgs, void* stream) {
+  if (!origins || !table) return fail("image_patch_planes_yuv_tiles: null origin table");
+  if (frames != 1) return fail("image_patch_planes_yuv_tiles: tiles are cut from one frame (a source batch of 1)");
+  if (frame_h <= 0 || frame_w <= 0) return fail("image_patch_planes_yuv_tiles: the frame's sizes must be positive");
+  if (hdr && hdr->size != int(sizeof(NosYuvHdr)))
+    return fail("image_patch_planes_yuv_hdr: table descriptor size mismatch (NosYuvHdr of another build)");
+  ImgArgs k{};
+  int grid = 0;
+  YuvHdrTileArgs n{};
+  if (const int rc = yuv_args(src, k, grid, n, planes, pixels, yidx, ywt, xidx, xwt, ytab, xtab, taps, max_fh, max_fw, a,
+                              b, B, h, w, H, W, p, gh, gw, wgs, 1, frame_h, frame_w))
+    return rc;
+  const NosYuvSrc& s = *src;
+  if (hdr)
+    if (const int rc = hdr_args(s, *hdr, n)) return rc;
+  for (int t = 0; t < B; ++t) {
+    const long long y0 = origins[2 * t], x0 = origins[2 * t + 1];
+    if (y0 < 0 || x0 < 0 || y0 + h > frame_h || x0 + w > frame_w)
+      return fail("image_patch_planes_yuv_tiles: a tile does not lie inside the frame");
+  }
+  n.f = TileFrame{table, frame_h, frame_w};
+  const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (hdr) {
+    void (*kern)(ImgArgs, YuvHdrTileArgs) = nullptr;
+    switch ((s.layout == YUV_SEMI ? 3 : 0) + (s.chroma == 1 ? 2 : s.hsub)) {
+      case 0: kern = image_patch_planes_yuv_hdr_tiles<Yuv<YUV_PLANAR, 0, 2>>; break;
+      case 1: kern = image_patch_planes_yuv_hdr_tiles<Yuv<YUV_PLANAR, 1, 2>>; break;
+      case 2: kern = image_patch_planes_yuv_hdr_tiles<Yuv<YUV_PLANAR, 1, 2, 1>>; break;
+      case 3: kern = image_patch_planes_yuv_hdr_tiles<Yuv<YUV_SEMI, 0, 2>>; break;
+      case 4: kern = image_patch_planes_yuv_hdr_tiles<Yuv<YUV_SEMI, 1, 2>>; break;
+      default: kern = image_patch_planes_yuv_hdr_tiles<Yuv<YUV_SEMI, 1, 2, 1>>; break;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, k, n);
+    return check("image_patch_planes_yuv_tiles");
+  }
+  if (s.chroma == 1) {
+    YuvBilinearTileArgs nb{};
+    static_cast<YuvBilinearArgs&>(nb) = n;
+    nb.f = n.f;
+    void (*bilinear)(ImgArgs, YuvBilinearTileArgs) = nullptr;
+    switch (s.layout * 2 + (s.sample_bytes - 1)) {
+      case 0: bilinear = image_patch_planes_yuv_bilinear_tiles<Yuv<YUV_PLANAR, 1, 1, 1>>; break;
+      case 1: bilinear = image_patch_planes_yuv_bilinear_tiles<Yuv<YUV_PLANAR, 1, 2, 1>>; break;
+      case 2: bilinear = image_patch_planes_yuv_bilinear_tiles<Yuv<YUV_SEMI, 1, 1, 1>>; break;
+      case 3: bilinear = image_patch_planes_yuv_bilinear_tiles<Yuv<YUV_SEMI, 1, 2, 1>>; break;
+      default: bilinear = image_patch_planes_yuv_bilinear_tiles<Yuv<YUV_PACKED, 1, 1, 1>>; break;
+    }
+    hipLaunchKernelGGL(bilinear, dim3(grid), dim3(256), 0, st, k, nb);
+    return check("image_patch_planes_yuv_tiles");
+  }
+  YuvTileArgs nn{};
+  static_cast<YuvArgs&>(nn) = n;
+  nn.f = n.f;
+  void (*kern)(ImgArgs, YuvTileArgs) = nullptr;
+  switch (s.layout * 4 + s.hsub * 2 + (s.sample_bytes - 1)) {
+    case 0: kern = image_patch_planes_yuv_tiles<Yuv<YUV_PLANAR, 0, 1>>; break;
+    case 1: kern = image_patch_planes_yuv_tiles<Yuv<YUV_PLANAR, 0, 2>>; break;
+    case 2: kern = image_patch_planes_yuv_tiles<Yuv<YUV_PLANAR, 1, 1>>; break;
+    case 3: kern = image_patch_planes_yuv_tiles<Yuv<YUV_PLANAR, 1, 2>>; break;
+    case 4: kern = image_patch_planes_yuv_tiles<Yuv<YUV_SEMI, 0, 1>>; break;
+    case 5: kern = image_patch_planes_yuv_tiles<Yuv<YUV_SEMI, 0, 2>>; break;
+    case 6: kern = image_patch_planes_yuv_tiles<Yuv<YUV_SEMI, 1, 1>>; break;
+    case 7: kern = image_patch_planes_yuv_tiles<Yuv<YUV_SEMI, 1, 2>>; break;
+    default: kern = image_patch_planes_yuv_tiles<Yuv<YUV_PACKED, 1, 1>>; break;
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, k, nn);
+  return check("image_patch_planes_yuv_tiles");
 }
 
 // logits [B][M][C] fp32, boxes [B][M][4] fp32, target [B][2] fp32 (height, width), all on the device ->

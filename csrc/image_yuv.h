@@ -61,6 +61,16 @@ int nos_image_patch_planes_yuv_hdr(const NosYuvSrc* src, const NosYuvHdr* hdr, v
                                    int xtab, int taps, int max_fh, int max_fw, const float* a, const float* b, int B,
                                    int h, int w, int H, int W, int p, int gh, int gw, int wgs, void* stream);
 
+// B tiles of h x w (the common arguments' sizes) of one frame of frame_h x frame_w, which src describes; hdr is null
+// for an SDR source. origins: host array [B][2] of (first row, first column); table: the same on the device, int32.
+// frames: the batch src's planes hold, which must be 1. As the two entries above on the crops of the converted frame,
+// bit for bit; nothing is launched unless their checks pass for the frame and every tile lies inside it.
+int nos_image_patch_planes_yuv_tiles(const NosYuvSrc* src, const NosYuvHdr* hdr, const int* origins, const int* table,
+                                     int frame_h, int frame_w, int frames, void* planes, float* pixels,
+                                     const int* yidx, const float* ywt, const int* xidx, const float* xwt, int ytab,
+                                     int xtab, int taps, int max_fh, int max_fw, const float* a, const float* b, int B,
+                                     int h, int w, int H, int W, int p, int gh, int gw, int wgs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,12 @@ Three rows time tiled detection (``--rows tiles`` runs them alone) on a 2160x384
 0.2 — tiles of 1200x2134 resized to 736x1328: ``tiles_planes_*``, the one tile launch against four
 ``packed_patch_planes`` launches on the crop views; ``merge_n400_*`` / ``merge_n900_*``, ``merge_detections`` of 4 and 9
 tiles of 100 rows against its torch reference; and, on the whole GPU only, ``detect_tiled_ms`` against four
-``detect_image`` calls on the crops (``detect_image_x4_ms``).
+``detect_image`` calls on the crops (``detect_image_x4_ms``). Three more time the tiles of a YUV frame of that size
+staged in place from its planes (``Frame.tile_planes``: ``*_hip_us``) against the route it replaces, the frame's
+``rgb()`` followed by the packed tile launch (``*_torch_us``): ``yuv_tiles_nv12_*``, ``yuv_tiles_nv12_bilinear_*``
+(siting ``left``) and ``yuv_tiles_p010_pq_*`` (BT.2020, peak 1000 nits); and, on the whole GPU only,
+``detect_tiled_nv12_ms`` against ``detect_tiled`` of the converted frame, conversion included
+(``detect_tiled_nv12_rgb_ms``).
 """
 from __future__ import annotations
 
@@ -407,6 +412,19 @@ def tiles_rows(r, pair, s, iters, rounds, whole_gpu):
         r[f"merge_n{B * 100}_torch_us"] = round(statistics.median(t["torch"]), 1)
         r[f"merge_n{B * 100}_rounds_us"] = {k: [round(v, 1) for v in vs] for k, vs in t.items()}
         r[f"merge_n{B * 100}_kept"] = int(I.merge_detections(lg, bx, org, (th, tw), 0.1)[0].item())
+    # the tiles of a YUV frame: staged from the planes by one launch, against rgb() and the packed tile launch
+    from dataclasses import replace
+
+    from walkai_nos_amd.models.workload import surfaces
+    from walkai_nos_amd.models.workload.processor import Nv12
+    nv12 = Nv12.from_buffer(torch.randint(0, 256, (3840 * 2160 * 3 // 2,), generator=g, dtype=torch.uint8).cuda(),
+                            2160, 3840)
+    p010 = surfaces.from_buffer("p010", torch.randint(0, 256, (3840 * 2160 * 3,), generator=g, dtype=torch.uint8).cuda(),
+                                2160, 3840, matrix="bt2020", transfer="pq")
+    for name, fr in (("nv12", nv12), ("nv12_bilinear", replace(nv12, chroma="bilinear")), ("p010_pq", p010)):
+        pair(r, f"yuv_tiles_{name}", lambda: fr.tile_planes(origins, (th, tw), out, 16, IMAGENET_MEAN, IMAGENET_STD),
+             lambda: I.tiled_patch_planes(fr.rgb(), "rgb", origins, (th, tw), out, 16, IMAGENET_MEAN, IMAGENET_STD),
+             s, iters)
     if not whole_gpu:
         return
     with torch.cuda.stream(s), torch.no_grad():
@@ -419,6 +437,14 @@ def tiles_rows(r, pair, s, iters, rounds, whole_gpu):
     r["detect_tiled_ms"] = round(statistics.median(t["detect_tiled"]) / 1000.0, 3)
     r["detect_image_x4_ms"] = round(statistics.median(t["detect_image_x4"]) / 1000.0, 3)
     r["tiles_model_rounds_ms"] = {k: [round(v / 1000.0, 3) for v in vs] for k, vs in t.items()}
+    with torch.cuda.stream(s), torch.no_grad():
+        t = {"detect_tiled_nv12": [], "detect_tiled_nv12_rgb": []}
+        for _ in range(rounds):
+            t["detect_tiled_nv12"].append(timeit(lambda: m.detect_tiled(nv12, (2, 2), 0.2), s, it))
+            t["detect_tiled_nv12_rgb"].append(timeit(lambda: m.detect_tiled(nv12.rgb()[0], (2, 2), 0.2), s, it))
+    for k, vs in t.items():
+        r[f"{k}_ms"] = round(statistics.median(vs) / 1000.0, 3)
+    r["yuv_tiles_model_rounds_ms"] = {k: [round(v / 1000.0, 3) for v in vs] for k, vs in t.items()}
 
 
 def free_running(slots, seconds: float) -> int:

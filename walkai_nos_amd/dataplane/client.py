@@ -27,7 +27,8 @@ decoder's ``p010`` / ``p210`` / ``p410``, ``i010`` (``yuv420p10le``) and their 1
 pq|hlg`` (with ``--peak-nits``) that a 10- or 12-bit format's codes are HDR and are tone-mapped to SDR in that launch.
 ``--tiles R,C`` runs a large frame as ``R x C`` overlapping tiles in one batch (``YolosSmall.detect_tiled``;
 ``--tile-overlap``, ``--match ios|iou``, ``--match-threshold``): the JSON line then carries ``"tiles"``, the tile count,
-and ``"detections"`` counts the merged boxes.
+and ``"detections"`` counts the merged boxes. With a YUV ``--pixel-format`` (and ``--transfer``, ``--peak-nits``) the
+tiles are staged straight from the surface's planes: no flag, the frame's own ``tile_planes``.
 """
 from __future__ import annotations
 

@@ -61,6 +61,13 @@ class Frame:
         """``ops.image.image_patch_planes`` of :meth:`rgb`, by this layout's fused launch."""
         raise NotImplementedError
 
+    def tile_planes(self, origins, tile_hw: Tuple[int, int], hw: Tuple[int, int], patch: int, mean: Sequence[float],
+                    std: Sequence[float], want_pixels: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """:meth:`patch_planes` of the tiles of this one frame, each ``tile_hw`` large at its ``(y0, x0)`` of
+        ``origins`` and resized to ``hw``: ``ops.image.tiled_patch_planes`` of :meth:`rgb`. A layout with a tile
+        launch of its own answers with that instead, bit for bit the same."""
+        return I.tiled_patch_planes(self.rgb(), "rgb", origins, tile_hw, hw, patch, mean, std, want_pixels)
+
     @property
     def device(self) -> torch.device:
         return getattr(self, self.PLANES[0]).device
@@ -153,6 +160,12 @@ class Nv12(Frame):
                                        want_pixels, vu=True)
         return I.nv12_patch_planes(self.y, self.uv, hw, patch, mean, std, self.matrix, self.full_range, want_pixels)
 
+    def tile_planes(self, origins, tile_hw, hw, patch, mean, std, want_pixels=False):
+        # the general entry's semi-planar 4:2:0 at depth 8, with either chroma
+        return I.yuv_semiplanar_tiled_patch_planes(self.y, self.uv, origins, tile_hw, hw, patch, mean, std, "420", 8,
+                                                   False, self.matrix, self.full_range, want_pixels, self.vu,
+                                                   self.chroma, self.siting)
+
 
 @dataclass(frozen=True)
 class Yuv420p(Frame):
@@ -227,6 +240,12 @@ class Yuv420p(Frame):
         return I.yuv420p_patch_planes(self.y, self.u, self.v, hw, patch, mean, std, self.matrix, self.full_range,
                                       want_pixels)
 
+    def tile_planes(self, origins, tile_hw, hw, patch, mean, std, want_pixels=False):
+        # the general entry's planar 4:2:0 at depth 8, with either chroma
+        return I.yuv_planar_tiled_patch_planes(self.y, self.u, self.v, origins, tile_hw, hw, patch, mean, std, "420", 8,
+                                               False, self.matrix, self.full_range, want_pixels, self.chroma,
+                                               self.siting)
+
 
 @dataclass(frozen=True)
 class Packed(Frame):
@@ -263,6 +282,9 @@ class Packed(Frame):
 
     def patch_planes(self, hw, patch, mean, std, want_pixels=False):
         return I.packed_patch_planes(self.batched(), self.order, hw, patch, mean, std, want_pixels)
+
+    def tile_planes(self, origins, tile_hw, hw, patch, mean, std, want_pixels=False):
+        return I.tiled_patch_planes(self.batched(), self.order, origins, tile_hw, hw, patch, mean, std, want_pixels)
 
 
 class YolosProcessor:
@@ -324,9 +346,10 @@ class YolosProcessor:
 
     @staticmethod
     def as_packed(img: Any) -> Tuple[torch.Tensor, str]:
-        """``(data [1, h, w, C], order)`` of :meth:`as_batch`'s result for the tile launch: a tensor or a
-        :class:`Packed` frame as it lies; any other :class:`Frame` (NV12, P010 and the rest) converted once by its
-        ``rgb()`` — the YUV staging loops take no tile origins."""
+        """``(data [1, h, w, C], order)`` of :meth:`as_batch`'s result for the packed tile launch and for the stacked
+        crops: a tensor or a :class:`Packed` frame as it lies; any other :class:`Frame` (NV12, P010 and the rest)
+        converted once by its ``rgb()``. (On the GPU such a frame's tiles need no conversion: its
+        :meth:`Frame.tile_planes` stages them from the planes, which is what :meth:`frame_tile_planes` asks for.)"""
         if isinstance(img, Packed):
             data, order = img.batched(), img.order
         else:
@@ -342,6 +365,20 @@ class YolosProcessor:
         ``(y0, x0)`` of ``origins`` and resized to ``hw``, by one launch (``ops.image.tiled_patch_planes``)."""
         return I.tiled_patch_planes(data, order, origins, tile_hw, hw, self.patch if patch is None else patch,
                                     self.mean, self.std, want_pixels)
+
+    @staticmethod
+    def tiles_in_place(img: Any) -> bool:
+        """True for :meth:`as_batch`'s result when it is a :class:`Frame` other than :class:`Packed`: its tiles are
+        staged by :meth:`frame_tile_planes`, not from :meth:`as_packed`'s pixels."""
+        return isinstance(img, Frame) and not isinstance(img, Packed)
+
+    def frame_tile_planes(self, frame: Frame, origins, tile_hw: Tuple[int, int], hw: Tuple[int, int],
+                          want_pixels: bool = False, patch: Optional[int] = None) \
+            -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """:meth:`tile_planes` of a :class:`Frame` as it lies, by the frame's own tile launch
+        (:meth:`Frame.tile_planes`): a YUV frame is not converted first."""
+        return frame.tile_planes(origins, tile_hw, hw, self.patch if patch is None else patch, self.mean, self.std,
+                                 want_pixels)
 
     @staticmethod
     def results(count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor) \

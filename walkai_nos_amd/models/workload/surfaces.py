@@ -88,6 +88,11 @@ class YuvPlanar(Frame):
                                          self.msb, self.matrix, self.full_range, want_pixels, self.chroma, self.siting,
                                          self.transfer, self.peak_nits)
 
+    def tile_planes(self, origins, tile_hw, hw, patch, mean, std, want_pixels=False):
+        return I.yuv_planar_tiled_patch_planes(self.y, self.u, self.v, origins, tile_hw, hw, patch, mean, std,
+                                               self.subsampling, self.depth, self.msb, self.matrix, self.full_range,
+                                               want_pixels, self.chroma, self.siting, self.transfer, self.peak_nits)
+
 
 @dataclass(frozen=True)
 class YuvSemiPlanar(Frame):
@@ -128,6 +133,12 @@ class YuvSemiPlanar(Frame):
                                              self.msb, self.matrix, self.full_range, want_pixels, self.vu, self.chroma,
                                              self.siting, self.transfer, self.peak_nits)
 
+    def tile_planes(self, origins, tile_hw, hw, patch, mean, std, want_pixels=False):
+        return I.yuv_semiplanar_tiled_patch_planes(self.y, self.uv, origins, tile_hw, hw, patch, mean, std,
+                                                   self.subsampling, self.depth, self.msb, self.matrix,
+                                                   self.full_range, want_pixels, self.vu, self.chroma, self.siting,
+                                                   self.transfer, self.peak_nits)
+
 
 @dataclass(frozen=True)
 class Yuyv(Frame):
@@ -161,6 +172,10 @@ class Yuyv(Frame):
     def patch_planes(self, hw, patch, mean, std, want_pixels=False):
         return I.yuyv_patch_planes(self.data, self.width, self.order, hw, patch, mean, std, self.matrix,
                                    self.full_range, want_pixels, self.chroma, self.siting)
+
+    def tile_planes(self, origins, tile_hw, hw, patch, mean, std, want_pixels=False):
+        return I.yuyv_tiled_patch_planes(self.data, self.width, self.order, origins, tile_hw, hw, patch, mean, std,
+                                         self.matrix, self.full_range, want_pixels, self.chroma, self.siting)
 
 
 #: name -> (layout, subsampling, depth, value in the high bits, second chroma first)

@@ -21,7 +21,8 @@ DETR-style MLP heads) built for the MI355X inference path:
   launch each (:mod:`walkai_nos_amd.ops.image`, :mod:`.processor`);
 * ``detect_tiled`` runs a frame too large for one input as ``R x C`` overlapping tiles in one batch — one tile-staging
   launch, one patch GEMM, the fused heads on all ``B x nd`` rows — and merges the tiles' detections in frame pixels by
-  one more launch (``ops.image.tiled_patch_planes`` / ``merge_detections``), still without a host synchronisation;
+  one more launch (``ops.image.tiled_patch_planes`` / ``merge_detections``), still without a host synchronisation; a
+  YUV frame's tiles are staged straight from its planes (``Frame.tile_planes``), not from its ``rgb()``;
 * the last block runs on the detection rows only ("detection tail"). ``detect`` reads nothing but
   the last ``nd`` = 100 rows, and a row of a block's output depends on the other rows only through K
   and V: so in the last block the attention queries, the projection, LN2, fc1, GELU and fc2 of the
@@ -423,20 +424,30 @@ class YolosSmall(nn.Module):
         (``ops.image.tiled_patch_planes``), one patch GEMM at ``M = B * P`` writes a temporary (bias and the position
         rows fused, broadcast over the tiles) that one copy puts into the patch rows of ``B`` token templates, the
         blocks run with the detection tail, and the final LayerNorm and both heads run fused on the ``B * nd`` rows.
-        Elsewhere it is ``detect(encode_detection(processor.preprocess(stacked crops)))`` and the merge. A
-        ``processor.Frame`` other than ``Packed`` is converted once by its ``rgb()`` and then tiled."""
+        Elsewhere it is ``detect(encode_detection(processor.preprocess(stacked crops)))`` and the merge. On that fused
+        route a ``processor.Frame`` other than ``Packed`` (NV12, P010, YUY2 ...) is not converted: its
+        ``tile_planes`` stages the tiles straight from the planes, bit-equal to the packed launch on its ``rgb()``;
+        elsewhere it is converted once by its ``rgb()`` and then tiled."""
         img = self.processor.as_batch(image_u8, self.pos_embed.device)
-        data, order = self.processor.as_packed(img)
+        if img.shape[0] != 1:
+            raise ValueError(f"tiles are cut from one frame, not from a batch of {img.shape[0]}")
         nd, p = self.c.num_detection_tokens, self.c.patch_size
-        th, tw, origins = self.processor.tile_plan(tuple(data.shape[1:3]), tiles, overlap, nd)
+        th, tw, origins = self.processor.tile_plan(tuple(img.shape[1:3]), tiles, overlap, nd)
         hw = self.processor.size((th, tw))
         B = len(origins)
-        if (data.is_cuda and K.x3_active(self.pos_embed) and self.c.num_channels == 3 and (3 * p * p) % 32 == 0
-                and I.fusable((th, tw), hw, p)):
+        fused = (img.is_cuda and K.x3_active(self.pos_embed) and self.c.num_channels == 3 and (3 * p * p) % 32 == 0
+                 and I.fusable((th, tw), hw, p))
+        in_place = fused and self.processor.tiles_in_place(img)
+        if not in_place:
+            data, order = self.processor.as_packed(img)
+        if fused:
             from ...ops.gemm import gemm_x3
             pe, mid = self.position_embeddings(hw)
             P = (hw[0] // p) * (hw[1] // p)
-            planes, _ = self.processor.tile_planes(data, order, origins, (th, tw), hw, patch=p)
+            if in_place:
+                planes, _ = self.processor.frame_tile_planes(img, origins, (th, tw), hw, patch=p)
+            else:
+                planes, _ = self.processor.tile_planes(data, order, origins, (th, tw), hw, patch=p)
             rows = gemm_x3(planes, self.patch.weight.reshape(self.patch.weight.shape[0], -1), self.patch.bias,
                            residual2=pe[0, 1:1 + P])
             x = self.token_template(hw).repeat(B, 1, 1)
@@ -454,7 +465,7 @@ class YolosSmall(nn.Module):
             if order != "rgb":
                 crops = I.packed_to_rgb(crops, order)
             logits, boxes = self.detect(self.encode_detection(self.processor.preprocess(crops)))
-        org = I.origin_tensor(origins, data.device)
+        org = I.origin_tensor(origins, img.device)
         count, scores, labels, xyxy, tile = I.merge_detections(logits, boxes, org, (th, tw), threshold, match,
                                                                match_threshold)
         return {"logits": logits, "pred_boxes": boxes, "origins": org.clone(), "tile_hw": (th, tw), "count": count,

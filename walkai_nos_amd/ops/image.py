@@ -58,8 +58,11 @@ which is also what runs on the CPU, with the ``torch`` backend and past a layout
   (the packed staging loops with a per-tile byte offset from a cached device table), and the tiles' detections mapped
   to frame pixels and merged by one launch — ordered by score, a box dropped when a kept box of the same label from
   *another* tile overlaps it by more than ``match_threshold`` (``inter / min(area)`` by default, or IoU). Tiles of
-  unequal size, merging boxes instead of suppressing, YUV tiles staged without ``rgb()`` and more than 1024 rows are
-  not offered.
+  unequal size, merging boxes instead of suppressing and more than 1024 rows are not offered.
+* :func:`yuv_planar_tiled_patch_planes`, :func:`yuv_semiplanar_tiled_patch_planes`, :func:`yuyv_tiled_patch_planes` —
+  the tiles of one YUV frame staged straight from its planes by one launch (every layout, depth, chroma mode and
+  transfer of the general YUV front end; the tile origins come from :func:`origin_tensor`'s table, the one the merge
+  reads), bit-equal to :func:`tiled_patch_planes` of the converted frame: no RGB frame is written and read back.
 """
 from __future__ import annotations
 
@@ -127,6 +130,9 @@ def _L() -> ctypes.CDLL:
             L.nos_detections_f32.argtypes = [vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, vp, vp]
             L.nos_image_patch_planes_tiles.argtypes = [vp, vp, vp, i64, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int),
                                                        vp, i32, i32] + L.nos_image_patch_planes_u8.argtypes[1:]
+            L.nos_image_patch_planes_yuv_tiles.argtypes = [ctypes.POINTER(NosYuvSrc), ctypes.POINTER(NosYuvHdr),
+                                                           ctypes.POINTER(ctypes.c_int), vp, i32, i32, i32] + \
+                L.nos_image_patch_planes_u8.argtypes[1:]
             L.nos_merge_detections_f32.argtypes = [vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, i32, vp, vp, vp, vp,
                                                    vp, vp]
             L.nos_image_last_error.restype = ctypes.c_char_p
@@ -1215,6 +1221,115 @@ def yuyv_patch_planes(data: torch.Tensor, width: int, order: str, out_hw: Tuple[
                                   mean, std, want_pixels)
     src = yuv_src(YUV_PACKED, (data,), "422", 8, False, tuple(YUYV_ORDERS).index(order), table, chroma, siting)
     return _yuv_launch(src, tabs, B, h, w, H, W, patch, mean, std, want_pixels, data.device, "yuyv_patch_planes")
+
+
+# ---- tiles of one YUV frame -----------------------------------------------------------------------
+def _yuv_tiles(first: torch.Tensor, hw: Tuple[int, int], origins, tile_hw: Tuple[int, int], out_hw: Tuple[int, int],
+               patch: int, who: str) -> Tuple[tuple, int, int, int, int, Optional[tuple]]:
+    """What the three tiled YUV functions check and plan: ``(origins, th, tw, H, W, tabs)``; ``tabs`` are the tile's
+    tap tables when the launch takes this call, else None (the composition runs)."""
+    if first.shape[0] != 1:
+        raise ValueError(f"{who}: tiles are cut from one frame, not from a batch of {first.shape[0]}")
+    th, tw = int(tile_hw[0]), int(tile_hw[1])
+    origins = _tile_origins(origins, th, tw, hw[0], hw[1], who)
+    H, W = int(out_hw[0]), int(out_hw[1])
+    return origins, th, tw, H, W, _yuv_fused(first, (th, tw), (H, W), patch)
+
+
+def _yuv_tiles_launch(src: NosYuvSrc, tabs: tuple, origins: tuple, hw: Tuple[int, int], th: int, tw: int, H: int,
+                      W: int, patch: int, mean, std, want_pixels: bool, device: torch.device, what: str,
+                      hdr: Optional[tuple] = None):
+    """:func:`_yuv_launch` of the ``len(origins)`` tiles of the one ``hw`` frame ``src`` describes; the device table
+    is :func:`origin_tensor`'s, the one :func:`merge_detections` reads."""
+    B = len(origins)
+    table = origin_tensor(origins, device)
+    planes, pixels, gh, gw = _outputs(B, H, W, patch, want_pixels, device)
+    flat = (ctypes.c_int * (2 * B))(*[v for o in origins for v in o])
+    tables = None if hdr is None else ctypes.byref(yuv_hdr(*_hdr_device_tables(*hdr, device)))
+    rc = _L().nos_image_patch_planes_yuv_tiles(ctypes.byref(src), tables, flat, table.data_ptr(), hw[0], hw[1], 1,
+                                               *_tail_args(tabs, planes, pixels, mean, std, B, th, tw, H, W, patch,
+                                                           gh, gw))
+    _check(rc, what)
+    return planes, pixels
+
+
+def yuv_planar_tiled_patch_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, origins,
+                                  tile_hw: Tuple[int, int], out_hw: Tuple[int, int], patch: int,
+                                  mean: Sequence[float], std: Sequence[float], subsampling: str = "420",
+                                  depth: int = 8, msb: bool = False, matrix: str = "bt601", full_range: bool = False,
+                                  want_pixels: bool = False, chroma: str = "nearest", siting: str = "left",
+                                  transfer: str = "sdr", peak_nits: float = 1000.0) \
+        -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """:func:`yuv_planar_patch_planes` of ``B`` tiles of one planar frame (a batch of 1) without converting or
+    stacking them: ``origins`` the ``(y0, x0)`` of the tiles, each ``tile_hw`` large and resized to ``out_hw`` ->
+    ``(planes [3, B*gh*gw, 3*p*p], pixels [B, 3, H, W] or None)``, bit-equal to ``image_patch_planes(tile_crops(
+    yuv_to_rgb(y, u, v, ...), origins, tile_hw), ...)`` — which is what runs on a CPU tensor, with the ``torch``
+    backend and past the kernel's limits — and so to :func:`tiled_patch_planes` of the converted frame. On the GPU
+    one HIP launch stages every tile from the planes in place: the kernel reads tile ``b``'s origin from
+    :func:`origin_tensor`'s device table (cached, dropped by :func:`invalidate_cache`) and moves the patch's
+    footprint into the frame, so a chroma sample lies under its luma whatever the origin's parity, and bilinear
+    chroma clamps at the frame's edge, not at the tile's."""
+    y, u, v = yuv_planes(y, u, v, subsampling, depth)
+    table = yuv_table(matrix, full_range, depth)
+    _chroma_check(chroma, siting)
+    _transfer_check(transfer, peak_nits, depth)
+    _, h, w = y.shape
+    origins, th, tw, H, W, tabs = _yuv_tiles(y, (h, w), origins, tile_hw, out_hw, patch, "yuv_planar_tiled")
+    if tabs is None:
+        rgb = yuv_to_rgb(y, u, v, subsampling, depth, msb, matrix, full_range, chroma, siting, transfer, peak_nits)
+        return image_patch_planes(tile_crops(rgb, origins, (th, tw)), (H, W), patch, mean, std, want_pixels)
+    src = yuv_src(YUV_PLANAR, (y, u, v), subsampling, depth, msb, 0, table, chroma, siting)
+    return _yuv_tiles_launch(src, tabs, origins, (h, w), th, tw, H, W, patch, mean, std, want_pixels, y.device,
+                             "yuv_planar_tiled_patch_planes",
+                             None if transfer == "sdr" else (transfer, depth, matrix, peak_nits))
+
+
+def yuv_semiplanar_tiled_patch_planes(y: torch.Tensor, uv: torch.Tensor, origins, tile_hw: Tuple[int, int],
+                                      out_hw: Tuple[int, int], patch: int, mean: Sequence[float],
+                                      std: Sequence[float], subsampling: str = "420", depth: int = 8,
+                                      msb: bool = False, matrix: str = "bt601", full_range: bool = False,
+                                      want_pixels: bool = False, vu: bool = False, chroma: str = "nearest",
+                                      siting: str = "left", transfer: str = "sdr", peak_nits: float = 1000.0) \
+        -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The same of one semi-planar frame (NV12 / NV21, NV16, NV24, P010 ...: :func:`yuv_semiplanar_patch_planes`'
+    arguments), bit-equal to ``image_patch_planes(tile_crops(yuv_semiplanar_to_rgb(...), origins, tile_hw), ...)``."""
+    y, uv = yuv_semiplanar_planes(y, uv, subsampling, depth)
+    table = yuv_table(matrix, full_range, depth)
+    _chroma_check(chroma, siting)
+    _transfer_check(transfer, peak_nits, depth)
+    _, h, w = y.shape
+    origins, th, tw, H, W, tabs = _yuv_tiles(y, (h, w), origins, tile_hw, out_hw, patch, "yuv_semiplanar_tiled")
+    if tabs is None:
+        rgb = yuv_semiplanar_to_rgb(y, uv, subsampling, depth, msb, matrix, full_range, vu, chroma, siting, transfer,
+                                    peak_nits)
+        return image_patch_planes(tile_crops(rgb, origins, (th, tw)), (H, W), patch, mean, std, want_pixels)
+    pairs = uv.as_strided((1, uv.shape[1], 2 * uv.shape[2]), (uv.stride(0), uv.stride(1), 1))   # a view, never a copy
+    src = yuv_src(YUV_SEMIPLANAR, (y, pairs), subsampling, depth, msb, int(bool(vu)), table, chroma, siting)
+    return _yuv_tiles_launch(src, tabs, origins, (h, w), th, tw, H, W, patch, mean, std, want_pixels, y.device,
+                             "yuv_semiplanar_tiled_patch_planes",
+                             None if transfer == "sdr" else (transfer, depth, matrix, peak_nits))
+
+
+def yuyv_tiled_patch_planes(data: torch.Tensor, width: int, order: str, origins, tile_hw: Tuple[int, int],
+                            out_hw: Tuple[int, int], patch: int, mean: Sequence[float], std: Sequence[float],
+                            matrix: str = "bt601", full_range: bool = False, want_pixels: bool = False,
+                            chroma: str = "nearest", siting: str = "left") \
+        -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The same of one packed 4:2:2 frame (YUY2, UYVY, YVYU: :func:`yuyv_patch_planes`' arguments), bit-equal to
+    ``image_patch_planes(tile_crops(yuyv_to_rgb(data, width, order, ...), origins, tile_hw), ...)``. A tile may start
+    at an odd column, in the middle of a macropixel: the kernel's column groups are the frame's."""
+    yv = yuyv_planes(data, width, order)[0]
+    _chroma_check(chroma, siting)
+    data = data if data.dim() == 3 else data[None]
+    table = yuv_table(matrix, full_range, 8)
+    _, h, w = yv.shape
+    origins, th, tw, H, W, tabs = _yuv_tiles(data, (h, w), origins, tile_hw, out_hw, patch, "yuyv_tiled")
+    if tabs is None:
+        rgb = yuyv_to_rgb(data, width, order, matrix, full_range, chroma, siting)
+        return image_patch_planes(tile_crops(rgb, origins, (th, tw)), (H, W), patch, mean, std, want_pixels)
+    src = yuv_src(YUV_PACKED, (data,), "422", 8, False, tuple(YUYV_ORDERS).index(order), table, chroma, siting)
+    return _yuv_tiles_launch(src, tabs, origins, (h, w), th, tw, H, W, patch, mean, std, want_pixels, data.device,
+                             "yuyv_tiled_patch_planes")
 
 
 # ---- detections ---------------------------------------------------------------------------------
