@@ -112,27 +112,20 @@ def _L() -> ctypes.CDLL:
             L = load(LIB)
             vp, i32, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
             fp = ctypes.POINTER(ctypes.c_float)
-            L.nos_image_patch_planes_u8.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, fp, fp,
-                                                    i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-            i64 = ctypes.c_longlong
-            L.nos_image_patch_planes_nv12.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64,
-                                                      ctypes.POINTER(ctypes.c_int)] + \
-                L.nos_image_patch_planes_u8.argtypes[1:]
+            i64, ip = ctypes.c_longlong, ctypes.POINTER(ctypes.c_int)
+            src, hdr = ctypes.POINTER(NosYuvSrc), ctypes.POINTER(NosYuvHdr)
+            # what every image entry takes behind its source, from the output planes on (:func:`_tail_args`)
+            tail = [vp] * 6 + [i32] * 5 + [fp, fp] + [i32] * 9 + [vp]
+            L.nos_image_patch_planes_u8.argtypes = [vp] + tail
+            L.nos_image_patch_planes_nv12.argtypes = [vp] * 6 + [i64] * 4 + [ip] + tail
             L.nos_image_patch_planes_nv12_order.argtypes = L.nos_image_patch_planes_nv12.argtypes + [i32]
-            L.nos_image_patch_planes_yuv420p.argtypes = [vp] * 9 + [i64] * 6 + [ctypes.POINTER(ctypes.c_int)] + \
-                L.nos_image_patch_planes_u8.argtypes[1:]
-            L.nos_image_patch_planes_packed.argtypes = [vp, vp, vp, i64, i64, ctypes.c_char_p] + \
-                L.nos_image_patch_planes_u8.argtypes[1:]
-            L.nos_image_patch_planes_yuv.argtypes = [ctypes.POINTER(NosYuvSrc)] + \
-                L.nos_image_patch_planes_u8.argtypes[1:]
-            L.nos_image_patch_planes_yuv_hdr.argtypes = [ctypes.POINTER(NosYuvSrc), ctypes.POINTER(NosYuvHdr)] + \
-                L.nos_image_patch_planes_u8.argtypes[1:]
+            L.nos_image_patch_planes_yuv420p.argtypes = [vp] * 9 + [i64] * 6 + [ip] + tail
+            L.nos_image_patch_planes_packed.argtypes = [vp, vp, vp, i64, i64, ctypes.c_char_p] + tail
+            L.nos_image_patch_planes_yuv.argtypes = [src] + tail
+            L.nos_image_patch_planes_yuv_hdr.argtypes = [src, hdr] + tail
             L.nos_detections_f32.argtypes = [vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, vp, vp]
-            L.nos_image_patch_planes_tiles.argtypes = [vp, vp, vp, i64, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int),
-                                                       vp, i32, i32] + L.nos_image_patch_planes_u8.argtypes[1:]
-            L.nos_image_patch_planes_yuv_tiles.argtypes = [ctypes.POINTER(NosYuvSrc), ctypes.POINTER(NosYuvHdr),
-                                                           ctypes.POINTER(ctypes.c_int), vp, i32, i32, i32] + \
-                L.nos_image_patch_planes_u8.argtypes[1:]
+            L.nos_image_patch_planes_tiles.argtypes = [vp, vp, vp, i64, ctypes.c_char_p, ip, vp, i32, i32] + tail
+            L.nos_image_patch_planes_yuv_tiles.argtypes = [src, hdr, ip, vp, i32, i32, i32] + tail
             L.nos_merge_detections_f32.argtypes = [vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, i32, vp, vp, vp, vp,
                                                    vp, vp]
             L.nos_image_last_error.restype = ctypes.c_char_p
@@ -304,6 +297,17 @@ def fusable(hw: Tuple[int, int], out_hw: Tuple[int, int], patch: int) -> bool:
             and hw[0] / out_hw[0] <= MAX_SCALE and hw[1] / out_hw[1] <= MAX_SCALE)
 
 
+def _fused_tables(t: torch.Tensor, hw: Tuple[int, int], out_hw: Tuple[int, int], patch: int, limit: int) \
+        -> Optional[tuple]:
+    """The tap tables (:func:`_device_tables`) when the HIP launch takes this call — ``t`` on the GPU, a resize the
+    kernel can take (:func:`fusable`) and no patch footprint wider than ``limit`` columns, the layout's
+    ``*_MAX_FOOTPRINT`` — else None: the torch composition runs."""
+    if not (_use_hip(t) and fusable(hw, out_hw, patch)):
+        return None
+    tabs = _device_tables(hw[0], hw[1], out_hw[0], out_hw[1], patch, t.device)
+    return None if tabs is None or tabs[5] > limit else tabs
+
+
 def image_patch_planes(img_u8: torch.Tensor, out_hw: Tuple[int, int], patch: int, mean: Sequence[float],
                        std: Sequence[float], want_pixels: bool = False) \
         -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
@@ -317,26 +321,16 @@ def image_patch_planes(img_u8: torch.Tensor, out_hw: Tuple[int, int], patch: int
         raise ValueError("image_patch_planes: a uint8 [B, h, w, 3] image")
     B, h, w, _ = img_u8.shape
     H, W = int(out_hw[0]), int(out_hw[1])
-    tabs = None
-    if _use_hip(img_u8) and fusable((h, w), (H, W), patch):
-        tabs = _device_tables(h, w, H, W, patch, img_u8.device)
+    tabs = _fused_tables(img_u8, (h, w), (H, W), patch, MAX_FOOTPRINT)
     if tabs is None:
         px = pixels_reference(img_u8, (H, W), mean, std)
         return K.split3(im2col(px, patch)), (px if want_pixels else None)
     if not img_u8.is_contiguous() and _packed_strides(img_u8) and tabs[5] <= PACKED_MAX_FOOTPRINT:
         return packed_patch_planes(img_u8, "rgb", (H, W), patch, mean, std, want_pixels)
     img = img_u8.contiguous()
-    gh, gw = H // patch, W // patch
-    planes = torch.empty(3, B * gh * gw, 3 * patch * patch, dtype=torch.bfloat16, device=img.device)
-    pixels = torch.empty(B, 3, H, W, dtype=torch.float32, device=img.device) if want_pixels else None
-    yidx, ywt, xidx, xwt, max_fh, max_fw = tabs
-    a, b = affine(mean, std)
-    F3 = ctypes.c_float * 3
-    rc = _L().nos_image_patch_planes_u8(img.data_ptr(), planes.data_ptr(), pixels.data_ptr() if want_pixels else None,
-                                        yidx.data_ptr(), ywt.data_ptr(), xidx.data_ptr(), xwt.data_ptr(),
-                                        ywt.shape[0], xwt.shape[0], ywt.shape[1], max_fh, max_fw, F3(*a), F3(*b),
-                                        B, h, w, H, W, patch, gh, gw, image_wgs(),
-                                        torch.cuda.current_stream().cuda_stream)
+    planes, pixels, gh, gw = _outputs(B, H, W, patch, want_pixels, img.device)
+    rc = _L().nos_image_patch_planes_u8(img.data_ptr(),
+                                        *_tail_args(tabs, planes, pixels, mean, std, B, h, w, H, W, patch, gh, gw))
     _check(rc, "image_patch_planes")
     return planes, pixels
 
@@ -522,25 +516,14 @@ def nv12_patch_planes(y: torch.Tensor, uv: torch.Tensor, out_hw: Tuple[int, int]
     table = nv12_table(matrix, full_range)
     B, h, w = y.shape
     H, W = int(out_hw[0]), int(out_hw[1])
-    tabs = None
-    if _use_hip(y) and fusable((h, w), (H, W), patch):
-        tabs = _device_tables(h, w, H, W, patch, y.device)
-    if tabs is None or tabs[5] > NV12_MAX_FOOTPRINT:
+    tabs = _fused_tables(y, (h, w), (H, W), patch, NV12_MAX_FOOTPRINT)
+    if tabs is None:
         rgb = nv12_to_rgb(y, uv, matrix, full_range, vu=True) if vu else nv12_to_rgb(y, uv, matrix, full_range)
         return image_patch_planes(rgb, (H, W), patch, mean, std, want_pixels)
-    gh, gw = H // patch, W // patch
-    planes = torch.empty(3, B * gh * gw, 3 * patch * patch, dtype=torch.bfloat16, device=y.device)
-    pixels = torch.empty(B, 3, H, W, dtype=torch.float32, device=y.device) if want_pixels else None
-    yidx, ywt, xidx, xwt, max_fh, max_fw = tabs
-    a, b = affine(mean, std)
-    F3 = ctypes.c_float * 3
-    args = (y.data_ptr(), *_storage_bounds(y), uv.data_ptr(), *_storage_bounds(uv),
-                                          y.stride(1), uv.stride(1), y.stride(0), uv.stride(0),
-                                          (ctypes.c_int * 12)(*table), planes.data_ptr(),
-                                          pixels.data_ptr() if want_pixels else None, yidx.data_ptr(), ywt.data_ptr(),
-                                          xidx.data_ptr(), xwt.data_ptr(), ywt.shape[0], xwt.shape[0], ywt.shape[1],
-                                          max_fh, max_fw, F3(*a), F3(*b), B, h, w, H, W, patch, gh, gw, image_wgs(),
-                                          torch.cuda.current_stream().cuda_stream)
+    planes, pixels, gh, gw = _outputs(B, H, W, patch, want_pixels, y.device)
+    args = (y.data_ptr(), *_storage_bounds(y), uv.data_ptr(), *_storage_bounds(uv), y.stride(1), uv.stride(1),
+            y.stride(0), uv.stride(0), (ctypes.c_int * 12)(*table),
+            *_tail_args(tabs, planes, pixels, mean, std, B, h, w, H, W, patch, gh, gw))
     rc = _L().nos_image_patch_planes_nv12_order(*args, 1) if vu else _L().nos_image_patch_planes_nv12(*args)
     _check(rc, "nv12_patch_planes")
     return planes, pixels
@@ -576,10 +559,8 @@ def yuv420p_patch_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, out_
     table = nv12_table(matrix, full_range)
     B, h, w = y.shape
     H, W = int(out_hw[0]), int(out_hw[1])
-    tabs = None
-    if _use_hip(y) and fusable((h, w), (H, W), patch):
-        tabs = _device_tables(h, w, H, W, patch, y.device)
-    if tabs is None or tabs[5] > YUV420P_MAX_FOOTPRINT:
+    tabs = _fused_tables(y, (h, w), (H, W), patch, YUV420P_MAX_FOOTPRINT)
+    if tabs is None:
         return image_patch_planes(yuv420_to_rgb(y, u, v, matrix, full_range), (H, W), patch, mean, std, want_pixels)
     planes, pixels, gh, gw = _outputs(B, H, W, patch, want_pixels, y.device)
     rc = _L().nos_image_patch_planes_yuv420p(y.data_ptr(), *_storage_bounds(y), u.data_ptr(), *_storage_bounds(u),
@@ -629,10 +610,8 @@ def packed_patch_planes(img: torch.Tensor, order: str, out_hw: Tuple[int, int], 
                          f"(stride(3) == 1, stride(2) == {C}, stride(1) >= {C} * w)")
     B, h, w, _ = img.shape
     H, W = int(out_hw[0]), int(out_hw[1])
-    tabs = None
-    if _use_hip(img) and fusable((h, w), (H, W), patch):
-        tabs = _device_tables(h, w, H, W, patch, img.device)
-    if tabs is None or tabs[5] > PACKED_MAX_FOOTPRINT:
+    tabs = _fused_tables(img, (h, w), (H, W), patch, PACKED_MAX_FOOTPRINT)
+    if tabs is None:
         return image_patch_planes(packed_to_rgb(img, order), (H, W), patch, mean, std, want_pixels)
     planes, pixels, gh, gw = _outputs(B, H, W, patch, want_pixels, img.device)
     rc = _L().nos_image_patch_planes_packed(img.data_ptr(), *_storage_bounds(img), img.stride(1), img.stride(0),
@@ -724,10 +703,8 @@ def tiled_patch_planes(img: torch.Tensor, order: str, origins, tile_hw: Tuple[in
     origins = _tile_origins(origins, th, tw, h, w, "tiled")
     B = len(origins)
     H, W = int(out_hw[0]), int(out_hw[1])
-    tabs = None
-    if _use_hip(img) and fusable((th, tw), (H, W), patch):
-        tabs = _device_tables(th, tw, H, W, patch, img.device)
-    if tabs is None or tabs[5] > PACKED_MAX_FOOTPRINT:
+    tabs = _fused_tables(img, (th, tw), (H, W), patch, PACKED_MAX_FOOTPRINT)
+    if tabs is None:
         return packed_patch_planes(tile_crops(img, origins, (th, tw)), order, (H, W), patch, mean, std, want_pixels)
     pitch = img.stride(1) if h > 1 else w * C
     table = _tables.get(("tiles", origins, pitch, C, str(img.device)),
@@ -1119,14 +1096,6 @@ def yuv_src(layout: int, planes: Sequence[torch.Tensor], subsampling: str, depth
     return src
 
 
-def _yuv_fused(first: torch.Tensor, hw: Tuple[int, int], out_hw: Tuple[int, int], patch: int) -> Optional[tuple]:
-    """The tap tables when the general YUV launch takes this call, else None (the composition runs)."""
-    if not (_use_hip(first) and fusable(hw, out_hw, patch)):
-        return None
-    tabs = _device_tables(hw[0], hw[1], out_hw[0], out_hw[1], patch, first.device)
-    return None if tabs is None or tabs[5] > YUV_MAX_FOOTPRINT else tabs
-
-
 def yuv_hdr(lut1: torch.Tensor, gamut: Sequence[int], lut2: torch.Tensor) -> NosYuvHdr:
     """The descriptor of HDR tables on the device (:func:`_hdr_device_tables`' three)."""
     return NosYuvHdr(size=ctypes.sizeof(NosYuvHdr), entries=lut1.numel(), lut1=lut1.data_ptr(), lut2=lut2.data_ptr(),
@@ -1134,18 +1103,90 @@ def yuv_hdr(lut1: torch.Tensor, gamut: Sequence[int], lut2: torch.Tensor) -> Nos
 
 
 def _yuv_launch(src: NosYuvSrc, tabs: tuple, B: int, h: int, w: int, H: int, W: int, patch: int, mean, std,
-                want_pixels: bool, device: torch.device, what: str, hdr: Optional[tuple] = None):
-    """``hdr``: ``(transfer, depth, matrix, peak_nits)`` of a frame that is not ``sdr``; its launch reads the cached
-    device tables."""
+                want_pixels: bool, device: torch.device, what: str, hdr: Optional[tuple] = None,
+                origins: Optional[tuple] = None, frame_hw: Optional[Tuple[int, int]] = None):
+    """One launch of the general YUV front end: on the ``B`` images of ``h x w`` that ``src`` describes or, with
+    ``origins``, on the ``B = len(origins)`` tiles of ``h x w`` of the one ``frame_hw`` frame it describes (the device
+    table is :func:`origin_tensor`'s, the one :func:`merge_detections` reads). ``hdr``: ``(transfer, depth, matrix,
+    peak_nits)`` of a frame that is not ``sdr``; its launch reads the cached device tables."""
     planes, pixels, gh, gw = _outputs(B, H, W, patch, want_pixels, device)
     tail = _tail_args(tabs, planes, pixels, mean, std, B, h, w, H, W, patch, gh, gw)
-    if hdr is None:
+    tables = None if hdr is None else ctypes.byref(yuv_hdr(*_hdr_device_tables(*hdr, device)))
+    if origins is not None:
+        flat = (ctypes.c_int * (2 * B))(*[v for o in origins for v in o])
+        rc = _L().nos_image_patch_planes_yuv_tiles(ctypes.byref(src), tables, flat,
+                                                   origin_tensor(origins, device).data_ptr(), frame_hw[0], frame_hw[1],
+                                                   1, *tail)
+    elif hdr is None:
         rc = _L().nos_image_patch_planes_yuv(ctypes.byref(src), *tail)
     else:
-        rc = _L().nos_image_patch_planes_yuv_hdr(ctypes.byref(src),
-                                                 ctypes.byref(yuv_hdr(*_hdr_device_tables(*hdr, device))), *tail)
+        rc = _L().nos_image_patch_planes_yuv_hdr(ctypes.byref(src), tables, *tail)
     _check(rc, what)
     return planes, pixels
+
+
+def _yuv_patch_planes(source: tuple, name: str, out_hw: Tuple[int, int], patch: int, mean, std, want_pixels: bool,
+                      tiles: Optional[tuple] = None):
+    """What the six YUV functions do behind their layout's checks. ``source``: what the layout's ``_*_source`` gives —
+    ``(first, (h, w), src, rgb, hdr)``, the tensor that says batch and device, the frame's size, the launch
+    descriptor, a callable that gives the converted RGB frame, and :func:`_yuv_launch`'s ``hdr``. The plan, then one
+    launch — or, on a CPU tensor, with the ``torch`` backend and past the kernel's limits, :func:`image_patch_planes`
+    of the converted frame. With ``tiles = (origins, tile_hw)`` the images are those tiles of the one frame
+    (:func:`tile_crops` of the converted frame in the composition)."""
+    first, (h, w), src, rgb, hdr = source
+    B, th, tw, origins = first.shape[0], h, w, None
+    if tiles is not None:
+        if B != 1:
+            raise ValueError(f"{name}: tiles are cut from one frame, not from a batch of {B}")
+        th, tw = int(tiles[1][0]), int(tiles[1][1])
+        origins = _tile_origins(tiles[0], th, tw, h, w, name)
+        B = len(origins)
+    H, W = int(out_hw[0]), int(out_hw[1])
+    tabs = _fused_tables(first, (th, tw), (H, W), patch, YUV_MAX_FOOTPRINT)
+    if tabs is None:
+        frame = rgb() if origins is None else tile_crops(rgb(), origins, (th, tw))
+        return image_patch_planes(frame, (H, W), patch, mean, std, want_pixels)
+    return _yuv_launch(src, tabs, B, th, tw, H, W, patch, mean, std, want_pixels, first.device, name + "_patch_planes",
+                       hdr, origins, (h, w))
+
+
+def _planar_source(y, u, v, subsampling, depth, msb, matrix, full_range, chroma, siting, transfer, peak_nits) -> tuple:
+    """A planar frame, checked, as :func:`_yuv_patch_planes`' ``source``."""
+    y, u, v = yuv_planes(y, u, v, subsampling, depth)
+    table = yuv_table(matrix, full_range, depth)
+    _chroma_check(chroma, siting)
+    _transfer_check(transfer, peak_nits, depth)
+    return (y, tuple(y.shape[1:]), yuv_src(YUV_PLANAR, (y, u, v), subsampling, depth, msb, 0, table, chroma, siting),
+            lambda: yuv_to_rgb(y, u, v, subsampling, depth, msb, matrix, full_range, chroma, siting, transfer,
+                               peak_nits),
+            None if transfer == "sdr" else (transfer, depth, matrix, peak_nits))
+
+
+def _semiplanar_source(y, uv, subsampling, depth, msb, matrix, full_range, vu, chroma, siting, transfer,
+                       peak_nits) -> tuple:
+    """A semi-planar frame, checked, as :func:`_yuv_patch_planes`' ``source``."""
+    y, uv = yuv_semiplanar_planes(y, uv, subsampling, depth)
+    table = yuv_table(matrix, full_range, depth)
+    _chroma_check(chroma, siting)
+    _transfer_check(transfer, peak_nits, depth)
+    B, ch, cw = uv.shape[:3]
+    pairs = uv.as_strided((B, ch, 2 * cw), (uv.stride(0), uv.stride(1), 1))   # a view, never a copy
+    return (y, tuple(y.shape[1:]),
+            yuv_src(YUV_SEMIPLANAR, (y, pairs), subsampling, depth, msb, int(bool(vu)), table, chroma, siting),
+            lambda: yuv_semiplanar_to_rgb(y, uv, subsampling, depth, msb, matrix, full_range, vu, chroma, siting,
+                                          transfer, peak_nits),
+            None if transfer == "sdr" else (transfer, depth, matrix, peak_nits))
+
+
+def _yuyv_source(data, width, order, matrix, full_range, chroma, siting) -> tuple:
+    """A packed 4:2:2 frame, checked, as :func:`_yuv_patch_planes`' ``source``."""
+    yv = yuyv_planes(data, width, order)[0]
+    _chroma_check(chroma, siting)
+    data = data if data.dim() == 3 else data[None]
+    table = yuv_table(matrix, full_range, 8)
+    return (data, tuple(yv.shape[1:]),
+            yuv_src(YUV_PACKED, (data,), "422", 8, False, tuple(YUYV_ORDERS).index(order), table, chroma, siting),
+            lambda: yuyv_to_rgb(data, width, order, matrix, full_range, chroma, siting), None)
 
 
 def yuv_planar_patch_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, out_hw: Tuple[int, int], patch: int,
@@ -1160,19 +1201,8 @@ def yuv_planar_patch_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, o
     On the GPU one HIP launch reads the three planes in place, each by its own strides; with ``chroma="bilinear"``
     it interpolates the chroma at ``siting`` (:func:`chroma_upsample`) while it stages them, and with ``transfer``
     ``"pq"`` or ``"hlg"`` it takes the codes through the HDR tables (:func:`hdr_to_sdr`) there as well."""
-    y, u, v = yuv_planes(y, u, v, subsampling, depth)
-    table = yuv_table(matrix, full_range, depth)
-    _chroma_check(chroma, siting)
-    _transfer_check(transfer, peak_nits, depth)
-    B, h, w = y.shape
-    H, W = int(out_hw[0]), int(out_hw[1])
-    tabs = _yuv_fused(y, (h, w), (H, W), patch)
-    if tabs is None:
-        return image_patch_planes(yuv_to_rgb(y, u, v, subsampling, depth, msb, matrix, full_range, chroma, siting,
-                                             transfer, peak_nits), (H, W), patch, mean, std, want_pixels)
-    src = yuv_src(YUV_PLANAR, (y, u, v), subsampling, depth, msb, 0, table, chroma, siting)
-    return _yuv_launch(src, tabs, B, h, w, H, W, patch, mean, std, want_pixels, y.device, "yuv_planar_patch_planes",
-                       None if transfer == "sdr" else (transfer, depth, matrix, peak_nits))
+    source = _planar_source(y, u, v, subsampling, depth, msb, matrix, full_range, chroma, siting, transfer, peak_nits)
+    return _yuv_patch_planes(source, "yuv_planar", out_hw, patch, mean, std, want_pixels)
 
 
 def yuv_semiplanar_patch_planes(y: torch.Tensor, uv: torch.Tensor, out_hw: Tuple[int, int], patch: int,
@@ -1184,21 +1214,9 @@ def yuv_semiplanar_patch_planes(y: torch.Tensor, uv: torch.Tensor, out_hw: Tuple
     """The same of a semi-planar frame (:func:`yuv_semiplanar_planes`' layout: NV12 / NV21, NV16 / NV61, NV24 / NV42,
     P010, P012, P210, P410), bit-equal to ``image_patch_planes(yuv_semiplanar_to_rgb(...), ...)``. ``vu``: the pairs
     are (V, U)."""
-    y, uv = yuv_semiplanar_planes(y, uv, subsampling, depth)
-    table = yuv_table(matrix, full_range, depth)
-    _chroma_check(chroma, siting)
-    _transfer_check(transfer, peak_nits, depth)
-    B, h, w = y.shape
-    H, W = int(out_hw[0]), int(out_hw[1])
-    tabs = _yuv_fused(y, (h, w), (H, W), patch)
-    if tabs is None:
-        rgb = yuv_semiplanar_to_rgb(y, uv, subsampling, depth, msb, matrix, full_range, vu, chroma, siting, transfer,
-                                    peak_nits)
-        return image_patch_planes(rgb, (H, W), patch, mean, std, want_pixels)
-    pairs = uv.as_strided((B, uv.shape[1], 2 * uv.shape[2]), (uv.stride(0), uv.stride(1), 1))   # a view, never a copy
-    src = yuv_src(YUV_SEMIPLANAR, (y, pairs), subsampling, depth, msb, int(bool(vu)), table, chroma, siting)
-    return _yuv_launch(src, tabs, B, h, w, H, W, patch, mean, std, want_pixels, y.device,
-                       "yuv_semiplanar_patch_planes", None if transfer == "sdr" else (transfer, depth, matrix, peak_nits))
+    source = _semiplanar_source(y, uv, subsampling, depth, msb, matrix, full_range, vu, chroma, siting, transfer,
+                                peak_nits)
+    return _yuv_patch_planes(source, "yuv_semiplanar", out_hw, patch, mean, std, want_pixels)
 
 
 def yuyv_patch_planes(data: torch.Tensor, width: int, order: str, out_hw: Tuple[int, int], patch: int,
@@ -1209,50 +1227,11 @@ def yuyv_patch_planes(data: torch.Tensor, width: int, order: str, out_hw: Tuple[
     ``image_patch_planes(yuyv_to_rgb(data, width, order, matrix, full_range, chroma, siting), ...)``. On the GPU one
     HIP launch reads a group's two macropixels in one read (with bilinear chroma the one before and the one after as
     well), the rows wherever their pitch puts them."""
-    yv = yuyv_planes(data, width, order)[0]
-    _chroma_check(chroma, siting)
-    data = data if data.dim() == 3 else data[None]
-    table = yuv_table(matrix, full_range, 8)
-    B, h, w = yv.shape
-    H, W = int(out_hw[0]), int(out_hw[1])
-    tabs = _yuv_fused(data, (h, w), (H, W), patch)
-    if tabs is None:
-        return image_patch_planes(yuyv_to_rgb(data, width, order, matrix, full_range, chroma, siting), (H, W), patch,
-                                  mean, std, want_pixels)
-    src = yuv_src(YUV_PACKED, (data,), "422", 8, False, tuple(YUYV_ORDERS).index(order), table, chroma, siting)
-    return _yuv_launch(src, tabs, B, h, w, H, W, patch, mean, std, want_pixels, data.device, "yuyv_patch_planes")
+    source = _yuyv_source(data, width, order, matrix, full_range, chroma, siting)
+    return _yuv_patch_planes(source, "yuyv", out_hw, patch, mean, std, want_pixels)
 
 
 # ---- tiles of one YUV frame -----------------------------------------------------------------------
-def _yuv_tiles(first: torch.Tensor, hw: Tuple[int, int], origins, tile_hw: Tuple[int, int], out_hw: Tuple[int, int],
-               patch: int, who: str) -> Tuple[tuple, int, int, int, int, Optional[tuple]]:
-    """What the three tiled YUV functions check and plan: ``(origins, th, tw, H, W, tabs)``; ``tabs`` are the tile's
-    tap tables when the launch takes this call, else None (the composition runs)."""
-    if first.shape[0] != 1:
-        raise ValueError(f"{who}: tiles are cut from one frame, not from a batch of {first.shape[0]}")
-    th, tw = int(tile_hw[0]), int(tile_hw[1])
-    origins = _tile_origins(origins, th, tw, hw[0], hw[1], who)
-    H, W = int(out_hw[0]), int(out_hw[1])
-    return origins, th, tw, H, W, _yuv_fused(first, (th, tw), (H, W), patch)
-
-
-def _yuv_tiles_launch(src: NosYuvSrc, tabs: tuple, origins: tuple, hw: Tuple[int, int], th: int, tw: int, H: int,
-                      W: int, patch: int, mean, std, want_pixels: bool, device: torch.device, what: str,
-                      hdr: Optional[tuple] = None):
-    """:func:`_yuv_launch` of the ``len(origins)`` tiles of the one ``hw`` frame ``src`` describes; the device table
-    is :func:`origin_tensor`'s, the one :func:`merge_detections` reads."""
-    B = len(origins)
-    table = origin_tensor(origins, device)
-    planes, pixels, gh, gw = _outputs(B, H, W, patch, want_pixels, device)
-    flat = (ctypes.c_int * (2 * B))(*[v for o in origins for v in o])
-    tables = None if hdr is None else ctypes.byref(yuv_hdr(*_hdr_device_tables(*hdr, device)))
-    rc = _L().nos_image_patch_planes_yuv_tiles(ctypes.byref(src), tables, flat, table.data_ptr(), hw[0], hw[1], 1,
-                                               *_tail_args(tabs, planes, pixels, mean, std, B, th, tw, H, W, patch,
-                                                           gh, gw))
-    _check(rc, what)
-    return planes, pixels
-
-
 def yuv_planar_tiled_patch_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, origins,
                                   tile_hw: Tuple[int, int], out_hw: Tuple[int, int], patch: int,
                                   mean: Sequence[float], std: Sequence[float], subsampling: str = "420",
@@ -1269,19 +1248,8 @@ def yuv_planar_tiled_patch_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Ten
     :func:`origin_tensor`'s device table (cached, dropped by :func:`invalidate_cache`) and moves the patch's
     footprint into the frame, so a chroma sample lies under its luma whatever the origin's parity, and bilinear
     chroma clamps at the frame's edge, not at the tile's."""
-    y, u, v = yuv_planes(y, u, v, subsampling, depth)
-    table = yuv_table(matrix, full_range, depth)
-    _chroma_check(chroma, siting)
-    _transfer_check(transfer, peak_nits, depth)
-    _, h, w = y.shape
-    origins, th, tw, H, W, tabs = _yuv_tiles(y, (h, w), origins, tile_hw, out_hw, patch, "yuv_planar_tiled")
-    if tabs is None:
-        rgb = yuv_to_rgb(y, u, v, subsampling, depth, msb, matrix, full_range, chroma, siting, transfer, peak_nits)
-        return image_patch_planes(tile_crops(rgb, origins, (th, tw)), (H, W), patch, mean, std, want_pixels)
-    src = yuv_src(YUV_PLANAR, (y, u, v), subsampling, depth, msb, 0, table, chroma, siting)
-    return _yuv_tiles_launch(src, tabs, origins, (h, w), th, tw, H, W, patch, mean, std, want_pixels, y.device,
-                             "yuv_planar_tiled_patch_planes",
-                             None if transfer == "sdr" else (transfer, depth, matrix, peak_nits))
+    source = _planar_source(y, u, v, subsampling, depth, msb, matrix, full_range, chroma, siting, transfer, peak_nits)
+    return _yuv_patch_planes(source, "yuv_planar_tiled", out_hw, patch, mean, std, want_pixels, (origins, tile_hw))
 
 
 def yuv_semiplanar_tiled_patch_planes(y: torch.Tensor, uv: torch.Tensor, origins, tile_hw: Tuple[int, int],
@@ -1293,21 +1261,9 @@ def yuv_semiplanar_tiled_patch_planes(y: torch.Tensor, uv: torch.Tensor, origins
         -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """The same of one semi-planar frame (NV12 / NV21, NV16, NV24, P010 ...: :func:`yuv_semiplanar_patch_planes`'
     arguments), bit-equal to ``image_patch_planes(tile_crops(yuv_semiplanar_to_rgb(...), origins, tile_hw), ...)``."""
-    y, uv = yuv_semiplanar_planes(y, uv, subsampling, depth)
-    table = yuv_table(matrix, full_range, depth)
-    _chroma_check(chroma, siting)
-    _transfer_check(transfer, peak_nits, depth)
-    _, h, w = y.shape
-    origins, th, tw, H, W, tabs = _yuv_tiles(y, (h, w), origins, tile_hw, out_hw, patch, "yuv_semiplanar_tiled")
-    if tabs is None:
-        rgb = yuv_semiplanar_to_rgb(y, uv, subsampling, depth, msb, matrix, full_range, vu, chroma, siting, transfer,
-                                    peak_nits)
-        return image_patch_planes(tile_crops(rgb, origins, (th, tw)), (H, W), patch, mean, std, want_pixels)
-    pairs = uv.as_strided((1, uv.shape[1], 2 * uv.shape[2]), (uv.stride(0), uv.stride(1), 1))   # a view, never a copy
-    src = yuv_src(YUV_SEMIPLANAR, (y, pairs), subsampling, depth, msb, int(bool(vu)), table, chroma, siting)
-    return _yuv_tiles_launch(src, tabs, origins, (h, w), th, tw, H, W, patch, mean, std, want_pixels, y.device,
-                             "yuv_semiplanar_tiled_patch_planes",
-                             None if transfer == "sdr" else (transfer, depth, matrix, peak_nits))
+    source = _semiplanar_source(y, uv, subsampling, depth, msb, matrix, full_range, vu, chroma, siting, transfer,
+                                peak_nits)
+    return _yuv_patch_planes(source, "yuv_semiplanar_tiled", out_hw, patch, mean, std, want_pixels, (origins, tile_hw))
 
 
 def yuyv_tiled_patch_planes(data: torch.Tensor, width: int, order: str, origins, tile_hw: Tuple[int, int],
@@ -1318,18 +1274,8 @@ def yuyv_tiled_patch_planes(data: torch.Tensor, width: int, order: str, origins,
     """The same of one packed 4:2:2 frame (YUY2, UYVY, YVYU: :func:`yuyv_patch_planes`' arguments), bit-equal to
     ``image_patch_planes(tile_crops(yuyv_to_rgb(data, width, order, ...), origins, tile_hw), ...)``. A tile may start
     at an odd column, in the middle of a macropixel: the kernel's column groups are the frame's."""
-    yv = yuyv_planes(data, width, order)[0]
-    _chroma_check(chroma, siting)
-    data = data if data.dim() == 3 else data[None]
-    table = yuv_table(matrix, full_range, 8)
-    _, h, w = yv.shape
-    origins, th, tw, H, W, tabs = _yuv_tiles(data, (h, w), origins, tile_hw, out_hw, patch, "yuyv_tiled")
-    if tabs is None:
-        rgb = yuyv_to_rgb(data, width, order, matrix, full_range, chroma, siting)
-        return image_patch_planes(tile_crops(rgb, origins, (th, tw)), (H, W), patch, mean, std, want_pixels)
-    src = yuv_src(YUV_PACKED, (data,), "422", 8, False, tuple(YUYV_ORDERS).index(order), table, chroma, siting)
-    return _yuv_tiles_launch(src, tabs, origins, (h, w), th, tw, H, W, patch, mean, std, want_pixels, data.device,
-                             "yuyv_tiled_patch_planes")
+    source = _yuyv_source(data, width, order, matrix, full_range, chroma, siting)
+    return _yuv_patch_planes(source, "yuyv_tiled", out_hw, patch, mean, std, want_pixels, (origins, tile_hw))
 
 
 # ---- detections ---------------------------------------------------------------------------------
