@@ -115,7 +115,8 @@ def merge_loop(logits, boxes, origins, tile_hw, threshold, match, match_threshol
             m_thr = min(m_thr, abs(score - threshold))
             if score > threshold:
                 # (the label of a row below the threshold is never written: its near-ties decide nothing)
-                m_label = min(m_label, score - max(v for i, v in enumerate(p) if i != label))
+                # (one class beside "no object": no second, and nothing to decide)
+                m_label = min(m_label, score - max((v for i, v in enumerate(p) if i != label), default=-math.inf))
                 cx, cy, w, h = bx[b][m]
                 oy, ox = origins[b]
                 cands.append((score, label, ((cx - 0.5 * w) * tw + ox, (cy - 0.5 * h) * th + oy,

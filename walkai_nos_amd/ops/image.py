@@ -1304,9 +1304,12 @@ def detections_reference(logits: torch.Tensor, boxes: torch.Tensor, target: torc
     count = keep.sum(-1).to(torch.int32)
     order = torch.sort((~keep).to(torch.int8), dim=-1, stable=True).indices     # kept rows first, in order
     live = torch.arange(keep.shape[1], device=keep.device)[None, :] < count[:, None]
-    scores = torch.gather(scores, 1, order) * live
+    # (selected, not multiplied: a NaN score behind the kept rows is a zero there, as the kernel's)
+    scores = torch.gather(scores, 1, order)
+    scores = torch.where(live, scores, torch.zeros_like(scores))
     labels = (torch.gather(labels, 1, order) * live).to(torch.int32)
-    xyxy = torch.gather(xyxy, 1, order[..., None].expand(-1, -1, 4)) * live[..., None]
+    xyxy = torch.gather(xyxy, 1, order[..., None].expand(-1, -1, 4))
+    xyxy = torch.where(live[..., None], xyxy, torch.zeros_like(xyxy))
     return count, scores, labels, xyxy
 
 
@@ -1396,8 +1399,10 @@ def merge_detections_reference(logits: torch.Tensor, boxes: torch.Tensor, origin
     count = keep.sum().to(torch.int32).reshape(1)
     front = torch.sort((~keep).to(torch.int8), stable=True).indices     # kept rows first, in order
     live = idx < count
-    return (count, scores[front] * live, (labels[front] * live).to(torch.int32), xyxy[front] * live[:, None],
-            (tile[front] * live).to(torch.int32))
+    # (selected, not multiplied: a NaN score or an infinite box behind the kept rows is a zero there, as the kernel's)
+    scores, xyxy = scores[front], xyxy[front]
+    return (count, torch.where(live, scores, torch.zeros_like(scores)), (labels[front] * live).to(torch.int32),
+            torch.where(live[:, None], xyxy, torch.zeros_like(xyxy)), (tile[front] * live).to(torch.int32))
 
 
 def merge_detections(logits: torch.Tensor, boxes: torch.Tensor, origins, tile_hw: Tuple[int, int], threshold: float,
@@ -1414,7 +1419,9 @@ def merge_detections(logits: torch.Tensor, boxes: torch.Tensor, origins, tile_hw
     *kept* one has the same label, comes from a *different* tile and overlaps it by more than ``match_threshold``
     (:func:`pair_overlap`, ``match`` of :data:`MATCHES`). Boxes of one tile never suppress each other, so one tile
     yields :func:`detections`' survivors stably sorted by score. The kept rows stand first in that order, zeros behind
-    them. One HIP launch (one workgroup) up to ``B * M`` = 1024 rows and 128 classes; past that, on the CPU and with
+    them. A row whose logits hold a NaN (or are all ``-inf``) has a NaN score, which exceeds no threshold: it is never
+    a candidate, changes nothing about the other rows, and nothing that is not finite is written for it. A box whose
+    width or height is not positive overlaps nothing. One HIP launch (one workgroup) up to ``B * M`` = 1024 rows and 128 classes; past that, on the CPU and with
     the ``torch`` backend :func:`merge_detections_reference`."""
     _merge_check(match, match_threshold)
     B, M, C = logits.shape
