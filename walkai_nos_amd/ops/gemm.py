@@ -47,6 +47,16 @@ def _lib() -> ctypes.CDLL:
     return L
 
 
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return t.data_ptr() if t is not None else None
+
+
+def _epi(bias, gelu, residual, residual2) -> int:
+    """The fused-epilogue flags of both GEMMs."""
+    return (EPI_BIAS if bias is not None else 0) | (EPI_GELU if gelu else 0) | (EPI_RES if residual is not None else 0) \
+        | (EPI_RES2 if residual2 is not None else 0)
+
+
 def eligible(M: int, N: int, Kd: int) -> list:
     if Kd % 32 or M < 1:
         return []
@@ -73,9 +83,8 @@ def _launch(cfg: int, x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Te
             out: torch.Tensor, epi: int, r2: Optional[torch.Tensor] = None) -> None:
     M, Kd = x2.shape
     N = w.shape[0]
-    rc = _lib().nos_gemm_f32(x2.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None,
-                             res2.data_ptr() if res2 is not None else None,
-                             r2.data_ptr() if r2 is not None else None, r2.shape[0] if r2 is not None else 0,
+    rc = _lib().nos_gemm_f32(x2.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(res2), _ptr(r2),
+                             r2.shape[0] if r2 is not None else 0,
                              out.data_ptr(), M, N, Kd, epi, cfg, torch.cuda.current_stream().cuda_stream)
     if rc != 0:
         raise RuntimeError(f"nos gemm failed: {_lib().nos_gemm_last_error().decode()} (rc={rc})")
@@ -168,8 +177,7 @@ def gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
         out2 = out.view(M, N)
     res2 = residual.reshape(M, N).contiguous() if residual is not None else None
     r2 = residual2.reshape(-1, N).contiguous() if residual2 is not None else None
-    epi = (EPI_BIAS if bias is not None else 0) | (EPI_GELU if gelu else 0) | (EPI_RES if residual is not None else 0) \
-        | (EPI_RES2 if residual2 is not None else 0)
+    epi = _epi(bias, gelu, residual, residual2)
     cands = eligible(M, N, Kd)
     result = out2.view(*shp[:-1], N) if out is None else out
     if tile is not None:
@@ -392,24 +400,66 @@ def x3_heuristic(M: int, N: int, cus: int, cands: list) -> int:
     return best
 
 
-def _launch_x3(cfg, a3, w3, bias, res, r2, out, out3, epi) -> None:
-    _, M, Kd = a3.shape
+def _x3_weight(w: torch.Tensor) -> torch.Tensor:
+    """The planes ``[3, N, K]`` of a weight given as planes or as fp32 ``[N, K]`` (split once, cached)."""
+    return w if w.dim() == 3 else weight_planes(w)
+
+
+def _x3_planes(a3: torch.Tensor, w: torch.Tensor):
+    """``(a3 as contiguous [3, M, K], weight planes [3, N, K], M, N, K)`` of an x3 GEMM's operands."""
+    Kd = a3.shape[-1]
+    a3 = a3.reshape(3, -1, Kd)
+    if not a3.is_contiguous():
+        a3 = a3.contiguous()
+    w3 = _x3_weight(w)
+    return a3, w3, a3.shape[1], w3.shape[1], Kd
+
+
+def _x3_check(rc: int, what: str) -> None:
+    if rc != 0:
+        raise RuntimeError(f"nos {what} failed: {_lib_x3().nos_gemm_x3_last_error().decode()} (rc={rc})")
+
+
+def _x3_operands(w3, M, Kd, dev, bias, gelu, residual, residual2, out_f32, out_x3, out=None):
+    """What :func:`gemm_x3` and :func:`gemm_x3_f32a` share behind their A operand: the outputs
+    ``(o, o3)`` (fp32 ``[M, N]``, planes ``[3, M, N]``; None where not asked for), the epilogue
+    flags, the library's arguments from the weight planes to those flags, and the residuals as passed
+    (contiguous copies, possibly), which the caller holds until its launches are enqueued."""
     N = w3.shape[1]
-    args = (a3.data_ptr(), a3[0].numel(), w3.data_ptr(), w3[0].numel(),
-            bias.data_ptr() if bias is not None else None,
-            res.data_ptr() if res is not None else None,
-            r2.data_ptr() if r2 is not None else None, r2.shape[0] if r2 is not None else 0,
-            out.data_ptr() if out is not None else None,
-            out3.data_ptr() if out3 is not None else None, out3[0].numel() if out3 is not None else 0,
-            M, N, Kd, epi)
+    o = None
+    if out_f32:
+        if out is not None:
+            if not out.is_contiguous() or out.numel() != M * N:
+                raise ValueError("gemm_x3: out must be contiguous with M x N elements")
+            o = out.view(M, N)
+        else:
+            o = torch.empty(M, N, dtype=torch.float32, device=dev)
+    o3 = torch.empty(3, M, N, dtype=torch.bfloat16, device=dev) if out_x3 else None
+    res = residual.reshape(M, N).contiguous() if residual is not None else None
+    r2 = residual2.reshape(-1, N).contiguous() if residual2 is not None else None
+    epi = _epi(bias, gelu, residual, residual2)
+    args = (w3.data_ptr(), w3[0].numel(), _ptr(bias), _ptr(res), _ptr(r2), r2.shape[0] if r2 is not None else 0,
+            _ptr(o), _ptr(o3), o3[0].numel() if o3 is not None else 0, M, N, Kd, epi)
+    return o, o3, epi, args, (res, r2)
+
+
+def _x3_result(o, o3, lead, N, out_f32, out_x3, out=None):
+    rf = None if o is None else (o.view(*lead, N) if out is None else out)
+    r3 = None if o3 is None else o3.view(3, *lead, N)
+    if out_f32 and out_x3:
+        return rf, r3
+    return rf if out_f32 else r3
+
+
+def _launch_x3(cfg, a3, args) -> None:
+    args = (a3.data_ptr(), a3[0].numel()) + args
     stream = torch.cuda.current_stream().cuda_stream
     if cfg >= 100:
         grid = max(1, X3_SLOTS_PER_CU[cfg] * K.slice_cus() - int(os.environ.get("NOS_X3_PGRID_SLACK", "0")))
         rc = _lib_x3().nos_gemm_x3_persistent(*args, cfg - 100, grid, stream)
     else:
         rc = _lib_x3().nos_gemm_x3(*args, cfg, stream)
-    if rc != 0:
-        raise RuntimeError(f"nos gemm_x3 failed: {_lib_x3().nos_gemm_x3_last_error().decode()} (rc={rc})")
+    _x3_check(rc, "gemm_x3")
 
 
 def gemm_x3(a3: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, gelu: bool = False,
@@ -422,27 +472,9 @@ def gemm_x3(a3: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = No
     (split once, cached) or its planes ``[3, N, K]``. Returns the fp32 result ``[..., N]`` and/or its
     x3 planes ``[3, ..., N]`` (a tuple when both are requested)."""
     lead = a3.shape[1:-1]
-    Kd = a3.shape[-1]
-    a3 = a3.reshape(3, -1, Kd)
-    if not a3.is_contiguous():
-        a3 = a3.contiguous()
-    M = a3.shape[1]
-    w3 = w if w.dim() == 3 else weight_planes(w)
-    N = w3.shape[1]
-    dev = a3.device
-    o = None
-    if out_f32:
-        if out is not None:
-            if not out.is_contiguous() or out.numel() != M * N:
-                raise ValueError("gemm_x3: out must be contiguous with M x N elements")
-            o = out.view(M, N)
-        else:
-            o = torch.empty(M, N, dtype=torch.float32, device=dev)
-    o3 = torch.empty(3, M, N, dtype=torch.bfloat16, device=dev) if out_x3 else None
-    res = residual.reshape(M, N).contiguous() if residual is not None else None
-    r2 = residual2.reshape(-1, N).contiguous() if residual2 is not None else None
-    epi = (EPI_BIAS if bias is not None else 0) | (EPI_GELU if gelu else 0) | (EPI_RES if residual is not None else 0) \
-        | (EPI_RES2 if residual2 is not None else 0)
+    a3, w3, M, N, Kd = _x3_planes(a3, w)
+    o, o3, epi, args, _held = _x3_operands(w3, M, Kd, a3.device, bias, gelu, residual, residual2, out_f32, out_x3,
+                                           out)
     if tile is None:
         cus, pin = K.slice_cus(), K.slice_pin()
         key = (M, N, Kd, epi, int(out_f32) | 2 * int(out_x3), cus, pin)
@@ -469,18 +501,13 @@ def gemm_x3(a3: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = No
                 tile = x3_heuristic(M, N, cus, cands)
             else:
                 stream = torch.cuda.current_stream()
-                times = {c: _gpu_time(lambda c=c: _launch_x3(c, a3, w3, bias, res, r2, o, o3, epi), stream)
-                         for c in cands}
+                times = {c: _gpu_time(lambda c=c: _launch_x3(c, a3, args), stream) for c in cands}
                 tile = min(times, key=times.get)
                 with _lock:
                     _x3_cache[key] = tile
                     _x3_times[key] = times
-    _launch_x3(tile, a3, w3, bias, res, r2, o, o3, epi)
-    rf = None if o is None else (o.view(*lead, N) if out is None else out)
-    r3 = None if o3 is None else o3.view(3, *lead, N)
-    if out_f32 and out_x3:
-        return rf, r3
-    return rf if out_f32 else r3
+    _launch_x3(tile, a3, args)
+    return _x3_result(o, o3, lead, N, out_f32, out_x3, out)
 
 
 # ---- fp32 activation operand (csrc/gemm_x3.hip gemm_x3a) ---------------------------------------
@@ -500,28 +527,12 @@ def gemm_x3_f32a(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] 
     if not x2.is_contiguous():
         x2 = x2.contiguous()
     M = x2.shape[0]
-    w3 = w if w.dim() == 3 else weight_planes(w)
+    w3 = _x3_weight(w)
     N = w3.shape[1]
-    o = torch.empty(M, N, dtype=torch.float32, device=x.device) if out_f32 else None
-    o3 = torch.empty(3, M, N, dtype=torch.bfloat16, device=x.device) if out_x3 else None
-    res = residual.reshape(M, N).contiguous() if residual is not None else None
-    r2 = residual2.reshape(-1, N).contiguous() if residual2 is not None else None
-    epi = (EPI_BIAS if bias is not None else 0) | (EPI_GELU if gelu else 0) | (EPI_RES if residual is not None else 0) \
-        | (EPI_RES2 if residual2 is not None else 0)
-    rc = _lib_x3().nos_gemm_x3_f32a(x2.data_ptr(), w3.data_ptr(), w3[0].numel(),
-                                    bias.data_ptr() if bias is not None else None,
-                                    res.data_ptr() if res is not None else None,
-                                    r2.data_ptr() if r2 is not None else None, r2.shape[0] if r2 is not None else 0,
-                                    o.data_ptr() if o is not None else None,
-                                    o3.data_ptr() if o3 is not None else None, o3[0].numel() if o3 is not None else 0,
-                                    M, N, Kd, epi, cfg, torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError(f"nos gemm_x3 f32a failed: {_lib_x3().nos_gemm_x3_last_error().decode()} (rc={rc})")
-    rf = None if o is None else o.view(*lead, N)
-    r3 = None if o3 is None else o3.view(3, *lead, N)
-    if out_f32 and out_x3:
-        return rf, r3
-    return rf if out_f32 else r3
+    o, o3, _, args, _held = _x3_operands(w3, M, Kd, x.device, bias, gelu, residual, residual2, out_f32, out_x3)
+    _x3_check(_lib_x3().nos_gemm_x3_f32a(x2.data_ptr(), *args, cfg, torch.cuda.current_stream().cuda_stream),
+              "gemm_x3 f32a")
+    return _x3_result(o, o3, lead, N, out_f32, out_x3)
 
 
 # ---- split-K partials + combine-and-LayerNorm --------------------------------------------------
@@ -546,19 +557,12 @@ def gemm_x3_partials(a3: torch.Tensor, w: torch.Tensor, cfg: int, splits: int,
     """Split-K partial sums of ``a @ w^T``: ``[splits, M, N]`` fp32, plane s summing the s-th K range
     (``csrc/gemm_x3.hip``, one launch of tiles x splits workgroups, no epilogue). The consumer adds
     the planes (``kernels.splitk_layernorm``): the hand-off is the kernel boundary."""
-    Kd = a3.shape[-1]
-    a3 = a3.reshape(3, -1, Kd)
-    if not a3.is_contiguous():
-        a3 = a3.contiguous()
-    M = a3.shape[1]
-    w3 = w if w.dim() == 3 else weight_planes(w)
-    N = w3.shape[1]
+    a3, w3, M, N, Kd = _x3_planes(a3, w)
     if out is None:
         out = torch.empty(splits, M, N, dtype=torch.float32, device=a3.device)
-    rc = _lib_x3().nos_gemm_x3_partials(a3.data_ptr(), a3[0].numel(), w3.data_ptr(), w3[0].numel(), out.data_ptr(),
-                                        M, N, Kd, cfg, splits, torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError(f"nos gemm_x3 partials failed: {_lib_x3().nos_gemm_x3_last_error().decode()} (rc={rc})")
+    _x3_check(_lib_x3().nos_gemm_x3_partials(a3.data_ptr(), a3[0].numel(), w3.data_ptr(), w3[0].numel(),
+                                             out.data_ptr(), M, N, Kd, cfg, splits,
+                                             torch.cuda.current_stream().cuda_stream), "gemm_x3 partials")
     return out
 
 
@@ -582,21 +586,14 @@ def gemm_x3_streamk(a3: torch.Tensor, w: torch.Tensor, cfg: int, P: int,
     """Stream-K partial sums of ``a @ w^T`` over ``P`` workgroups: ``([planes, M, N] fp32, map)``;
     plane s of tile t holds its s-th K segment for s < segments(t) (``csrc/streamk.h``), the rest is
     never written. ``kernels.streamk_layernorm`` with the same map is the consumer."""
-    Kd = a3.shape[-1]
-    a3 = a3.reshape(3, -1, Kd)
-    if not a3.is_contiguous():
-        a3 = a3.contiguous()
-    M = a3.shape[1]
-    w3 = w if w.dim() == 3 else weight_planes(w)
-    N = w3.shape[1]
+    a3, w3, M, N, Kd = _x3_planes(a3, w)
     m = streamk_map(M, N, Kd, cfg, P)
     if out is not None and (tuple(out.shape) != (m[6], M, N) or not out.is_contiguous()):
         raise ValueError(f"gemm_x3_streamk: out must be a contiguous [{m[6]}, {M}, {N}] buffer")
     part = out if out is not None else torch.empty(m[6], M, N, dtype=torch.float32, device=a3.device)
-    rc = _lib_x3().nos_gemm_x3_streamk(a3.data_ptr(), a3[0].numel(), w3.data_ptr(), w3[0].numel(), part.data_ptr(),
-                                       M, N, Kd, cfg, m[0], torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError(f"nos gemm_x3 stream-K failed: {_lib_x3().nos_gemm_x3_last_error().decode()} (rc={rc})")
+    _x3_check(_lib_x3().nos_gemm_x3_streamk(a3.data_ptr(), a3[0].numel(), w3.data_ptr(), w3[0].numel(),
+                                            part.data_ptr(), M, N, Kd, cfg, m[0],
+                                            torch.cuda.current_stream().cuda_stream), "gemm_x3 stream-K")
     return part, m
 
 
@@ -696,31 +693,46 @@ def linear_residual_ln_x3(a3: torch.Tensor, w: torch.Tensor, b: torch.Tensor, re
     return unsplit() if choice[0] == "unsplit" else split(choice[1], choice[2])
 
 
+def _x3_key_label(key) -> str:
+    m, n, k, e, o, c, p = key
+    return f"M{m}_N{n}_K{k}_epi{e}_out{o}_cus{c}_pin{p}"
+
+
+def _x3_tile_label(t: int) -> str:
+    return "x".join(map(str, X3_TILES[t][:2])) + f"/{X3_TILES[t][3]} ({t})"
+
+
+def _fused_key_label(key) -> str:
+    m, n, k, r2, ln, c, p = key
+    return f"M{m}_N{n}_K{k}_r2{int(r2)}_ln{int(ln)}_cus{c}_pin{p}"
+
+
+def _fused_choice_label(choice) -> str:
+    return "/".join(map(str, choice))
+
+
 def x3_table() -> Dict[str, str]:
     """The x3 tiles picked so far: shape/epilogue/outputs/slice -> ``BMxBN/<kind>`` (tile id)."""
     with _lock:
-        return {f"M{m}_N{n}_K{k}_epi{e}_out{o}_cus{c}_pin{p}": "x".join(map(str, X3_TILES[v][:2])) + f"/{X3_TILES[v][3]}"
-                + f" ({v})" for (m, n, k, e, o, c, p), v in sorted(_x3_cache.items())}
+        return {_x3_key_label(k): _x3_tile_label(v) for k, v in sorted(_x3_cache.items())}
 
 
 def x3_timings(top: int = 6) -> Dict[str, Dict[str, float]]:
     """The fastest ``top`` tiles the x3 tuner timed per key: ``BMxBN/<kind> (id)`` -> µs per call."""
     with _lock:
-        return {f"M{m}_N{n}_K{k}_epi{e}_out{o}_cus{c}_pin{p}":
-                {"x".join(map(str, X3_TILES[t][:2])) + f"/{X3_TILES[t][3]} ({t})": round(ms * 1000 / 3, 2)
-                 for t, ms in sorted(v.items(), key=lambda x: x[1])[:top]}
-                for (m, n, k, e, o, c, p), v in sorted(_x3_times.items())}
+        return {_x3_key_label(k): {_x3_tile_label(t): round(ms * 1000 / 3, 2)
+                                   for t, ms in sorted(v.items(), key=lambda x: x[1])[:top]}
+                for k, v in sorted(_x3_times.items())}
 
 
 def fused_timings() -> Dict[str, Dict[str, float]]:
     """Every pipeline the projection/fc2 tuner timed, per key: ``/``-joined choice -> µs per call."""
     with _lock:
-        return {f"M{m}_N{n}_K{k}_r2{int(r2)}_ln{int(ln)}_cus{c}_pin{p}":
-                {"/".join(map(str, ch)): round(t * 1000 / 3, 2) for ch, t in sorted(v.items(), key=lambda x: x[1])}
-                for (m, n, k, r2, ln, c, p), v in sorted(_fused_times.items())}
+        return {_fused_key_label(k): {_fused_choice_label(ch): round(t * 1000 / 3, 2)
+                                      for ch, t in sorted(v.items(), key=lambda x: x[1])}
+                for k, v in sorted(_fused_times.items())}
 
 
 def fused_table() -> Dict[str, str]:
     with _lock:
-        return {f"M{m}_N{n}_K{k}_r2{int(r2)}_ln{int(ln)}_cus{c}_pin{p}": "/".join(map(str, v))
-                for (m, n, k, r2, ln, c, p), v in sorted(_fused_cache.items())}
+        return {_fused_key_label(k): _fused_choice_label(v) for k, v in sorted(_fused_cache.items())}
