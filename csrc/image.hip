@@ -14,6 +14,7 @@
 //    patch matrix (row (b, i, j), column (c, u, v), as patch_planes_f32 in head.hip); optionally the fp32 pixels
 //    [B][3][H][W] as well. So every layout is bit-equal to the RGB kernel on the converted frame.
 //  * Detections (image_detect.h): detections_f32 and merge_detections_f32.
+//  * Tracking (image_track.h): track_update_f32, the detections of successive frames associated in device state.
 //  * Entries. The extern "C" functions at the end check every argument of an outside caller, fill the kernel's
 //    arguments and launch; the arguments all image entries share travel as one struct (Common).
 #include <hip/hip_runtime.h>
@@ -25,6 +26,7 @@
 #include <type_traits>
 
 #include "image_detect.h"
+#include "image_track.h"
 #include "image_stage.h"
 #include "image_yuv.h"
 
@@ -767,6 +769,27 @@ int nos_merge_detections_f32(const float* logits, const float* boxes, const int*
                      origins, tile_h, tile_w, threshold, match_threshold, iou, B * M, M, C, scores, labels, out_boxes,
                      tile, count);
   return check("merge_detections_f32");
+}
+
+// One frame's detections associated with a tracker's state, which is updated in place (track_update_f32): count [1]
+// int32, scores [N] fp32, labels [N] int32, boxes [N][4] fp32 (corners), as the two entries above write them; the state
+// t_boxes / t_vel [T][4] fp32, t_labels / t_ids / t_hits / t_misses [T] int32, next_id [1], dropped [1] int32; motion: 0
+// no prediction, 1 constant velocity with velocity_gain in [0, 1] -> track_id [N], track_hits [N] int32 by input row
+int nos_track_update_f32(const int* count, const float* scores, const int* labels, const float* boxes, int N,
+                         float* t_boxes, float* t_vel, int* t_labels, int* t_ids, int* t_hits, int* t_misses,
+                         int* next_id, int* dropped, int T, float match_threshold, int max_age, float birth_threshold,
+                         int motion, float velocity_gain, int* track_id, int* track_hits, void* stream) {
+  if (!count || !scores || !labels || !boxes || !t_boxes || !t_vel || !t_labels || !t_ids || !t_hits || !t_misses ||
+      !next_id || !dropped || !track_id || !track_hits)
+    return fail("track_update: null operand");
+  if (N <= 0 || N > MMAX || T <= 0 || T > TMAX) return fail("track_update: 0 < rows <= 1024, 0 < slots <= 1024");
+  if (motion != 0 && motion != 1) return fail("track_update: the motion is 0 (none) or 1 (constant)");
+  if (!(match_threshold >= 0.f) || max_age < 0 || !(velocity_gain >= 0.f && velocity_gain <= 1.f))
+    return fail("track_update: match_threshold >= 0, max_age >= 0, 0 <= velocity_gain <= 1");
+  hipLaunchKernelGGL(track_update_f32, dim3(1), dim3(DT), 0, reinterpret_cast<hipStream_t>(stream), count, scores,
+                     labels, boxes, N, t_boxes, t_vel, t_labels, t_ids, t_hits, t_misses, next_id, dropped, T,
+                     match_threshold, max_age, birth_threshold, motion, velocity_gain, track_id, track_hits);
+  return check("track_update_f32");
 }
 
 }  // extern "C"

@@ -35,6 +35,12 @@ staged in place from its planes (``Frame.tile_planes``: ``*_hip_us``) against th
 (siting ``left``) and ``yuv_tiles_p010_pq_*`` (BT.2020, peak 1000 nits); and, on the whole GPU only,
 ``detect_tiled_nv12_ms`` against ``detect_tiled`` of the converted frame, conversion included
 (``detect_tiled_nv12_rgb_ms``).
+Three rows time the tracker (``--rows track`` runs them alone): ``track_n100_t256_*``, ``track_n400_t256_*`` and
+``track_n1000_t1024_*``, ``track_update`` of ``n`` rows on a state of ``t`` slots against its torch reference, on a
+constructed scene in which about half the rows continue a track, a quarter start one and an eighth of the matched
+number of tracks die. The state is restored from a saved copy inside the timed graph, so every replay does the same
+work; ``*_restore_us`` is that copy alone, which both sides include. On the whole GPU ``track_image_ms`` stands beside
+``detect_image_ms`` and ``track_tiled_ms`` beside ``detect_tiled_ms`` (the same calls with the tracker's launch).
 """
 from __future__ import annotations
 
@@ -83,7 +89,8 @@ def main() -> int:
     ap.add_argument("--out", default="gpurun_out/kbench.json")
     ap.add_argument("--only", choices=("all", "attn", "gemm", "model", "modes", "image"), default="all")
     ap.add_argument("--slices", default="spx,dpx,qpx,cpx")
-    ap.add_argument("--rows", choices=("all", "tiles"), default="all", help="image: every row, or the tiled-detection rows alone")
+    ap.add_argument("--rows", choices=("all", "tiles", "track"), default="all",
+                    help="image: every row, or the tiled-detection rows alone, or the tracker's")
     ap.add_argument("--partitions", type=int, default=0, help="modes: run only this many partitions of each mode")
     ap.add_argument("--free-s", type=float, default=0.0,
                     help="modes: serve free-running (one thread per pod, as the bench) for this many seconds "
@@ -354,7 +361,10 @@ def image_bench(a) -> int:
                            lambda: I.image_patch_planes(conv, out, 16, IMAGENET_MEAN, IMAGENET_STD),
                            lambda: I.image_patch_planes(fr.rgb(), out, 16, IMAGENET_MEAN, IMAGENET_STD),
                            s, a.iters)
-            tiles_rows(r, pair, s, a.iters, rounds, whole_gpu=cus is None)
+            if a.rows != "track":
+                tiles_rows(r, pair, s, a.iters, rounds, whole_gpu=cus is None)
+            if a.rows != "tiles":
+                track_rows(r, s, a.iters, rounds, whole_gpu=cus is None)
             if not full:
                 print(json.dumps(r), flush=True)
                 results.append(r)
@@ -445,6 +455,109 @@ def tiles_rows(r, pair, s, iters, rounds, whole_gpu):
     for k, vs in t.items():
         r[f"{k}_ms"] = round(statistics.median(vs) / 1000.0, 3)
     r["yuv_tiles_model_rounds_ms"] = {k: [round(v / 1000.0, 3) for v in vs] for k, vs in t.items()}
+
+
+def track_scene(n: int, T: int, seed: int = 0):
+    """``(state, lists, what)``: a tracker of ``T`` slots holding ``matched + dying`` tracks on a lattice of 64 px
+    cells, and ``n`` rows of which ``matched = min(n, T) // 2`` continue a track (moved by its velocity and a pixel),
+    ``n // 4`` start one and the rest lie behind ``count``; the ``matched // 8`` other tracks are at ``max_age``."""
+    from walkai_nos_amd.ops import image as I
+    g = torch.Generator().manual_seed(3000 + seed + n)
+    matched, born = min(n, T) // 2, n // 4
+    dying = matched // 8
+    live = matched + dying
+    cell = torch.arange(live + born)
+    xy = torch.stack((64.0 * (cell % 40), 64.0 * (cell // 40)), dim=1) + 8.0
+    state = I.track_state(T, "cpu")
+    slots = torch.randperm(T, generator=g)[:live]
+    state.boxes[slots] = torch.cat((xy[:live], xy[:live] + 32.0), dim=1)
+    state.vel[slots] = torch.tensor([2.0, 1.0, 2.0, 1.0])
+    state.labels[slots] = (cell[:live] % 16).to(torch.int32)
+    state.ids[slots] = torch.arange(1, live + 1, dtype=torch.int32)
+    state.hits[slots] = 3
+    state.misses[slots[matched:]] = 30
+    state.next_id.fill_(live + 1)
+    seen = torch.cat((cell[:matched], cell[live:]))                    # the matched objects and the new ones
+    rows = torch.arange(seen.shape[0])
+    order = torch.randperm(seen.shape[0], generator=g)
+    seen = seen[order]
+    boxes = torch.zeros(n, 4)
+    boxes[rows] = torch.cat((xy[seen] + 3.0, xy[seen] + 35.0), dim=1)
+    scores = torch.zeros(n)
+    scores[rows] = 0.25 + 0.7 * (torch.randperm(seen.shape[0], generator=g).float() + 1.0) / seen.shape[0]
+    labels = torch.zeros(n, dtype=torch.int32)
+    labels[rows] = (seen % 16).to(torch.int32)
+    count = torch.tensor([seen.shape[0]], dtype=torch.int32)
+    return state, (count, scores, labels, boxes), {"matched": matched, "born": born, "dying": dying}
+
+
+def track_rows(r, s, iters, rounds, whole_gpu):
+    """The tracker (see the module docstring): ``track_n*_t*_hip_us`` against ``*_torch_us``, both with the restore of
+    the state that ``*_restore_us`` times alone."""
+    import statistics
+
+    from walkai_nos_amd.models.workload.tracker import Tracker
+    from walkai_nos_amd.models.workload.yolos import YolosSmall
+    from walkai_nos_amd.ops import image as I
+    for n, T in ((100, 256), (400, 256), (1000, 1024)):
+        saved, lists, what = track_scene(n, T)
+        saved = [t.cuda() for t in saved.tensors()]
+        lists = [t.cuda() for t in lists]
+        state = I.track_state(T, "cuda")
+
+        def restore():
+            for dst, src in zip(state.tensors(), saved):
+                dst.copy_(src)
+
+        def hip():
+            restore()
+            return I.track_update(state, *lists)
+
+        def composed():
+            restore()
+            return I.track_update_reference(state, *lists)
+        with torch.cuda.stream(s):
+            a, b = hip(), [t.clone() for t in state.tensors()]
+            c, d = composed(), [t.clone() for t in state.tensors()]
+            s.synchronize()
+        same = all(torch.equal(x, y) for x, y in zip(a, c)) and all(
+            torch.equal(x, y) for x, y in zip(b[2:], d[2:])) and all(
+            torch.allclose(x, y, rtol=0, atol=1e-3) for x, y in zip(b[:2], d[:2]))
+        ids = a[0].cpu()
+        what.update(rows_with_a_track=int((ids > 0).sum()), live_after=int((b[3] != 0).sum()),
+                    next_id=int(b[6].item()), dropped=int(b[7].item()), hip_equals_torch=bool(same))
+        t = {"hip": [], "torch": [], "restore": []}
+        for _ in range(rounds):
+            t["hip"].append(timeit(hip, s, iters))
+            t["torch"].append(timeit(composed, s, 2))           # n steps of several launches: fewer calls per graph
+            t["restore"].append(timeit(restore, s, iters))
+        name = f"track_n{n}_t{T}"
+        for k, vs in t.items():
+            r[f"{name}_{k}_us"] = round(statistics.median(vs), 1)
+        r[f"{name}_rounds_us"] = {k: [round(v, 1) for v in vs] for k, vs in t.items()}
+        r[f"{name}_scene"] = what
+    if not whole_gpu:
+        return
+    g = torch.Generator().manual_seed(2)
+    small = torch.randint(0, 256, (480, 640, 3), generator=g, dtype=torch.uint8).cuda()
+    large = torch.randint(0, 256, (2160, 3840, 3), generator=g, dtype=torch.uint8).cuda()
+    with torch.cuda.stream(s), torch.no_grad():
+        m = YolosSmall().cuda().eval()
+        # thresholds under which the random model keeps rows, so that the tracker has work: its state grows over
+        # the replays of the timed graph until every row continues a track
+        tr_i, tr_t = Tracker(capacity=256, device="cuda"), Tracker(capacity=1024, device="cuda")
+        it = max(2, iters // 5)
+        t = {"detect_image": [], "track_image": [], "detect_tiled": [], "track_tiled": []}
+        for _ in range(rounds):
+            t["detect_image"].append(timeit(lambda: m.detect_image(small, 0.0), s, it))
+            t["track_image"].append(timeit(lambda: m.track_image(small, tr_i, 0.0), s, it))
+            t["detect_tiled"].append(timeit(lambda: m.detect_tiled(large, (2, 2), 0.2, 0.0), s, it))
+            t["track_tiled"].append(timeit(lambda: m.track_tiled(large, tr_t, (2, 2), 0.2, 0.0), s, it))
+        s.synchronize()
+    for k, vs in t.items():
+        r[f"{k}_thr0_ms"] = round(statistics.median(vs) / 1000.0, 3)
+    r["track_model_rounds_ms"] = {k: [round(v / 1000.0, 3) for v in vs] for k, vs in t.items()}
+    r["track_model_live"] = {"track_image": len(tr_i.tracks()), "track_tiled": len(tr_t.tracks())}
 
 
 def free_running(slots, seconds: float) -> int:

@@ -29,6 +29,11 @@ pq|hlg`` (with ``--peak-nits``) that a 10- or 12-bit format's codes are HDR and 
 ``--tile-overlap``, ``--match ios|iou``, ``--match-threshold``): the JSON line then carries ``"tiles"``, the tile count,
 and ``"detections"`` counts the merged boxes. With a YUV ``--pixel-format`` (and ``--transfer``, ``--peak-nits``) the
 tiles are staged straight from the surface's planes: no flag, the frame's own ``tile_planes``.
+``--track`` gives every detection a stable id across the frames (``YolosSmall.track_image`` / ``track_tiled``, one more
+launch inside the captured graph, whose replays advance the tracker; ``--track-iou``, ``--track-max-age``,
+``--track-min-hits``, ``--track-capacity``, ``--track-motion``). The tracker is reset after the warm-ups and again after
+the capture, so the timed loop starts at frame 0; the JSON line then carries a ``"track"`` block: the live tracks (and
+those of them seen in ``--track-min-hits`` frames), the ids issued, the births dropped for lack of a slot, the frames.
 """
 from __future__ import annotations
 
@@ -113,7 +118,25 @@ def main(argv=None) -> int:
                     help="--tiles: how two tiles' boxes are compared: intersection over the smaller area, or over the union")
     ap.add_argument("--match-threshold", type=float, default=0.5,
                     help="--tiles: a box is dropped when a kept box of the same label from another tile overlaps it by more")
+    ap.add_argument("--track", action="store_true", help="--end-to-end: stable ids across frames (a tracker in the graph)")
+    ap.add_argument("--track-iou", type=float, default=0.3, help="--track: the IoU a detection must exceed to continue a track")
+    ap.add_argument("--track-max-age", type=int, default=30, help="--track: frames a track survives unmatched")
+    ap.add_argument("--track-min-hits", type=int, default=1, help="--track: frames a track is seen in before it is counted as confirmed")
+    ap.add_argument("--track-capacity", type=int, default=256, help="--track: slots of the tracker (1..1024 run in HIP)")
+    ap.add_argument("--track-motion", choices=("constant", "none"), default="constant",
+                    help="--track: compare a track one frame along its velocity, or where it was")
     args = ap.parse_args(argv)
+    if args.track:
+        if not args.end_to_end:
+            ap.error("--track takes --end-to-end")
+        if not args.track_iou >= 0.0:
+            ap.error(f"--track-iou {args.track_iou!r} is not a number from 0 up")
+        if args.track_max_age < 0:
+            ap.error(f"--track-max-age {args.track_max_age} is negative")
+        if args.track_min_hits < 1:
+            ap.error(f"--track-min-hits {args.track_min_hits} is not a number of frames from 1 up")
+        if not 1 <= args.track_capacity <= 1024:
+            ap.error(f"--track-capacity {args.track_capacity} is not in 1..1024")
     tiles = None
     if args.tiles:
         if not args.end_to_end:
@@ -139,6 +162,7 @@ def main(argv=None) -> int:
     dev = "cuda:0"
     model = YolosSmall().to(dev).eval()
     seed = int(os.environ.get("NOS_POD_SEED", "0"))
+    tracker = None
     if args.end_to_end:
         from ..models.workload.processor import Nv12, Packed, YolosProcessor, Yuv420p
         ih, iw = (int(v) for v in args.image_hw.split(","))
@@ -180,8 +204,17 @@ def main(argv=None) -> int:
         if tiles is not None:
             th, tw, origins = model.processor.tile_plan((ih, iw), tiles, args.tile_overlap, model.c.num_detection_tokens)
             hw = model.processor.size((th, tw))
+        if args.track:
+            from ..models.workload.tracker import Tracker
+            tracker = Tracker(args.track_capacity, args.track_iou, args.track_max_age, motion=args.track_motion,
+                              min_hits=args.track_min_hits, device=dev)
 
         def infer():
+            if tracker is not None:
+                if tiles is not None:
+                    return model.track_tiled(img, tracker, tiles, args.tile_overlap, args.threshold, args.match,
+                                             args.match_threshold)
+                return model.track_image(img, tracker, args.threshold)
             if tiles is not None:
                 return model.detect_tiled(img, tiles, args.tile_overlap, args.threshold, args.match, args.match_threshold)
             return model.detect_image(img, args.threshold)
@@ -202,12 +235,17 @@ def main(argv=None) -> int:
     with torch.no_grad(), torch.cuda.stream(stream):
         for _ in range(2):
             res = infer()
+        if tracker is not None:
+            tracker.reset()     # the warm-ups were no frames of the stream
     stream.synchronize()
     graph = None
     if not args.no_graph:
         graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(graph, stream=stream):
             res = infer()
+        if tracker is not None:
+            with torch.cuda.stream(stream):
+                tracker.reset()     # nor was the capture, where the launch may have run
         stream.synchronize()
     out: Dict[str, Any] = {"pid": os.getpid(), "slice_ids": os.environ.get("NOS_SLICE_IDS", ""),
                            "hsa_cu_mask": os.environ.get("HSA_CU_MASK", ""), "slice_cus": K.slice_cus(),
@@ -255,6 +293,12 @@ def main(argv=None) -> int:
             out["tiles"] = len(origins)
             out["tile_hw"] = [th, tw]
         out["detections"] = int(res["count"].sum().item())   # of the last inference
+        if tracker is not None:
+            live = tracker.tracks()
+            out["track"] = {"live": len(live), "confirmed": sum(1 for t in live if t["hits"] >= tracker.min_hits),
+                            "ids_issued": int(tracker.state.next_id.item()) - 1,
+                            "dropped": int(tracker.state.dropped.item()), "frames": len(lat),
+                            "capacity": tracker.capacity, "motion": args.track_motion}
     if census is not None:
         out["census"] = census
     out["hbm"] = _shim()

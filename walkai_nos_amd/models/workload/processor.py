@@ -391,6 +391,25 @@ class YolosProcessor:
         return [{"scores": scores[i, :n], "labels": labels[i, :n].long(), "boxes": boxes[i, :n]}
                 for i, n in enumerate(count.tolist())]
 
+    @staticmethod
+    def tracked_results(count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor,
+                        track_id: torch.Tensor, track_hits: torch.Tensor, min_hits: int = 1) \
+            -> List[Dict[str, torch.Tensor]]:
+        """:meth:`results` of a tracked frame (``YolosSmall.track_image`` / ``track_tiled``), each entry with the
+        rows' ``"ids"`` and ``"hits"``, restricted to the rows that have a track seen in at least ``min_hits`` frames
+        (this reads ``count`` on the host)."""
+        if scores.dim() == 1:
+            scores, labels, boxes, track_id, track_hits = scores[None], labels[None], boxes[None], \
+                track_id[None], track_hits[None]
+        track_id, track_hits = track_id.reshape(scores.shape), track_hits.reshape(scores.shape)
+        out = []
+        for i, n in enumerate(count.tolist()):
+            keep = (track_id[i, :n] > 0) & (track_hits[i, :n] >= min_hits)
+            out.append({"scores": scores[i, :n][keep], "labels": labels[i, :n][keep].long(),
+                        "boxes": boxes[i, :n][keep], "ids": track_id[i, :n][keep].long(),
+                        "hits": track_hits[i, :n][keep].long()})
+        return out
+
     def post_process(self, logits: torch.Tensor, boxes: torch.Tensor, threshold: float = 0.5,
                      target_sizes=None) -> List[Dict[str, torch.Tensor]]:
         """``post_process_object_detection``: per image the scores, labels and ``(x0, y0, x1, y1)`` boxes

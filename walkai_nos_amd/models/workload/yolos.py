@@ -471,6 +471,20 @@ class YolosSmall(nn.Module):
         return {"logits": logits, "pred_boxes": boxes, "origins": org.clone(), "tile_hw": (th, tw), "count": count,
                 "scores": scores, "labels": labels, "boxes": xyxy, "tile": tile}
 
+    def track_image(self, image_u8, tracker, threshold: float = 0.5) -> Dict[str, torch.Tensor]:
+        """:meth:`detect_image` and ``tracker.update`` (``tracker.Tracker``): the same dict with ``track_id`` and
+        ``track_hits`` ``[1, nd]`` int32 beside ``labels`` — the id of each row's track and the frames it has been
+        seen in, 0 behind ``count``. No host synchronisation either: captured as one graph, each replay detects on the
+        frame then in the buffers and advances the tracker by one frame."""
+        return tracker.update(self.detect_image(image_u8, threshold))
+
+    def track_tiled(self, image_u8, tracker, tiles: Tuple[int, int] = (2, 2), overlap: float = 0.2,
+                    threshold: float = 0.5, match: str = "ios", match_threshold: float = 0.5) -> Dict[str, object]:
+        """:meth:`detect_tiled` and ``tracker.update``: the merged list with ``track_id`` and ``track_hits``
+        ``[B * nd]`` int32 beside it, capturable as :meth:`track_image` is. (``match`` and ``match_threshold`` are the
+        cross-tile merge's; the tracker's own are set on the tracker.)"""
+        return tracker.update(self.detect_tiled(image_u8, tiles, overlap, threshold, match, match_threshold))
+
     def _target_sizes(self, img: torch.Tensor) -> torch.Tensor:
         """``[B, 2]`` fp32 (height, width) of the original images on their device, cached: a captured
         graph must not copy from the host."""

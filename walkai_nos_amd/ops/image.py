@@ -63,12 +63,18 @@ which is also what runs on the CPU, with the ``torch`` backend and past a layout
   the tiles of one YUV frame staged straight from its planes by one launch (every layout, depth, chroma mode and
   transfer of the general YUV front end; the tile origins come from :func:`origin_tensor`'s table, the one the merge
   reads), bit-equal to :func:`tiled_patch_planes` of the converted frame: no RGB frame is written and read back.
+* :func:`track_state` / :func:`track_update` — the detections of successive frames associated on the device: a greedy
+  IoU tracker with an optional constant-velocity prediction (:data:`MOTIONS`) as one launch per frame. Its state
+  (:class:`TrackState`) lives in device buffers updated in place, so each replay of a captured graph is the next frame;
+  the ids come back in the row order of the lists passed in. Kalman filtering, appearance features, Hungarian
+  assignment, a second pass on low scores and more than 1024 tracks are not offered.
 """
 from __future__ import annotations
 
 import ctypes
 import math
 import threading
+from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -128,6 +134,7 @@ def _L() -> ctypes.CDLL:
             L.nos_image_patch_planes_yuv_tiles.argtypes = [src, hdr, ip, vp, i32, i32, i32] + tail
             L.nos_merge_detections_f32.argtypes = [vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, i32, vp, vp, vp, vp,
                                                    vp, vp]
+            L.nos_track_update_f32.argtypes = [vp] * 4 + [i32] + [vp] * 8 + [i32, f32, i32, f32, i32, f32, vp, vp, vp]
             L.nos_image_last_error.restype = ctypes.c_char_p
             if (L.nos_image_taps(), L.nos_image_max_footprint(), L.nos_image_max_patch(),
                     L.nos_image_nv12_max_footprint(), L.nos_image_yuv420p_max_footprint(),
@@ -1445,3 +1452,211 @@ def merge_detections(logits: torch.Tensor, boxes: torch.Tensor, origins, tile_hw
                                        xyxy.data_ptr(), tile.data_ptr(), torch.cuda.current_stream().cuda_stream)
     _check(rc, "merge_detections")
     return count, scores, labels, xyxy, tile
+
+
+# ---- detections associated across frames --------------------------------------------------------------
+#: what a track's box is compared at: where it was (``none``), or one frame further along its velocity
+#: (``nos_track_update_f32``'s flag)
+MOTIONS = {"none": 0, "constant": 1}
+#: tracker limits: slots of one state
+MAX_TRACKS = 1024
+
+
+@dataclass
+class TrackState:
+    """A tracker's state, entirely on the device (:func:`track_state`): ``boxes [T, 4]`` fp32 (corners, in the pixels
+    the detections come in), ``vel [T, 4]`` fp32 (per-frame displacement of the four corners), ``labels``, ``ids``
+    (0: a free slot; ids start at 1), ``hits`` (frames matched, birth included), ``misses`` (consecutive frames
+    unmatched) ``[T]`` int32, ``next_id [1]`` and ``dropped [1]`` int32 (births refused for lack of a slot). A free
+    slot holds zeros in every field."""
+    boxes: torch.Tensor
+    vel: torch.Tensor
+    labels: torch.Tensor
+    ids: torch.Tensor
+    hits: torch.Tensor
+    misses: torch.Tensor
+    next_id: torch.Tensor
+    dropped: torch.Tensor
+
+    @property
+    def capacity(self) -> int:
+        return self.ids.shape[0]
+
+    @property
+    def device(self) -> torch.device:
+        return self.ids.device
+
+    def tensors(self) -> Tuple[torch.Tensor, ...]:
+        return (self.boxes, self.vel, self.labels, self.ids, self.hits, self.misses, self.next_id, self.dropped)
+
+    def reset(self) -> None:
+        """No track, ``next_id`` 1, nothing dropped: fills on the current stream, in place (capturable)."""
+        for t in self.tensors():
+            t.zero_()
+        self.next_id.fill_(1)
+
+
+def track_state(capacity: int = 256, device=None) -> TrackState:
+    """An empty :class:`TrackState` of ``capacity`` slots on ``device``."""
+    T = int(capacity)
+    if T < 1:
+        raise ValueError(f"track_state: capacity {capacity!r} is not a positive number of slots")
+    z = lambda *shape, dtype=torch.int32: torch.zeros(*shape, dtype=dtype, device=device)      # noqa: E731
+    state = TrackState(z(T, 4, dtype=torch.float32), z(T, 4, dtype=torch.float32), z(T), z(T), z(T), z(T), z(1), z(1))
+    state.reset()
+    return state
+
+
+def track_params_check(match_threshold: float, max_age: int, motion: str, velocity_gain: float) -> None:
+    """``ValueError`` for parameters :func:`track_update` does not take."""
+    if motion not in MOTIONS:
+        raise ValueError(f"track_update: motion {motion!r} is none of {tuple(MOTIONS)}")
+    if not match_threshold >= 0.0:
+        raise ValueError(f"track_update: match_threshold {match_threshold!r} is not a number from 0 up")
+    if not max_age >= 0:
+        raise ValueError(f"track_update: max_age {max_age!r} is not a number of frames from 0 up")
+    if not 0.0 <= velocity_gain <= 1.0:
+        raise ValueError(f"track_update: velocity_gain {velocity_gain!r} is not in [0, 1]")
+
+
+def _track_check(state: TrackState, count, scores, labels, boxes, match_threshold, max_age, motion, velocity_gain) \
+        -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The arguments of :func:`track_update` checked; the lists as ``count [1]``, ``scores [N]``, ``labels [N]``,
+    ``boxes [N, 4]`` (``[1, M]`` views of one image's :func:`detections` are flattened)."""
+    track_params_check(match_threshold, max_age, motion, velocity_gain)
+    if scores.dim() == 2 and scores.shape[0] == 1:
+        scores, labels, boxes = scores[0], labels.reshape(-1), boxes.reshape(-1, 4)
+    if scores.dim() != 1 or count.numel() != 1:
+        raise ValueError("track_update: count and scores are one image's: count [1], scores [N] (or [1, N])")
+    N = scores.shape[0]
+    if labels.shape != (N,) or boxes.shape != (N, 4):
+        raise ValueError(f"track_update: labels {tuple(labels.shape)} and boxes {tuple(boxes.shape)} do not go with "
+                         f"the {N} scores")
+    for name, t in (("count", count), ("scores", scores), ("labels", labels), ("boxes", boxes)):
+        if t.device != state.device:
+            raise ValueError(f"track_update: state is on {state.device}, {name} on {t.device}")
+    return count.reshape(1), scores, labels, boxes
+
+
+def track_update_reference(state: TrackState, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor,
+                           boxes: torch.Tensor, match_threshold: float = 0.3, max_age: int = 30,
+                           birth_threshold: float = 0.0, motion: str = "constant", velocity_gain: float = 0.5) \
+        -> Tuple[torch.Tensor, torch.Tensor]:
+    """The torch composition of :func:`track_update`, with the same effect on ``state`` in place and without a host
+    sync (the greedy pass is a loop of ``N`` steps on the device, each over one row of the candidate x track IoU
+    matrix). The lists are taken in the state's fp32."""
+    count, scores, labels, boxes = _track_check(state, count, scores, labels, boxes, match_threshold, max_age, motion,
+                                                velocity_gain)
+    if scores.shape[0] == 0:        # no row: one that is no candidate, and nothing to return
+        none = track_update_reference(state, count, scores.new_zeros(1), labels.new_zeros(1), boxes.new_zeros(1, 4),
+                                      match_threshold, max_age, birth_threshold, motion, velocity_gain)
+        return none[0][:0], none[1][:0]
+    N, T, dev = scores.shape[0], state.capacity, state.device
+    scores, boxes, labels = scores.to(torch.float32), boxes.to(torch.float32), labels.to(torch.int32)
+    constant = motion == "constant"
+    rows, slots = torch.arange(N, device=dev), torch.arange(T, device=dev)
+    cand = (rows < count.clamp(0, N)) & (scores > 0)
+    # candidates first, by score descending; the stable sort leaves ties in row order
+    order = torch.sort(torch.where(cand, -scores, torch.full_like(scores, math.inf)), stable=True).indices
+    sc, lb, bx, cd = scores[order], labels[order], boxes[order], cand[order]
+    live = state.ids != 0
+    pred = state.boxes + state.vel if constant else state.boxes
+    ov = pair_overlap(bx[:, None, :], pred[None, :, :], "iou")
+    ok = (ov > match_threshold) & (lb[:, None] == state.labels[None, :]) & live[None, :] & cd[:, None]
+    ov = torch.where(ok, ov, torch.full_like(ov, -1.0))
+    taken = torch.zeros(T, dtype=torch.bool, device=dev)
+    match = torch.full((N,), T, dtype=torch.int64, device=dev)          # T: no track
+    for c in range(N):
+        v = torch.where(taken, -1.0, ov[c])
+        best = v.max()
+        slot = torch.where((v == best) & (best >= 0), slots, T).min()   # the lowest slot of the largest overlap
+        match[c] = slot
+        taken = taken | (slots == slot)
+    hit = match[:, None] == slots[None, :]                              # [N, T], at most a one per row and column
+    rank_of = hit.to(torch.int8).argmax(0)                              # the candidate a taken track took
+    box_in = bx[rank_of]
+    vel = state.vel + velocity_gain * ((box_in - state.boxes) - state.vel) if constant else state.vel
+    missed = live & ~taken
+    misses = torch.where(missed, state.misses + 1, torch.zeros_like(state.misses))
+    dead = missed & (misses > max_age)
+    new_boxes = torch.where(taken[:, None], box_in, state.boxes + state.vel if constant else state.boxes)
+    new_vel = torch.where(taken[:, None], vel, state.vel)
+    hits = state.hits + taken.to(torch.int32)
+    keep = live & ~dead
+    k4 = keep[:, None]
+    new_boxes, new_vel = torch.where(k4, new_boxes, 0.0), torch.where(k4, new_vel, 0.0)
+    new_labels, new_ids = state.labels * keep, state.ids * keep
+    hits, misses = hits * keep, misses * keep
+    # births: the b-th unmatched candidate above the birth threshold into the b-th free slot
+    want = cd & (match == T) & (sc > birth_threshold)
+    free = ~keep
+    b = torch.cumsum(want, 0) - 1
+    nb, nf = want.sum(), free.sum()
+    born = want & (b < nf)
+    free_slots = torch.sort((~free).to(torch.int8), stable=True).indices        # free slots first, ascending
+    dest = torch.where(born, free_slots[b.clamp(0, T - 1)], T)                   # T: a spare row behind the state
+    first = state.next_id[0]
+    new_id = (first + b).to(torch.int32) * born
+
+    def place(old, new):
+        ext = torch.cat((old, old.new_zeros((1,) + tuple(old.shape[1:]))))
+        ext.index_copy_(0, dest, new.to(old.dtype))
+        return ext[:T]
+    one = born.to(torch.int32)
+    new_boxes, new_vel = place(new_boxes, bx), place(new_vel, torch.zeros_like(bx))
+    new_labels, new_ids = place(new_labels.to(torch.int32), lb), place(new_ids.to(torch.int32), new_id)
+    hits, misses = place(hits.to(torch.int32), one), place(misses.to(torch.int32), torch.zeros_like(one))
+    # the outputs by rank, then back to the input's rows
+    ext_ids, ext_hits = torch.cat((new_ids, new_ids.new_zeros(1))), torch.cat((hits, hits.new_zeros(1)))
+    out_id = torch.where(born, new_id, ext_ids[match] * cd)
+    out_hits = torch.where(born, one, ext_hits[match] * cd)
+    track_id = torch.zeros(N, dtype=torch.int32, device=dev).index_copy_(0, order, out_id.to(torch.int32))
+    track_hits = torch.zeros(N, dtype=torch.int32, device=dev).index_copy_(0, order, out_hits.to(torch.int32))
+    started = torch.minimum(nb, nf)
+    state.next_id.add_(started.to(torch.int32))
+    state.dropped.add_((nb - started).to(torch.int32))
+    for t, new in zip(state.tensors()[:6], (new_boxes, new_vel, new_labels, new_ids, hits, misses)):
+        t.copy_(new)
+    return track_id, track_hits
+
+
+def track_update(state: TrackState, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor,
+                 boxes: torch.Tensor, match_threshold: float = 0.3, max_age: int = 30, birth_threshold: float = 0.0,
+                 motion: str = "constant", velocity_gain: float = 0.5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One frame's detections — ``count [1]`` int32, ``scores [N]``, ``labels [N]`` int32, ``boxes [N, 4]`` (corners),
+    what :func:`detections` (one image; its ``[1, M]`` views are accepted) and :func:`merge_detections` return —
+    associated with the tracks of ``state``, which is updated in place, with no host synchronisation: captured in a
+    graph, each replay is the next frame. Returns ``(track_id [N], track_hits [N])`` int32 in the input's row order:
+    the id of the row's track and its ``hits`` after this update, 0 for a row without one.
+
+    Row ``r`` is a candidate when ``r < count`` (clamped to ``[0, N]``) and ``scores[r] > 0``; a NaN score never is.
+
+    1. A live track's predicted box is ``boxes + vel`` (``motion="constant"``) or ``boxes`` (``"none"``).
+    2. Candidates go by score descending (ties: the lower row). Each takes the live track of the same label that no
+       earlier candidate took and whose IoU with the predicted box (:func:`pair_overlap`, ``"iou"``) is largest, when
+       that exceeds ``match_threshold`` (ties: the lowest slot). A box of no or negative extent matches nothing.
+    3. A matched track: ``vel += velocity_gain * ((box - boxes) - vel)`` (zero under ``"none"``), ``boxes = box`` bit
+       for bit, ``hits += 1``, ``misses = 0``.
+    4. Any other live track: ``misses += 1``; past ``max_age`` its slot is freed and zeroed, else ``boxes += vel``
+       under ``"constant"``.
+    5. Unmatched candidates with ``score > birth_threshold`` start tracks, in score order in the free slots ascending
+       (those freed in step 4 included): ``ids = next_id++``, ``hits = 1``. When the slots run out, each remaining one
+       adds 1 to ``dropped``.
+
+    One HIP launch (one workgroup) for fp32 lists up to 1024 rows and a state up to 1024 slots; past that, for other
+    dtypes, on the CPU and with the ``torch`` backend :func:`track_update_reference`."""
+    lists = _track_check(state, count, scores, labels, boxes, match_threshold, max_age, motion, velocity_gain)
+    count, scores, labels, boxes = lists
+    N, T = scores.shape[0], state.capacity
+    if not _use_hip(scores) or scores.dtype != torch.float32 or boxes.dtype != torch.float32 \
+            or labels.dtype != torch.int32 or count.dtype != torch.int32 or N > MAX_ROWS or T > MAX_TRACKS or N < 1:
+        return track_update_reference(state, *lists, match_threshold, max_age, birth_threshold, motion, velocity_gain)
+    scores, labels, boxes = scores.contiguous(), labels.contiguous(), boxes.contiguous()
+    track_id = torch.empty(N, dtype=torch.int32, device=scores.device)
+    track_hits = torch.empty(N, dtype=torch.int32, device=scores.device)
+    rc = _L().nos_track_update_f32(count.data_ptr(), scores.data_ptr(), labels.data_ptr(), boxes.data_ptr(), N,
+                                   *(t.data_ptr() for t in state.tensors()), T, float(match_threshold), int(max_age),
+                                   float(birth_threshold), MOTIONS[motion], float(velocity_gain), track_id.data_ptr(),
+                                   track_hits.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    _check(rc, "track_update")
+    return track_id, track_hits
