@@ -15,6 +15,8 @@
 //    [B][3][H][W] as well. So every layout is bit-equal to the RGB kernel on the converted frame.
 //  * Detections (image_detect.h): detections_f32 and merge_detections_f32.
 //  * Tracking (image_track.h): track_update_f32, the detections of successive frames associated in device state.
+//  * Drawing (image_overlay.h): overlay_k, the detections painted into the frame's own planes — the one kernel here
+//    that writes a surface.
 //  * Entries. The extern "C" functions at the end check every argument of an outside caller, fill the kernel's
 //    arguments and launch; the arguments all image entries share travel as one struct (Common).
 #include <hip/hip_runtime.h>
@@ -28,6 +30,7 @@
 #include "image_detect.h"
 #include "image_track.h"
 #include "image_stage.h"
+#include "image_overlay.h"
 #include "image_yuv.h"
 
 namespace {
@@ -412,17 +415,8 @@ int patch_planes_semiplanar(const PlaneArg& y, const PlaneArg& uv, const int* ta
   return launch(image_patch_planes_k<Src::NV12, Nv12Args>, grid, c.stream, "image_patch_planes_nv12", k, n);
 }
 
-// What the entries of the general YUV front end check and fill: every check of the descriptor and of the common
-// arguments, then the kernel's arguments k and n and the workgroups to launch. sB x sh x sw: the batch and the size
-// of the source the descriptor's planes hold — B x h x w itself, or the one frame that B tiles of h x w are cut from.
-int yuv_args(const NosYuvSrc* src, ImgArgs& k, int& grid, YuvBilinearArgs& n, const Common& c, int sB, int sh, int sw) {
-  if (!src) return fail("image_patch_planes: null operand");
-  if (src->size != int(sizeof(NosYuvSrc)))
-    return fail("image_patch_planes_yuv: descriptor size mismatch (NosYuvSrc of another build)");
-  const NosYuvSrc& s = *src;
-  if (const int rc = image_args(k, grid, c)) return rc;
-  if (c.max_fw > GROUP_FMAX_W) return fail("image_patch_planes_yuv: a patch's source footprint exceeds 69 columns");
-  // the known combinations
+// The known combinations of a descriptor's layout, subsampling, sample format and order.
+int yuv_format(const NosYuvSrc& s) {
   const bool packed = s.layout == YUV_PACKED;
   if (s.layout != YUV_PLANAR && s.layout != YUV_SEMI && !packed)
     return fail("image_patch_planes_yuv: unknown layout (0 planar, 1 semi-planar, 2 packed 4:2:2)");
@@ -437,15 +431,16 @@ int yuv_args(const NosYuvSrc* src, ImgArgs& k, int& grid, YuvBilinearArgs& n, co
                 "shift 0 or 16 - depth)");
   if (s.order < 0 || s.order > (packed ? 2 : s.layout == YUV_SEMI ? 1 : 0))
     return fail("image_patch_planes_yuv: unknown order (semi-planar 0 UV / 1 VU; packed 0 YUYV / 1 UYVY / 2 YVYU)");
-  if (s.chroma != 0 && s.chroma != 1)
-    return fail("image_patch_planes_yuv: unknown chroma reconstruction (0 nearest, 1 bilinear)");
-  if (s.siting < 0 || s.siting > 3)
-    return fail("image_patch_planes_yuv: unknown chroma siting (bit 0 horizontally, bit 1 vertically co-sited)");
-  if (s.chroma == 1 && s.hsub == 0)
-    return fail("image_patch_planes_yuv: bilinear chroma takes a subsampled source (4:4:4 is launched as nearest)");
+  return 0;
+}
+
+// The planes of a descriptor whose format is known, holding sB frames of sh x sw, as pl[0..2]: every plane's first
+// and last sample inside its storage [lo, hi). cw x ch: the size of a chroma plane in samples.
+int yuv_planes(const NosYuvSrc& s, int sB, int sh, int sw, PlaneArg* pl, long long& cw, long long& ch) {
+  const bool packed = s.layout == YUV_PACKED;
   // rows and row bytes of every plane
-  const long long SB = s.sample_bytes, cw = (sw + (1LL << s.hsub) - 1) >> s.hsub,
-                  ch = (sh + (1LL << s.vsub) - 1) >> s.vsub;
+  const long long SB = s.sample_bytes;
+  cw = (sw + (1LL << s.hsub) - 1) >> s.hsub, ch = (sh + (1LL << s.vsub) - 1) >> s.vsub;
   const int np = packed ? 1 : s.layout == YUV_SEMI ? 2 : 3;
   const long long rows[3] = {sh, ch, ch};
   const long long rowbytes[3] = {packed ? 4 * ((sw + 1LL) / 2) : sw * SB, s.layout == YUV_SEMI ? 2 * cw * SB : cw * SB,
@@ -459,8 +454,30 @@ int yuv_args(const NosYuvSrc* src, ImgArgs& k, int& grid, YuvBilinearArgs& n, co
       return fail("image_patch_planes_yuv: 16-bit planes lie at an even address with an even pitch and batch stride");
     if (!inside(sB, q, rows[i], rowbytes[i]))
       return fail("image_patch_planes_yuv: a plane does not lie inside its storage bounds");
-    n.pl[i] = q;
+    pl[i] = q;
   }
+  return 0;
+}
+
+// What the entries of the general YUV front end check and fill: every check of the descriptor and of the common
+// arguments, then the kernel's arguments k and n and the workgroups to launch. sB x sh x sw: the batch and the size
+// of the source the descriptor's planes hold — B x h x w itself, or the one frame that B tiles of h x w are cut from.
+int yuv_args(const NosYuvSrc* src, ImgArgs& k, int& grid, YuvBilinearArgs& n, const Common& c, int sB, int sh, int sw) {
+  if (!src) return fail("image_patch_planes: null operand");
+  if (src->size != int(sizeof(NosYuvSrc)))
+    return fail("image_patch_planes_yuv: descriptor size mismatch (NosYuvSrc of another build)");
+  const NosYuvSrc& s = *src;
+  if (const int rc = image_args(k, grid, c)) return rc;
+  if (c.max_fw > GROUP_FMAX_W) return fail("image_patch_planes_yuv: a patch's source footprint exceeds 69 columns");
+  if (const int rc = yuv_format(s)) return rc;
+  if (s.chroma != 0 && s.chroma != 1)
+    return fail("image_patch_planes_yuv: unknown chroma reconstruction (0 nearest, 1 bilinear)");
+  if (s.siting < 0 || s.siting > 3)
+    return fail("image_patch_planes_yuv: unknown chroma siting (bit 0 horizontally, bit 1 vertically co-sited)");
+  if (s.chroma == 1 && s.hsub == 0)
+    return fail("image_patch_planes_yuv: bilinear chroma takes a subsampled source (4:4:4 is launched as nearest)");
+  long long cw = 0, ch = 0;
+  if (const int rc = yuv_planes(s, sB, sh, sw, n.pl, cw, ch)) return rc;
   if (!table_ok(s.tab, s.depth))
     return fail("image_patch_planes_yuv: colour table: coefficients below 2^23 in size, offsets below 2^depth");
   for (int i = 0; i < 12; ++i) n.tab[i] = s.tab[i];
@@ -505,6 +522,29 @@ int yuv_launch(const NosYuvSrc& s, bool hdr, const ImgArgs& k, const YuvHdrArgs&
   if (hdr) return yuv_launch_as<YuvHdrArgs>(s, k, n, f, grid, stream, what);
   if (s.chroma == 1) return yuv_launch_as<YuvBilinearArgs>(s, k, n, f, grid, stream, what);
   return yuv_launch_as<YuvArgs>(s, k, n, f, grid, stream, what);
+}
+// What both overlay entries check of the lists, the tables and the parameters, and fill of k.
+int overlay_args(OverlayArgs& k, int h, int w, const int* count, const float* scores, const int* labels,
+                 const float* boxes, const int* track_id, const int* track_hits, int N, const void* modes, int L,
+                 const int* codes, int K, const int* font, int thickness, int scale, int min_hits) {
+  if (!count || !scores || !labels || !boxes || !modes || !codes || !font) return fail("overlay: null operand");
+  if ((track_id == nullptr) != (track_hits == nullptr)) return fail("overlay: track_id and track_hits go together");
+  if (h <= 0 || w <= 0 || h > (1 << 15) || w > (1 << 15)) return fail("overlay: a frame of 1..32768 rows and columns");
+  if (N <= 0 || N > OMAX) return fail("overlay: 0 < rows <= 1024");
+  if (L <= 0 || K <= 0 || K > OVERLAY_MAX_K) return fail("overlay: labels > 0, 0 < colours <= 1024");
+  if (thickness < 1 || thickness > OVERLAY_MAX_T || scale < 0 || scale > OVERLAY_MAX_S || min_hits < 1)
+    return fail("overlay: 1 <= thickness <= 2^20, 0 <= scale <= 1024, min_hits >= 1");
+  k = OverlayArgs{count, scores, labels, boxes, track_id, track_hits, static_cast<const uint8_t*>(modes), codes, font,
+                  N, L, K, thickness, scale, min_hits, h, w};
+  return 0;
+}
+
+// overlay_k on one workgroup per tile of the h x w frame
+template <class Dst>
+int overlay_launch(const OverlayArgs& k, const Dst& dst, void* stream, const char* what) {
+  const int grid = ((k.h + OTH - 1) / OTH) * ((k.w + OTW - 1) / OTW);
+  hipLaunchKernelGGL(overlay_k<Dst>, dim3(grid), dim3(OT), 0, reinterpret_cast<hipStream_t>(stream), k, dst);
+  return check(what);
 }
 }  // namespace
 
@@ -790,6 +830,58 @@ int nos_track_update_f32(const int* count, const float* scores, const int* label
                      labels, boxes, N, t_boxes, t_vel, t_labels, t_ids, t_hits, t_misses, next_id, dropped, T,
                      match_threshold, max_age, birth_threshold, motion, velocity_gain, track_id, track_hits);
   return check("track_update_f32");
+}
+
+int nos_overlay_tile_rows() { return OTH; }
+int nos_overlay_tile_columns() { return OTW; }
+
+// One frame's detections painted into packed pixels img [h][w][C] (order, pitch and [lo, hi) as in
+// nos_image_patch_planes_packed; the fourth byte of a pixel is never written): count [1] int32, scores [N] fp32, labels
+// [N] int32, boxes [N][4] fp32 as the entries above write them, track_id / track_hits [N] int32 as nos_track_update_f32
+// does or both null; modes [L] uint8, codes [2 K + 1][3] int32 and font [10][7] int32 are device tables
+// (image_overlay.h). Nothing is launched unless every check passes, the first and last byte of the image inside
+// [lo, hi) among them; the kernel stores nothing outside pixels (y, x) with y < h and x < w.
+int nos_overlay_packed(void* img, const void* lo, const void* hi, long long pitch, const char* order, int h, int w,
+                       const int* count, const float* scores, const int* labels, const float* boxes,
+                       const int* track_id, const int* track_hits, int N, const void* modes, int L, const int* codes,
+                       int K, const int* font, int thickness, int scale, int min_hits, void* stream) {
+  if (!img || !order) return fail("overlay: null operand");
+  PackedArgs o{};
+  const int C = packed_order(order, o);
+  if (!C) return fail("overlay_packed: unknown channel order (rgb, bgr, rgba or bgra)");
+  OverlayArgs k{};
+  if (const int rc = overlay_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, modes, L, codes, K,
+                                  font, thickness, scale, min_hits))
+    return rc;
+  const PackedDst dst{plane_arg(img, lo, hi, pitch, 0), C, o.r};
+  if (pitch < (long long)w * C) return fail("overlay_packed: the row pitch is smaller than a row's bytes");
+  if (!stride_range(dst.s)) return fail("overlay_packed: pitch out of range");
+  if (!inside(1, dst.s, h, (long long)w * C)) return fail("overlay_packed: the image does not lie inside its storage bounds");
+  return overlay_launch(k, dst, stream, "overlay_packed");
+}
+
+// The same into the one h x w frame of any YUV surface NosYuvSrc describes (tab, chroma and siting are not read): the
+// luma sample of every painted pixel, and a chroma sample where its top-left luma pixel is painted; 16-bit samples as
+// whole words, code << shift. codes holds Y, U, V codes of the surface's depth. Every check of the descriptor that
+// nos_image_patch_planes_yuv makes of its planes, the first and last sample of each inside its [lo, hi).
+int nos_overlay_yuv(const NosYuvSrc* dst, int h, int w, const int* count, const float* scores, const int* labels,
+                    const float* boxes, const int* track_id, const int* track_hits, int N, const void* modes, int L,
+                    const int* codes, int K, const int* font, int thickness, int scale, int min_hits, void* stream) {
+  if (!dst) return fail("overlay: null operand");
+  if (dst->size != int(sizeof(NosYuvSrc))) return fail("overlay_yuv: descriptor size mismatch (NosYuvSrc of another build)");
+  OverlayArgs k{};
+  if (const int rc = overlay_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, modes, L, codes, K,
+                                  font, thickness, scale, min_hits))
+    return rc;
+  YuvDst d{};
+  long long cw = 0, ch = 0;
+  if (yuv_format(*dst) || yuv_planes(*dst, 1, h, w, d.pl, cw, ch)) {
+    g_err = "overlay_yuv: the surface: " + g_err;
+    return -1;
+  }
+  d.layout = dst->layout, d.hsub = dst->hsub, d.vsub = dst->vsub, d.sb = dst->sample_bytes, d.shift = dst->shift;
+  d.order = dst->order;
+  return overlay_launch(k, d, stream, "overlay_yuv");
 }
 
 }  // extern "C"

@@ -41,6 +41,13 @@ constructed scene in which about half the rows continue a track, a quarter start
 number of tracks die. The state is restored from a saved copy inside the timed graph, so every replay does the same
 work; ``*_restore_us`` is that copy alone, which both sides include. On the whole GPU ``track_image_ms`` stands beside
 ``detect_image_ms`` and ``track_tiled_ms`` beside ``detect_tiled_ms`` (the same calls with the tracker's launch).
+
+Five rows time the overlay (``--rows overlay`` runs them alone): ``overlay_n100_1080p_nv12_*``, ``overlay_n400_2160p_nv12_*``,
+``_rgb_*``, ``_p010_*`` and ``_nv12_redact_*`` (a quarter of the rows filled), ``ops.image.overlay`` of ``n`` rows with ids on
+a lattice against ``overlay_reference``, the frame restored from a saved copy inside the timed graph on both sides
+(``*_restore_us`` is that copy alone). ``*_scene`` gives the painted samples, their bytes, and those bytes over the
+kernel's time (hip minus restore). On the whole GPU ``overlay_annotate_image_thr0_ms`` stands beside
+``overlay_track_image_thr0_ms`` and ``overlay_annotate_tiled_thr0_ms`` beside ``overlay_track_tiled_thr0_ms``.
 """
 from __future__ import annotations
 
@@ -62,11 +69,11 @@ from walkai_nos_amd.ops.probe import Stream  # noqa: E402
 T, H, HD, D, FF = 3401, 6, 64, 384, 1536
 
 
-def timeit(fn, stream, iters):
+def timeit(fn, stream, iters, warm=3):
     """GPU time per call: ``iters`` calls captured in one HIP graph on the slice's stream and
     replayed, so host-side launch overhead (ctypes, allocation) is not measured."""
     with torch.cuda.stream(stream):
-        for _ in range(3):
+        for _ in range(warm):
             fn()
         stream.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -89,8 +96,8 @@ def main() -> int:
     ap.add_argument("--out", default="gpurun_out/kbench.json")
     ap.add_argument("--only", choices=("all", "attn", "gemm", "model", "modes", "image"), default="all")
     ap.add_argument("--slices", default="spx,dpx,qpx,cpx")
-    ap.add_argument("--rows", choices=("all", "tiles", "track"), default="all",
-                    help="image: every row, or the tiled-detection rows alone, or the tracker's")
+    ap.add_argument("--rows", choices=("all", "tiles", "track", "overlay"), default="all",
+                    help="image: every row, or the tiled-detection rows alone, or the tracker's, or the overlay's")
     ap.add_argument("--partitions", type=int, default=0, help="modes: run only this many partitions of each mode")
     ap.add_argument("--free-s", type=float, default=0.0,
                     help="modes: serve free-running (one thread per pod, as the bench) for this many seconds "
@@ -361,10 +368,12 @@ def image_bench(a) -> int:
                            lambda: I.image_patch_planes(conv, out, 16, IMAGENET_MEAN, IMAGENET_STD),
                            lambda: I.image_patch_planes(fr.rgb(), out, 16, IMAGENET_MEAN, IMAGENET_STD),
                            s, a.iters)
-            if a.rows != "track":
+            if a.rows in ("all", "tiles"):
                 tiles_rows(r, pair, s, a.iters, rounds, whole_gpu=cus is None)
-            if a.rows != "tiles":
+            if a.rows in ("all", "track"):
                 track_rows(r, s, a.iters, rounds, whole_gpu=cus is None)
+            if a.rows in ("all", "overlay"):
+                overlay_rows(r, s, a.iters, rounds, whole_gpu=cus is None)
             if not full:
                 print(json.dumps(r), flush=True)
                 results.append(r)
@@ -558,6 +567,112 @@ def track_rows(r, s, iters, rounds, whole_gpu):
         r[f"{k}_thr0_ms"] = round(statistics.median(vs) / 1000.0, 3)
     r["track_model_rounds_ms"] = {k: [round(v / 1000.0, 3) for v in vs] for k, vs in t.items()}
     r["track_model_live"] = {"track_image": len(tr_i.tracks()), "track_tiled": len(tr_t.tracks())}
+
+
+def overlay_scene(n: int, h: int, w: int, redact: bool = False):
+    """``n`` rows with ids on a lattice over an ``h x w`` frame, as ``track_scene`` lays its tracks out: a box of 55 to
+    80 % of its cell, labels 0..7; with ``redact`` the rows of labels 0 and 1 (a quarter) are filled."""
+    g = torch.Generator().manual_seed(n + h)
+    cols = int((n * w / h) ** 0.5) + 1
+    rows = -(-n // cols)
+    cw, ch = w / cols, h / rows
+    k = torch.arange(n)
+    x0, y0 = (k % cols) * cw + 0.1 * cw, (k // cols) * ch + 0.15 * ch
+    size = 0.55 + 0.25 * torch.rand(n, 2, generator=g)
+    boxes = torch.stack((x0, y0, x0 + size[:, 0] * cw, y0 + size[:, 1] * ch), dim=1).float()
+    i32 = torch.int32
+    lists = (torch.tensor([n], dtype=i32), 0.5 + 0.5 * torch.rand(n, generator=g), (k % 8).to(i32), boxes,
+             (7 * k + 1).to(i32), torch.full((n,), 3, dtype=i32))
+    modes = torch.tensor([2 if redact and label < 2 else 1 for label in range(8)], dtype=torch.uint8)
+    return lists, modes
+
+
+def overlay_rows(r, s, iters, rounds, whole_gpu):
+    """The overlay (see the module docstring): ``overlay_*_hip_us`` against ``*_torch_us``, both with the restore of
+    the frame from a saved copy that ``*_restore_us`` times alone; ``*_scene`` says what was painted."""
+    import statistics
+
+    from walkai_nos_amd.models.workload import surfaces
+    from walkai_nos_amd.models.workload.overlay import Overlay
+    from walkai_nos_amd.models.workload.processor import Nv12
+    from walkai_nos_amd.models.workload.tracker import Tracker
+    from walkai_nos_amd.models.workload.yolos import YolosSmall
+    from walkai_nos_amd.ops import image as I
+    g = torch.Generator().manual_seed(3)
+    for name, n, h, w, fmt, redact in (("n100_1080p_nv12", 100, 1080, 1920, "nv12", False),
+                                       ("n400_2160p_nv12", 400, 2160, 3840, "nv12", False),
+                                       ("n400_2160p_rgb", 400, 2160, 3840, "rgb", False),
+                                       ("n400_2160p_p010", 400, 2160, 3840, "p010", False),
+                                       ("n400_2160p_nv12_redact", 400, 2160, 3840, "nv12", True)):
+        if fmt == "rgb":
+            buf = torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8).cuda()
+            frame = buf
+        else:
+            pitch = -(-w * (2 if fmt == "p010" else 1) // 256) * 256
+            buf = torch.randint(0, 256, (pitch * h * 3 // 2,), generator=g, dtype=torch.uint8).cuda()
+            frame = Nv12.from_buffer(buf, h, w, pitch) if fmt == "nv12" else surfaces.from_buffer(fmt, buf, h, w, pitch)
+        saved = buf.clone()
+        lists, modes = overlay_scene(n, h, w, redact)
+        lists, modes = [t.cuda() for t in lists], modes.cuda()
+        thickness, scale = Overlay().sizes(h, w)
+        codes = I.overlay_codes(I.overlay_palette(), (0, 0, 0), frame)
+        kw = dict(thickness=thickness, scale=scale, modes=modes, min_hits=1, codes=codes)
+
+        def restore():
+            buf.copy_(saved)
+
+        def hip():
+            restore()
+            return I.overlay(frame, *lists, **kw)
+
+        def composed():
+            restore()
+            return I.overlay_reference(frame, *lists, **kw)
+        with torch.cuda.stream(s):
+            hip()
+            a = buf.clone()
+            composed()
+            same = torch.equal(a, buf)
+            surf = I.overlay_surface(frame)
+            slot = I.overlay_slots(h, w, *lists, thickness, scale, modes, 1, 16)
+            sb = 1 if fmt != "p010" else 2
+            samples = sum(int((slot[::1 << vs, ::1 << hs] >= 0).sum()) for _, _, hs, vs in surf.samples)
+            s.synchronize()
+        t = {"hip": [], "torch": [], "restore": []}
+        for _ in range(rounds):
+            t["hip"].append(timeit(hip, s, iters))
+            t["torch"].append(timeit(composed, s, 1, warm=1))       # n steps of many launches: one call per graph
+            t["restore"].append(timeit(restore, s, iters))
+        for k, vs in t.items():
+            r[f"overlay_{name}_{k}_us"] = round(statistics.median(vs), 1)
+        r[f"overlay_{name}_rounds_us"] = {k: [round(v, 1) for v in vs] for k, vs in t.items()}
+        print(f"[kbench] overlay_{name}: hip {t['hip']} torch {t['torch']} us", file=sys.stderr, flush=True)
+        kernel_us = max(statistics.median(t["hip"]) - statistics.median(t["restore"]), 1e-3)
+        r[f"overlay_{name}_scene"] = {"rows": n, "frame": [h, w], "thickness": thickness, "scale": scale,
+                                      "painted_samples": samples, "painted_bytes": samples * sb,
+                                      "frame_bytes": int(buf.numel()), "hip_equals_torch": bool(same),
+                                      "painted_bytes_per_kernel_us": round(samples * sb / kernel_us, 1)}
+    if not whole_gpu:
+        return
+    small = torch.randint(0, 256, (480, 640, 3), generator=g, dtype=torch.uint8).cuda()
+    large = torch.randint(0, 256, (2160, 3840, 3), generator=g, dtype=torch.uint8).cuda()
+    small_out, large_out = torch.empty_like(small), torch.empty_like(large)
+    with torch.cuda.stream(s), torch.no_grad():
+        m = YolosSmall().cuda().eval()
+        tr = [Tracker(capacity=c, device="cuda") for c in (256, 256, 1024, 1024)]
+        ov = Overlay()
+        it = max(2, iters // 5)
+        t = {"track_image": [], "annotate_image": [], "track_tiled": [], "annotate_tiled": []}
+        for _ in range(rounds):
+            t["track_image"].append(timeit(lambda: m.track_image(small, tr[0], 0.0), s, it))
+            t["annotate_image"].append(timeit(lambda: m.annotate_image(small, ov, 0.0, tr[1], small_out), s, it))
+            t["track_tiled"].append(timeit(lambda: m.track_tiled(large, tr[2], (2, 2), 0.2, 0.0), s, it))
+            t["annotate_tiled"].append(timeit(lambda: m.annotate_tiled(large, ov, (2, 2), 0.2, 0.0, tracker=tr[3],
+                                                                       target=large_out), s, it))
+        s.synchronize()
+    for k, vs in t.items():
+        r[f"overlay_{k}_thr0_ms"] = round(statistics.median(vs) / 1000.0, 3)
+    r["overlay_model_rounds_ms"] = {k: [round(v / 1000.0, 3) for v in vs] for k, vs in t.items()}
 
 
 def free_running(slots, seconds: float) -> int:

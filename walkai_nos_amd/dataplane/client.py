@@ -34,6 +34,13 @@ launch inside the captured graph, whose replays advance the tracker; ``--track-i
 ``--track-min-hits``, ``--track-capacity``, ``--track-motion``). The tracker is reset after the warm-ups and again after
 the capture, so the timed loop starts at frame 0; the JSON line then carries a ``"track"`` block: the live tracks (and
 those of them seen in ``--track-min-hits`` frames), the ids issued, the births dropped for lack of a slot, the frames.
+``--annotate`` draws the detections into the frame (``YolosSmall.annotate_image`` / ``annotate_tiled``, one more launch
+inside the captured graph; with ``--track`` the tags are the ids): boxes ``--annotate-thickness`` thick, tags of glyph
+dots ``--annotate-scale`` pixels large or none with ``--no-tags``, the labels of ``--redact L1,L2,...`` filled instead.
+The client builds a second surface of the same layout over a second buffer; inside the graph the source buffer is
+copied there and painted there, so the synthetic frame stays the same from replay to replay. The JSON line then carries
+``"annotate": {"changed_bytes": ...}``, the bytes of the second buffer that differ from the source, counted once on the
+host after the loop. It is refused with ``--transfer pq|hlg``: an SDR colour has no code on such a surface.
 """
 from __future__ import annotations
 
@@ -125,7 +132,32 @@ def main(argv=None) -> int:
     ap.add_argument("--track-capacity", type=int, default=256, help="--track: slots of the tracker (1..1024 run in HIP)")
     ap.add_argument("--track-motion", choices=("constant", "none"), default="constant",
                     help="--track: compare a track one frame along its velocity, or where it was")
+    ap.add_argument("--annotate", action="store_true",
+                    help="--end-to-end: draw the detections into a copy of the frame (an overlay launch in the graph)")
+    ap.add_argument("--annotate-thickness", type=int, default=None, help="--annotate: a box outline's pixels (default: twice the scale)")
+    ap.add_argument("--annotate-scale", type=int, default=None,
+                    help="--annotate: the pixels of a glyph's dot (default: the frame's shorter side / 360, at least 1)")
+    ap.add_argument("--redact", default="", help="--annotate: L1,L2,... labels that are filled, not outlined")
+    ap.add_argument("--no-tags", action="store_true", help="--annotate: boxes without id tags")
     args = ap.parse_args(argv)
+    redact = ()
+    if args.annotate:
+        if not args.end_to_end:
+            ap.error("--annotate takes --end-to-end")
+        if args.transfer != "sdr":
+            ap.error(f"--annotate draws SDR colours: it is not offered with --transfer {args.transfer}")
+        if args.annotate_thickness is not None and args.annotate_thickness < 1:
+            ap.error(f"--annotate-thickness {args.annotate_thickness} is not a number of pixels from 1 up")
+        if args.annotate_scale is not None and args.annotate_scale < 1:
+            ap.error(f"--annotate-scale {args.annotate_scale} is not a number of pixels from 1 up (--no-tags draws none)")
+        try:
+            redact = tuple(int(v) for v in args.redact.split(",")) if args.redact else ()
+        except ValueError:
+            redact = (-1,)
+        if any(not 0 <= v < 91 for v in redact):
+            ap.error(f"--redact {args.redact!r} is not L1,L2,... with labels in 0..90")
+    elif args.annotate_thickness is not None or args.annotate_scale is not None or args.redact or args.no_tags:
+        ap.error("--annotate-thickness, --annotate-scale, --redact and --no-tags take --annotate")
     if args.track:
         if not args.end_to_end:
             ap.error("--track takes --end-to-end")
@@ -179,27 +211,35 @@ def main(argv=None) -> int:
                 ap.error(f"--pitch {pitch} is smaller than a row of {iw} {fmt} pixels ({row} bytes)")
             # luma rows, then at most twice as many bytes of chroma (4:4:4)
             buf = torch.randint(0, 256, (3 * pitch * ih,), generator=gen, dtype=torch.uint8).to(dev)
-            img = surfaces.from_buffer(fmt, buf, ih, iw, pitch, matrix=args.matrix, full_range=args.full_range,
-                                       transfer=args.transfer, peak_nits=args.peak_nits)
+
+            def surface(b):
+                return surfaces.from_buffer(fmt, b, ih, iw, pitch, matrix=args.matrix, full_range=args.full_range,
+                                            transfer=args.transfer, peak_nits=args.peak_nits)
         elif fmt in ("nv12", "nv21", "i420", "yv12"):
             if args.matrix == "bt2020":
                 ap.error(f"--matrix bt2020 is not offered for {fmt}")
             pitch = args.pitch or -(-iw // 256) * 256
             buf = torch.randint(0, 256, (pitch * (ih + ih // 2),), generator=gen, dtype=torch.uint8).to(dev)
-            if fmt in ("nv12", "nv21"):
-                img = Nv12.from_buffer(buf, ih, iw, pitch, args.matrix, args.full_range, vu=fmt == "nv21")
-            else:
-                img = Yuv420p.from_buffer(buf, ih, iw, pitch, order=fmt, matrix=args.matrix,
-                                          full_range=args.full_range)
+
+            def surface(b):
+                if fmt in ("nv12", "nv21"):
+                    return Nv12.from_buffer(b, ih, iw, pitch, args.matrix, args.full_range, vu=fmt == "nv21")
+                return Yuv420p.from_buffer(b, ih, iw, pitch, order=fmt, matrix=args.matrix, full_range=args.full_range)
         elif fmt == "rgb" and not args.pitch:
-            img = torch.randint(0, 256, (ih, iw, 3), generator=gen, dtype=torch.uint8).to(dev)
+            buf = torch.randint(0, 256, (ih, iw, 3), generator=gen, dtype=torch.uint8).to(dev)
+
+            def surface(b):
+                return b
         else:
             C = len(fmt)
             pitch = args.pitch or iw * C
             if pitch < iw * C:
                 ap.error(f"--pitch {pitch} is smaller than a row of {iw} {fmt} pixels")
             buf = torch.randint(0, 256, (ih * pitch,), generator=gen, dtype=torch.uint8).to(dev)
-            img = Packed(buf.as_strided((ih, iw, C), (pitch, C, 1)), fmt)
+
+            def surface(b):
+                return Packed(b.as_strided((ih, iw, C), (pitch, C, 1)), fmt)
+        img = surface(buf)      # the frame over its buffer, in place
         hw = model.processor.size((ih, iw))
         if tiles is not None:
             th, tw, origins = model.processor.tile_plan((ih, iw), tiles, args.tile_overlap, model.c.num_detection_tokens)
@@ -208,8 +248,22 @@ def main(argv=None) -> int:
             from ..models.workload.tracker import Tracker
             tracker = Tracker(args.track_capacity, args.track_iou, args.track_max_age, motion=args.track_motion,
                               min_hits=args.track_min_hits, device=dev)
+        overlay = painted = None
+        if args.annotate:
+            from ..models.workload.overlay import Overlay
+            overlay = Overlay(thickness=args.annotate_thickness, scale=args.annotate_scale, tags=not args.no_tags,
+                              redact=redact, min_hits=args.track_min_hits if args.track else 1,
+                              num_labels=model.c.num_labels)
+            painted = torch.empty_like(buf)     # a second surface of the same layout over a second buffer
+            target = surface(painted)
 
         def infer():
+            if overlay is not None:
+                painted.copy_(buf)
+                if tiles is not None:
+                    return model.annotate_tiled(img, overlay, tiles, args.tile_overlap, args.threshold, args.match,
+                                                args.match_threshold, tracker, target)
+                return model.annotate_image(img, overlay, args.threshold, tracker, target)
             if tracker is not None:
                 if tiles is not None:
                     return model.track_tiled(img, tracker, tiles, args.tile_overlap, args.threshold, args.match,
@@ -299,6 +353,8 @@ def main(argv=None) -> int:
                             "ids_issued": int(tracker.state.next_id.item()) - 1,
                             "dropped": int(tracker.state.dropped.item()), "frames": len(lat),
                             "capacity": tracker.capacity, "motion": args.track_motion}
+        if overlay is not None:
+            out["annotate"] = {"changed_bytes": int((painted != buf).sum().item())}
     if census is not None:
         out["census"] = census
     out["hbm"] = _shim()

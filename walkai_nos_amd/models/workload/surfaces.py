@@ -35,6 +35,10 @@ inside the one launch. The default, ``"sdr"``, reads the codes as they are.
 Not offered: the bottom sitings; bicubic or Lanczos chroma; luminance-based or BT.2390 tone mapping; dynamic metadata
 (HDR10+, Dolby Vision); 8-bit HLG; linear or float surfaces; 16-bit-deep samples; Y210 / Y410 / AYUV; big-endian
 samples; BT.2020 constant luminance; batches above one on the fused model path and mixed sizes in one call.
+
+Every SDR frame here is also a target of ``ops.image.overlay`` (``models/workload/overlay.py``), which paints detections
+into its planes in place. Not offered there: alpha blending; antialiased lines; class names or any glyph but digits; PQ
+/ HLG surfaces (an SDR colour has no code without the inverse tone map); batches above one; more than 1024 rows.
 """
 from __future__ import annotations
 

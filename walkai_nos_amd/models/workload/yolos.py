@@ -485,6 +485,28 @@ class YolosSmall(nn.Module):
         cross-tile merge's; the tracker's own are set on the tracker.)"""
         return tracker.update(self.detect_tiled(image_u8, tiles, overlap, threshold, match, match_threshold))
 
+    def annotate_image(self, frame, overlay, threshold: float = 0.5, tracker=None, target=None) -> Dict[str, object]:
+        """:meth:`detect_image` — :meth:`track_image` with a ``tracker`` — and ``overlay.draw`` (``overlay.Overlay``)
+        into ``target``: the same dict with ``"frame"``, the painted target, added. One more launch and no host
+        synchronisation: frame in, annotated (or redacted) frame out is still one capturable graph. ``target`` is a
+        surface of the frame's size (the boxes are in the frame's pixels) and defaults to ``frame`` itself, painted in
+        place: a decoder writes the next frame over it before the next replay. With ``target=None`` a replay on an
+        unchanged buffer therefore detects on the annotated frame, not on the one that was put there."""
+        det = self.detect_image(frame, threshold) if tracker is None else self.track_image(frame, tracker, threshold)
+        return {**det, "frame": overlay.draw(det, frame if target is None else target)}
+
+    def annotate_tiled(self, frame, overlay, tiles: Tuple[int, int] = (2, 2), overlap: float = 0.2,
+                       threshold: float = 0.5, match: str = "ios", match_threshold: float = 0.5, tracker=None,
+                       target=None) -> Dict[str, object]:
+        """:meth:`detect_tiled` — :meth:`track_tiled` with a ``tracker`` — and ``overlay.draw`` of the merged list into
+        ``target``, as :meth:`annotate_image`: with ``target=None`` the frame itself is painted, and a replay on an
+        unchanged buffer detects on the annotated frame."""
+        if tracker is None:
+            det = self.detect_tiled(frame, tiles, overlap, threshold, match, match_threshold)
+        else:
+            det = self.track_tiled(frame, tracker, tiles, overlap, threshold, match, match_threshold)
+        return {**det, "frame": overlay.draw(det, frame if target is None else target)}
+
     def _target_sizes(self, img: torch.Tensor) -> torch.Tensor:
         """``[B, 2]`` fp32 (height, width) of the original images on their device, cached: a captured
         graph must not copy from the host."""

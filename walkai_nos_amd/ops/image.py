@@ -68,6 +68,12 @@ which is also what runs on the CPU, with the ``torch`` backend and past a layout
   (:class:`TrackState`) lives in device buffers updated in place, so each replay of a captured graph is the next frame;
   the ids come back in the row order of the lists passed in. Kalman filtering, appearance features, Hungarian
   assignment, a second pass on low scores and more than 1024 tracks are not offered.
+* :func:`overlay` / :func:`overlay_codes` / :func:`overlay_palette` — the write side: one frame's detections (and ids)
+  painted into the frame's own planes by one launch, on every SDR layout the front end reads — outlines, id tags in
+  5 x 7 digits (:data:`OVERLAY_FONT`) and redactions, in exact integers, colours turned into the surface's codes once
+  on the host in fp64. No RGB frame, no host sync, no copy; :func:`overlay_reference` is the torch composition. Alpha
+  blending, antialiased lines, class names or any glyph but digits, PQ / HLG surfaces, batches above one and more than
+  1024 rows are not offered.
 """
 from __future__ import annotations
 
@@ -135,7 +141,13 @@ def _L() -> ctypes.CDLL:
             L.nos_merge_detections_f32.argtypes = [vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, i32, vp, vp, vp, vp,
                                                    vp, vp]
             L.nos_track_update_f32.argtypes = [vp] * 4 + [i32] + [vp] * 8 + [i32, f32, i32, f32, i32, f32, vp, vp, vp]
+            # the lists, the tables and the parameters both overlay entries take behind their surface
+            drawn = [vp] * 6 + [i32, vp, i32, vp, i32, vp, i32, i32, i32, vp]
+            L.nos_overlay_packed.argtypes = [vp, vp, vp, i64, ctypes.c_char_p, i32, i32] + drawn
+            L.nos_overlay_yuv.argtypes = [src, i32, i32] + drawn
             L.nos_image_last_error.restype = ctypes.c_char_p
+            if (L.nos_overlay_tile_rows(), L.nos_overlay_tile_columns()) != OVERLAY_TILE:
+                raise NativeUnavailable(f"{LIB} was built with another overlay tile than ops/image.py expects")
             if (L.nos_image_taps(), L.nos_image_max_footprint(), L.nos_image_max_patch(),
                     L.nos_image_nv12_max_footprint(), L.nos_image_yuv420p_max_footprint(),
                     L.nos_image_packed_max_footprint(), L.nos_image_yuv_max_footprint()) != \
@@ -242,10 +254,11 @@ _tables = GraphCache(16)
 
 
 def invalidate_cache() -> None:
-    """Drop every cached tap table, tile-origin table and HDR table, also those a captured graph holds: capture such
+    """Drop every cached tap table, tile-origin table, HDR table and overlay table, also those a captured graph holds: capture such
     graphs again."""
     _tables.clear()
     _hdr_tables.clear()
+    _overlay_tables.clear()
 
 
 def _make_tables(h: int, w: int, H: int, W: int, p: int, device: torch.device) -> Optional[tuple]:
@@ -1660,3 +1673,349 @@ def track_update(state: TrackState, count: torch.Tensor, scores: torch.Tensor, l
                                    track_hits.data_ptr(), torch.cuda.current_stream().cuda_stream)
     _check(rc, "track_update")
     return track_id, track_hits
+
+
+# ---- detections drawn into the frame --------------------------------------------------------------------
+#: the ten digits, 5 x 7: a digit's seven rows, bit 4 the leftmost column (the kernel reads the same table)
+OVERLAY_FONT = (
+    (0b01110, 0b10001, 0b10011, 0b10101, 0b11001, 0b10001, 0b01110),
+    (0b00100, 0b01100, 0b00100, 0b00100, 0b00100, 0b00100, 0b01110),
+    (0b01110, 0b10001, 0b00001, 0b00010, 0b00100, 0b01000, 0b11111),
+    (0b11111, 0b00010, 0b00100, 0b00010, 0b00001, 0b10001, 0b01110),
+    (0b00010, 0b00110, 0b01010, 0b10010, 0b11111, 0b00010, 0b00010),
+    (0b11111, 0b10000, 0b11110, 0b00001, 0b00001, 0b10001, 0b01110),
+    (0b00110, 0b01000, 0b10000, 0b11110, 0b10001, 0b10001, 0b01110),
+    (0b11111, 0b00001, 0b00010, 0b00100, 0b01000, 0b01000, 0b01000),
+    (0b01110, 0b10001, 0b10001, 0b01110, 0b10001, 0b10001, 0b01110),
+    (0b01110, 0b10001, 0b10001, 0b01111, 0b00001, 0b00010, 0b01100),
+)
+#: the drawing modes of a label (``nos_overlay_*``'s ``modes`` table)
+OVERLAY_MODES = {"off": 0, "outline": 1, "redact": 2}
+#: the raster tile of the kernel (rows, columns of luma pixels per workgroup), and its limits (``csrc/image_overlay.h``)
+OVERLAY_TILE = (32, 64)
+OVERLAY_MAX_THICKNESS, OVERLAY_MAX_SCALE, OVERLAY_MAX_COLOURS = 1 << 20, 1 << 10, 1 << 10
+#: a coordinate is clamped to this size, in fp32, before it is floored
+OVERLAY_CLAMP = float(1 << 20)
+
+
+def overlay_palette(K: int = 16) -> np.ndarray:
+    """``[K, 2, 3]`` uint8 RGB: ``K`` fill colours — hues a golden-ratio step apart at full saturation, in fp64 —
+    each with the text colour that reads on it: black when the fill's BT.709 luma ``0.2126 R + 0.7152 G + 0.0722 B``
+    is 128 or more, else white."""
+    K = int(K)
+    if not 1 <= K <= OVERLAY_MAX_COLOURS:
+        raise ValueError(f"overlay_palette: {K!r} is not a number of colours in 1..{OVERLAY_MAX_COLOURS}")
+    out = np.zeros((K, 2, 3), dtype=np.uint8)
+    for k in range(K):
+        hue = 6.0 * ((k * 0.6180339887498949) % 1.0)
+        x = 1.0 - abs(hue % 2.0 - 1.0)
+        rgb = ((1.0, x, 0.0), (x, 1.0, 0.0), (0.0, 1.0, x), (0.0, x, 1.0), (x, 0.0, 1.0), (1.0, 0.0, x))[int(hue) % 6]
+        out[k, 0] = np.floor(255.0 * np.array(rgb) + 0.5)
+        out[k, 1] = 0 if float(np.dot((0.2126, 0.7152, 0.0722), out[k, 0].astype(np.float64))) >= 128.0 else 255
+    return out
+
+
+@dataclass
+class OverlaySurface:
+    """What :func:`overlay` knows of a target (:func:`overlay_surface`): the frame's size, ``packed = (data [1, h, w,
+    C], order)`` or ``yuv = (layout, planes, subsampling, depth, msb, order)`` as :func:`yuv_src` takes them, how a YUV
+    colour becomes codes (``colour = (matrix, full_range, depth)``, None for packed pixels), and ``samples``: every
+    written sample plane as ``(2-D strided view, colour component, hsub, vsub)``; ``shift`` moves a code into a
+    16-bit word's high bits."""
+    h: int
+    w: int
+    device: torch.device
+    packed: Optional[tuple]
+    yuv: Optional[tuple]
+    colour: Optional[tuple]
+    samples: list
+    shift: int = 0
+
+
+def _writable(views, who: str) -> None:
+    for v in views:
+        if any(st == 0 and n > 1 for st, n in zip(v.stride(), v.shape)):
+            raise ValueError(f"{who}: the target is an expanded view, not memory a frame can be written into")
+
+
+def overlay_surface(target) -> OverlaySurface:
+    """A target described, without a copy. ``target``: a uint8 ``[h, w, 3]`` (or ``[1, h, w, 3]``) RGB tensor whose
+    rows may be pitched, or a frame of ``models/workload``: ``Packed`` (``data``, ``order``), ``Nv12`` / ``YuvSemiPlanar``
+    (``y``, ``uv``), ``Yuv420p`` / ``YuvPlanar`` (``y``, ``u``, ``v``) or ``Yuyv`` (``data``, ``width``) — told apart by
+    those fields, so nothing here imports them. ``ValueError`` for a batch above one, a transfer that is not ``sdr``
+    and memory that is not a writable surface of the layout."""
+    who = "overlay"
+    if getattr(target, "transfer", "sdr") != "sdr":
+        raise ValueError(f"{who}: an SDR colour has no code on a {target.transfer!r} surface (no inverse tone map)")
+    g = lambda name, default: getattr(target, name, default)    # noqa: E731
+    if isinstance(target, torch.Tensor) or (hasattr(target, "data") and hasattr(target, "order")
+                                            and not hasattr(target, "width")):
+        data, order = (target, "rgb") if isinstance(target, torch.Tensor) else (target.data, target.order)
+        if order not in PACKED_ORDERS:
+            raise ValueError(f"{who}: channel order {order!r} is none of {sorted(PACKED_ORDERS)}")
+        C, (r, _, b) = PACKED_ORDERS[order]
+        if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() not in (3, 4) \
+                or data.shape[-1] != C or 0 in data.shape:
+            raise ValueError(f"{who}: {order} takes a uint8 [h, w, {C}] tensor")
+        data = data if data.dim() == 4 else data[None]
+        if data.shape[0] != 1:
+            raise ValueError(f"{who}: one frame, not a batch of {data.shape[0]}")
+        if not _packed_strides(data):
+            raise ValueError(f"{who}: rows may be pitched, but the bytes of a row are contiguous")
+        _writable((data,), who)
+        return OverlaySurface(data.shape[1], data.shape[2], data.device, (data, order), None, None,
+                              [(data[0, :, :, c], k, 0, 0) for k, c in enumerate((r, 1, b))])
+    matrix, full = g("matrix", "bt601"), bool(g("full_range", False))
+    if hasattr(target, "data") and hasattr(target, "width"):
+        order = g("order", "yuyv")
+        yv, uv, vv = yuyv_planes(target.data, target.width, order)
+        data = target.data if target.data.dim() == 3 else target.data[None]
+        planes, sub, depth, msb = (data,), "422", 8, False
+        yuv = (YUV_PACKED, planes, sub, depth, msb, tuple(YUYV_ORDERS).index(order))
+        views = (yv, uv, vv)
+    elif hasattr(target, "y") and hasattr(target, "uv"):
+        sub, depth, msb = g("subsampling", "420"), g("depth", 8), bool(g("msb", False))
+        y, uv = yuv_semiplanar_planes(target.y, target.uv, sub, depth)
+        B, ch, cw = uv.shape[:3]
+        pairs = uv.as_strided((B, ch, 2 * cw), (uv.stride(0), uv.stride(1), 1))
+        vu = int(bool(g("vu", False)))
+        yuv = (YUV_SEMIPLANAR, (y, pairs), sub, depth, msb, vu)
+        views = (y, uv[..., vu], uv[..., 1 - vu])
+    elif hasattr(target, "y") and hasattr(target, "u") and hasattr(target, "v"):
+        sub, depth, msb = g("subsampling", "420"), g("depth", 8), bool(g("msb", False))
+        views = yuv_planes(target.y, target.u, target.v, sub, depth)
+        yuv = (YUV_PLANAR, tuple(views), sub, depth, msb, 0)
+    else:
+        raise ValueError(f"{who}: the target is a uint8 [h, w, 3] tensor or a Packed, Nv12, Yuv420p, YuvPlanar, "
+                         f"YuvSemiPlanar or Yuyv frame, not {type(target).__name__}")
+    _yuv_check(matrix, yuv[3])
+    if views[0].shape[0] != 1:
+        raise ValueError(f"{who}: one frame, not a batch of {views[0].shape[0]}")
+    _writable(yuv[1], who)
+    hs, vs = YUV_SUBSAMPLING[yuv[2]]
+    samples = [(views[0][0], 0, 0, 0), (views[1][0], 1, hs, vs), (views[2][0], 2, hs, vs)]
+    return OverlaySurface(views[0].shape[1], views[0].shape[2], views[0].device, None, yuv, (matrix, full, yuv[3]),
+                          samples, 16 - yuv[3] if (yuv[4] and yuv[3] != 8) else 0)
+
+
+def overlay_host_codes(palette, redact_rgb, colour: Optional[tuple]) -> np.ndarray:
+    """The colour table of :func:`overlay_codes` on the host, int32 ``[2 K + 1, 3]``: entry ``k``'s fill at ``2 k``,
+    its text colour at ``2 k + 1``, the redact colour last. ``colour`` None: the RGB bytes. ``colour = (matrix,
+    full_range, depth)``: Y, U, V codes — the inverse of :func:`yuv_real_matrix` applied in fp64, ``inv(M) @ rgb +
+    offsets``, rounded half up and clipped to ``[0, 2^depth - 1]``."""
+    pal = np.asarray(palette)
+    if pal.ndim != 3 or pal.shape[1:] != (2, 3) or not 1 <= pal.shape[0] <= OVERLAY_MAX_COLOURS \
+            or pal.dtype.kind not in "iu" or pal.min() < 0 or pal.max() > 255:
+        raise ValueError(f"overlay: a palette is [K, 2, 3] integers in 0..255 with 1 <= K <= {OVERLAY_MAX_COLOURS}")
+    red = np.asarray(redact_rgb)
+    if red.shape != (3,) or red.dtype.kind not in "iu" or red.min() < 0 or red.max() > 255:
+        raise ValueError("overlay: the redact colour is three integers in 0..255")
+    rgb = np.concatenate((pal.reshape(-1, 3), red[None])).astype(np.float64)
+    if colour is None:
+        return rgb.astype(np.int32)
+    matrix, full_range, depth = colour
+    m, off = yuv_real_matrix(matrix, full_range, depth)
+    yuv = rgb @ np.linalg.inv(m).T + np.array(off, dtype=np.float64)
+    return np.clip(np.floor(yuv + 0.5), 0, (1 << depth) - 1).astype(np.int32)
+
+
+#: the colour tables of :func:`overlay_codes` per (palette, redact colour, layout description, device), and the glyph
+#: table per device: read by address by a recorded launch, so kept as :data:`_tables` are
+_overlay_tables = GraphCache(16)
+
+
+def overlay_codes(palette, redact_rgb, frame) -> torch.Tensor:
+    """``palette`` (:func:`overlay_palette`'s shape) and the redact colour as the codes of ``frame``'s surface
+    (:func:`overlay_host_codes`), an int32 ``[2 K + 1, 3]`` table on the frame's device, cached: a captured graph
+    must not copy from the host, so make it eagerly first; :func:`invalidate_cache` drops it."""
+    s = frame if isinstance(frame, OverlaySurface) else overlay_surface(frame)
+    pal, red = np.asarray(palette), np.asarray(redact_rgb)
+    key = ("codes", pal.shape, pal.tobytes(), red.tobytes(), s.colour, str(s.device))
+    return _overlay_tables.get(key, lambda: torch.from_numpy(overlay_host_codes(pal, red, s.colour)).to(s.device))
+
+
+def _overlay_table(name: str, values, device: torch.device) -> torch.Tensor:
+    """A constant int32 table on ``device``, cached by name."""
+    return _overlay_tables.get((name, str(device)), lambda: torch.tensor(values, dtype=torch.int32).to(device))
+
+
+def _overlay_font(device: torch.device) -> torch.Tensor:
+    return _overlay_table("font", OVERLAY_FONT, device)
+
+
+def _overlay_check(surface: OverlaySurface, count, scores, labels, boxes, track_id, track_hits, thickness, scale, modes,
+                   min_hits, codes) -> tuple:
+    """The arguments of :func:`overlay` checked, ``ValueError`` before any launch; the lists as ``count [1]``,
+    ``scores [N]``, ``labels [N]``, ``boxes [N, 4]``, ids and hits ``[N]`` or None (``[1, N]`` views are flattened)."""
+    who = "overlay"
+    if not 1 <= int(thickness) <= OVERLAY_MAX_THICKNESS:
+        raise ValueError(f"{who}: thickness {thickness!r} is not in 1..{OVERLAY_MAX_THICKNESS}")
+    if not 0 <= int(scale) <= OVERLAY_MAX_SCALE:
+        raise ValueError(f"{who}: scale {scale!r} is not in 0..{OVERLAY_MAX_SCALE} (0: no tags)")
+    if not int(min_hits) >= 1:
+        raise ValueError(f"{who}: min_hits {min_hits!r} is not a number of frames from 1 up")
+    if (track_id is None) != (track_hits is None):
+        raise ValueError(f"{who}: track_id and track_hits go together")
+    if scores.dim() == 2 and scores.shape[0] == 1:
+        scores, labels, boxes = scores[0], labels.reshape(-1), boxes.reshape(-1, 4)
+        if track_id is not None:
+            track_id, track_hits = track_id.reshape(-1), track_hits.reshape(-1)
+    if scores.dim() != 1 or count.numel() != 1:
+        raise ValueError(f"{who}: count and scores are one frame's: count [1], scores [N] (or [1, N])")
+    N = scores.shape[0]
+    if labels.shape != (N,) or boxes.shape != (N, 4) or (track_id is not None and (track_id.shape != (N,)
+                                                                                 or track_hits.shape != (N,))):
+        raise ValueError(f"{who}: labels, boxes [N, 4] and ids do not go with the {N} scores")
+    ints = (torch.int32, torch.int64)
+    if not scores.is_floating_point() or not boxes.is_floating_point() or labels.dtype not in ints \
+            or count.dtype not in ints or (track_id is not None and (track_id.dtype not in ints
+                                                                    or track_hits.dtype not in ints)):
+        raise ValueError(f"{who}: floating-point scores and boxes, int32 or int64 count, labels, ids and hits")
+    if not isinstance(modes, torch.Tensor) or modes.dtype != torch.uint8 or modes.dim() != 1 or modes.numel() < 1:
+        raise ValueError(f"{who}: modes is a uint8 [L] tensor of 0 (not drawn), 1 (outline and tag), 2 (redacted)")
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.int32 or codes.dim() != 2 or codes.shape[1] != 3 \
+            or codes.shape[0] < 3 or codes.shape[0] % 2 != 1 or codes.shape[0] > 2 * OVERLAY_MAX_COLOURS + 1 \
+            or not codes.is_contiguous():
+        raise ValueError(f"{who}: codes is overlay_codes' contiguous int32 [2 K + 1, 3] table")
+    for name, t in (("count", count), ("scores", scores), ("labels", labels), ("boxes", boxes), ("track_id", track_id),
+                    ("track_hits", track_hits), ("modes", modes), ("codes", codes)):
+        if t is not None and t.device != surface.device:
+            raise ValueError(f"{who}: the target is on {surface.device}, {name} on {t.device}")
+    return count.reshape(1), scores, labels, boxes, track_id, track_hits
+
+
+def overlay_slots(h: int, w: int, count, scores, labels, boxes, track_id, track_hits, thickness: int, scale: int,
+                  modes: torch.Tensor, min_hits: int, K: int) -> torch.Tensor:
+    """The drawing rule of :func:`overlay` on the lists' device, without a host sync: int32 ``[h, w]``, the colour slot
+    of every pixel (``2 k`` fill and ``2 k + 1`` text of palette entry ``k``, ``2 K`` the redact colour) or -1 where
+    nothing is drawn. Written for clarity: a loop of ``N`` steps over full-frame masks."""
+    dev, N, t, s = scores.device, scores.shape[0], int(thickness), int(scale)
+    i32 = torch.int32
+    Y = torch.arange(h, device=dev, dtype=i32)[:, None]
+    X = torch.arange(w, device=dev, dtype=i32)[None, :]
+    font, tens = _overlay_font(dev), _overlay_table("tens", (1, 10, 100, 1000, 10000, 100000), dev)
+    L = modes.shape[0]
+    lb = labels.to(torch.int64)
+    inside = (lb >= 0) & (lb < L)
+    mode = torch.where(inside, modes[lb.clamp(0, L - 1)].to(i32), 0)
+    bx = boxes.to(torch.float32)
+    finite = torch.isfinite(bx).all(dim=1)
+    c = torch.where(finite[:, None], bx, 0.0).clamp(-OVERLAY_CLAMP, OVERLAY_CLAMP)
+    x0, y0 = torch.floor(c[:, 0]).to(i32), torch.floor(c[:, 1]).to(i32)
+    x1, y1 = torch.ceil(c[:, 2]).to(i32) - 1, torch.ceil(c[:, 3]).to(i32) - 1
+    n = count.reshape(1)[0].clamp(0, N)
+    ok = (torch.arange(N, device=dev) < n) & (scores.to(torch.float32) > 0) & ((mode == 1) | (mode == 2)) & finite \
+        & (x1 >= x0) & (y1 >= y0)
+    key = lb
+    if track_id is not None:
+        ok = ok & (track_id > 0) & (track_hits >= int(min_hits))
+        key = track_id.to(torch.int64)
+    key = torch.where(ok, key, 0)          # (a row that is not drawn may hold anything)
+    v = (key % 1000000).to(i32)
+    nd = 1 + sum((v >= p).to(i32) for p in (10, 100, 1000, 10000, 100000))
+    col = torch.where(mode == 2, 2 * K, 2 * (key % K)).to(i32)
+    ty = torch.where(y0 - 9 * s >= 0, y0 - 9 * s, y0)
+    slot = torch.full((h, w), -1, dtype=i32, device=dev)
+    for r in range(N):
+        outer = (X >= x0[r]) & (X <= x1[r]) & (Y >= y0[r]) & (Y <= y1[r])
+        inner = (X >= x0[r] + t) & (X <= x1[r] - t) & (Y >= y0[r] + t) & (Y <= y1[r] - t)
+        mine = torch.where(outer & ((mode[r] == 2) | ~inner), col[r], -1)
+        if s > 0:
+            u, tv = X - x0[r], Y - ty[r]
+            tag = (mode[r] == 1) & (u >= 0) & (u < (6 * nd[r] + 1) * s) & (tv >= 0) & (tv < 9 * s)
+            gu, gv = u - s, tv - s
+            glyph = (gu >= 0) & (gu < 6 * s * nd[r]) & (gv >= 0) & (gv < 7 * s)
+            gu, gv = gu.clamp(0, 36 * s - 1), gv.clamp(0, 7 * s - 1)
+            digit = torch.div(v[r], tens[(nd[r] - 1 - torch.div(gu, 6 * s, rounding_mode="floor")).clamp(0, 5).long()],
+                              rounding_mode="floor") % 10
+            cu = torch.div(gu % (6 * s), s, rounding_mode="floor")
+            bits = font[digit.long(), torch.div(gv, s, rounding_mode="floor").long()]      # [h, w] by broadcast
+            text = glyph & (cu < 5) & (((bits >> (4 - cu.clamp(max=4))) & 1) == 1)
+            mine = torch.where(tag, torch.where(text, col[r] + 1, col[r]), mine)
+        slot = torch.where((slot < 0) & ok[r], mine, slot)
+    return slot
+
+
+def overlay_reference(target, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor,
+                      track_id: Optional[torch.Tensor] = None, track_hits: Optional[torch.Tensor] = None, *,
+                      thickness: int, scale: int, modes: torch.Tensor, min_hits: int = 1, codes: torch.Tensor):
+    """The torch composition of :func:`overlay`, with the same effect on ``target`` in place and without a host sync:
+    :func:`overlay_slots`, then every sample plane of the surface rewritten through its strided view — the sample of
+    ``(cy, cx)`` takes the colour of luma pixel ``(cy << vsub, cx << hsub)`` where that pixel is painted and keeps its
+    value elsewhere."""
+    surface = overlay_surface(target)
+    lists = _overlay_check(surface, count, scores, labels, boxes, track_id, track_hits, thickness, scale, modes,
+                           min_hits, codes)
+    if lists[1].shape[0] == 0:
+        return target
+    slot = overlay_slots(surface.h, surface.w, *lists, thickness, scale, modes, min_hits, (codes.shape[0] - 1) // 2)
+    for view, comp, hs, vs in surface.samples:
+        sub = slot[::1 << vs, ::1 << hs]
+        val = codes[sub.clamp(min=0).long(), comp] << surface.shift
+        if view.dtype == torch.uint8:
+            view.copy_(torch.where(sub >= 0, val.to(torch.uint8), view))
+        else:       # 16-bit words, written whole: the same bits as int16
+            bits = view if view.dtype == torch.int16 else view.view(torch.int16)
+            bits.copy_(torch.where(sub >= 0, ((val + 32768) % 65536 - 32768).to(torch.int16), bits))
+    return target
+
+
+def overlay(target, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor,
+            track_id: Optional[torch.Tensor] = None, track_hits: Optional[torch.Tensor] = None, *, thickness: int,
+            scale: int, modes: torch.Tensor, min_hits: int = 1, codes: torch.Tensor):
+    """One frame's detections — ``count [1]``, ``scores [N]``, ``labels [N]``, ``boxes [N, 4]`` (corners, frame pixels)
+    as :func:`detections` (one image; its ``[1, N]`` views are accepted) and :func:`merge_detections` return them, and
+    optionally ``track_id``, ``track_hits`` ``[N]`` of :func:`track_update` — painted into ``target``
+    (:func:`overlay_surface`) in place, with no host synchronisation, no RGB frame and no copy; returns ``target``.
+    ``modes``: uint8 ``[L]`` on the device, per label 0 (not drawn), 1 (outline and tag) or 2 (redacted); ``codes``:
+    :func:`overlay_codes`' table of ``K`` palette entries and the redact colour. The rule, in exact integers:
+
+    1. Row ``r`` is drawn when ``r < clamp(count, 0, N)``, ``scores[r] > 0`` (a NaN is not), ``0 <= labels[r] < L``
+       with a mode of 1 or 2, all four coordinates finite, with ids ``track_id[r] > 0`` and ``track_hits[r] >=
+       min_hits``, and its rectangle not empty.
+    2. Each coordinate is clamped in fp32 to ``[-2^20, 2^20]``; pixel ``i`` covers ``[i, i + 1)``, so the outer
+       rectangle is columns ``floor(x0) .. ceil(x1) - 1`` and rows ``floor(y0) .. ceil(y1) - 1``, inclusive.
+    3. Mode 1 paints the outer rectangle minus the inner one, ``thickness`` in from every side (a box thinner than
+       twice that is solid), in fill colour ``key mod K``; ``key`` is the row's id with ids, else its label. With
+       ``scale = s > 0`` it also paints a tag: ``key mod 10^6`` in decimal, ``nd`` digits of :data:`OVERLAY_FONT` in
+       cells ``6 s`` wide inside a margin of ``s`` — ``(6 nd + 1) s`` wide and ``9 s`` high, its columns from the box's
+       first, its rows above the box when they fit the frame, else from the box's first row; the digits' set bits in the
+       text colour, the rest of the tag in the fill colour. Mode 2 paints the whole outer rectangle in the redact colour.
+    4. Everything is clipped to the frame; where several rows cover a pixel, the lowest row wins.
+    5. Packed pixels: the three colour bytes, never a fourth. YUV: the luma sample of every painted pixel, and a chroma
+       sample ``(cy, cx)`` exactly when luma pixel ``(cy << vsub, cx << hsub)`` is painted, in that pixel's colour (so a
+       one-pixel line on an odd column of a subsampled surface changes luma only); 16-bit samples as whole words,
+       ``code << shift``. No other byte is written: not the pitch padding, not the parent of a crop.
+
+    One HIP launch (a workgroup per :data:`OVERLAY_TILE` of luma pixels) for fp32 / int32 lists up to 1024 rows on the
+    GPU; past that, for other dtypes, on the CPU and with the ``torch`` backend :func:`overlay_reference`. Alpha
+    blending, antialiased lines, class names or any glyph but digits, PQ / HLG surfaces, batches above one and more
+    than 1024 rows are not offered."""
+    surface = overlay_surface(target)
+    lists = _overlay_check(surface, count, scores, labels, boxes, track_id, track_hits, thickness, scale, modes,
+                           min_hits, codes)
+    count, scores, labels, boxes, track_id, track_hits = lists
+    N = scores.shape[0]
+    i32 = torch.int32
+    if not _use_hip(scores) or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or labels.dtype != i32 \
+            or count.dtype != i32 or (track_id is not None and (track_id.dtype != i32 or track_hits.dtype != i32)) \
+            or N > MAX_ROWS or N < 1:
+        return overlay_reference(target, *lists, thickness=thickness, scale=scale, modes=modes, min_hits=min_hits,
+                                 codes=codes)
+    scores, labels, boxes, modes = scores.contiguous(), labels.contiguous(), boxes.contiguous(), modes.contiguous()
+    ids = (None, None) if track_id is None else (track_id.contiguous(), track_hits.contiguous())
+    tail = (count.data_ptr(), scores.data_ptr(), labels.data_ptr(), boxes.data_ptr(),
+            None if ids[0] is None else ids[0].data_ptr(), None if ids[1] is None else ids[1].data_ptr(), N,
+            modes.data_ptr(), modes.shape[0], codes.data_ptr(), (codes.shape[0] - 1) // 2,
+            _overlay_font(surface.device).data_ptr(), int(thickness), int(scale), int(min_hits),
+            torch.cuda.current_stream().cuda_stream)
+    if surface.packed is not None:
+        data, order = surface.packed
+        lo, hi = _storage_bounds(data)
+        pitch = data.stride(1) if data.shape[1] > 1 else data.shape[2] * data.shape[3]
+        rc = _L().nos_overlay_packed(data.data_ptr(), lo, hi, pitch, order.encode(), surface.h, surface.w, *tail)
+    else:
+        src = yuv_src(*surface.yuv, (0,) * 12)
+        rc = _L().nos_overlay_yuv(ctypes.byref(src), surface.h, surface.w, *tail)
+    _check(rc, "overlay")
+    return target
