@@ -425,6 +425,14 @@ def test_agent_process_serves_the_real_gpu(gpu):
             c.stop()
 
 
+def _needs_kfd_process_list():
+    """amd-smi's per-process list (VRAM, CU occupancy) is the KFD's per-process directory: a KFD
+    that publishes none (a guest kernel's) lists no process, whatever runs on the GPU."""
+    from walkai_nos_amd.deviceplugin.startgate import KFD_PROC
+    if not os.path.isdir(KFD_PROC):
+        pytest.skip(f"the KFD publishes no per-process directory here ({KFD_PROC}): amd-smi lists no process")
+
+
 def test_hbm_guard_sees_a_process_that_bypasses_the_budget_shim(gpu, tmp_path):
     """The HBM guard's input is amd-smi's per-process VRAM, not the container's own interposer: a
     process given a 1 GiB slice budget that runs WITHOUT the shim and holds 3 GiB is found over
@@ -436,6 +444,7 @@ def test_hbm_guard_sees_a_process_that_bypasses_the_budget_shim(gpu, tmp_path):
     not resolve (the agent DaemonSet runs with hostPID: true instead). So the test maps them itself:
     the two processes that appear in amd-smi's list after the children start, told apart by size,
     get a stand-in /proc entry holding the child's real environment."""
+    _needs_kfd_process_list()
     import time
     from types import SimpleNamespace
 
@@ -510,6 +519,7 @@ def test_cu_guard_flags_only_the_process_outside_its_cu_mask(gpu):
     none (a pod that unset it). The guard, from amd-smi's per-process CU occupancy alone, flags the
     unmasked one only — or, when amd-smi reports no occupancy here, says "unavailable", never
     "clean". The samples are written to gpurun_out/cu_guard_samples.json (profiles/)."""
+    _needs_kfd_process_list()
     import json
 
     from walkai_nos_amd.controllers.hbmguard import HbmGuard

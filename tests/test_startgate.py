@@ -151,3 +151,37 @@ def test_kfd_probe_without_a_shared_pid_namespace(tmp_path):
     assert not p.ready("bdf::s1", bdf, snap)
     add(601, "17010", ["0", "0"])
     assert p.ready("bdf::s1", bdf, snap)
+
+
+def test_kfd_probe_without_the_kfd_process_directory(tmp_path):
+    """A KFD that publishes no per-process directory: a process is ready once it has its GPU's
+    doorbells mapped from /dev/kfd (offset: type 3 in bits 63:62, the KFD gpu_id in bits 61:46)."""
+    from walkai_nos_amd.deviceplugin.startgate import KfdProbe, kfd_doorbell_gpu_ids
+    topo, proc = tmp_path / "topo", tmp_path / "proc"
+    for node, (gid, loc) in enumerate((("0", 0), ("16143", 0xd9 << 8), ("9999", 0x75 << 8))):
+        d = topo / str(node)
+        d.mkdir(parents=True)
+        (d / "gpu_id").write_text(gid + "\n")
+        (d / "properties").write_text(f"cpu_cores_count 0\nlocation_id {loc}\ndomain 0\n")
+
+    def add(pid, ids, rows):
+        (proc / str(pid)).mkdir(parents=True)
+        (proc / str(pid) / "environ").write_bytes(f"NOS_SLICE_IDS={ids}".encode() + b"\0" if ids else b"")
+        (proc / str(pid) / "maps").write_text("".join(
+            f"4ffffff{i:x}a000-4ffffff{i:x}c000 rw-s {off:08x} 00:06 136 {path}\n" for i, (off, path) in enumerate(rows)))
+    doorbell, mmio, render = (3 << 62) | (16143 << 46), 16143 << 46, "/dev/dri/renderD128"
+    add(500, "bdf::s0", [(0x10004c000, render), (mmio, "/dev/kfd"), (doorbell, "/dev/kfd")])    # an older pod
+    add(501, None, [(0x7f00, "/usr/lib/libc.so.6")])
+    (proc / "self").mkdir()
+    assert kfd_doorbell_gpu_ids(500, str(proc)) == {"16143"}
+    assert kfd_doorbell_gpu_ids(501, str(proc)) == kfd_doorbell_gpu_ids(502, str(proc)) == frozenset()
+    p = KfdProbe(proc=str(proc), kfd=str(tmp_path / "kfd"), topology=str(topo))
+    bdf = "0000:d9:00.0"
+    snap = p.snapshot(bdf)
+    assert snap == {500} and p.ready("bdf::s0", bdf, snap) and not p.ready("bdf::s1", bdf, snap)
+    add(600, "bdf::s1", [(0x10004c000, render), (mmio, "/dev/kfd")])        # the KFD open, no queue yet
+    assert not p.ready("bdf::s1", bdf, snap)
+    add(777, "bdf::s1", [((3 << 62) | (9999 << 46), "/dev/kfd")])            # another GPU's doorbells
+    assert not p.ready("bdf::s1", bdf, snap) and p.ready_pids() == {500, 777}
+    add(601, "bdf::s1", [(mmio, "/dev/kfd"), (doorbell, "/dev/kfd")])
+    assert p.ready("bdf::s1", bdf, snap)

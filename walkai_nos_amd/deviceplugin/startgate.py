@@ -16,7 +16,9 @@ once the previous memory-only container let through on that GPU is *ready* — i
 queues in the KFD (``/sys/class/kfd/kfd/proc/<pid>/queues/*/type`` = 0, on that GPU's KFD
 ``gpuid``) — or ``timeout`` seconds after it was let through (a container that never opens the GPU,
 or one that failed, does not hold the others back for longer; kubelet gives the call 30 s).
-Dedicated-CU slices pass at once: their CUs are their own.
+Dedicated-CU slices pass at once: their CUs are their own. A KFD without the per-process directory
+(a guest kernel's) gives no queue count: there a container is ready once its process has that GPU's
+doorbells mapped (``/proc/<pid>/maps``), which the runtime does when it creates the first queue.
 
 Which KFD process is the previous container's: with hostPID (the agent's DaemonSet) the process
 whose environment carries the slice in ``NOS_SLICE_IDS``; where the agent's PIDs are not the KFD's
@@ -55,6 +57,30 @@ def kfd_compute_queues(pid: int, root: str = KFD_PROC) -> int:
         except OSError:
             continue
     return n
+
+
+#: a doorbell mapping's offset into /dev/kfd: type in bits 63:62 (3: doorbells), KFD gpu_id in 61:46
+_KFD_MMAP_DOORBELL = 3
+
+
+def kfd_doorbell_gpu_ids(pid: int, proc: str = "/proc") -> frozenset:
+    """KFD ``gpu_id`` of every GPU whose doorbells ``pid`` has mapped (its ``/dev/kfd`` rows in
+    ``/proc/<pid>/maps``); the runtime maps a GPU's doorbells when it creates the process's first
+    queue there. Empty when the process has none, is gone or is not ours to read."""
+    try:
+        with open(os.path.join(proc, str(pid), "maps"), "rb") as f:
+            maps = f.read()
+    except OSError:
+        return frozenset()
+    out = set()
+    if b"/dev/kfd" in maps:
+        for ln in maps.splitlines():
+            col = ln.split()
+            if len(col) >= 6 and col[5] == b"/dev/kfd":
+                off = int(col[2], 16)
+                if off >> 62 == _KFD_MMAP_DOORBELL:
+                    out.add(str((off >> 46) & 0xFFFF))
+    return frozenset(out)
 
 
 def slice_ids_of(pid: int, proc: str = "/proc") -> frozenset:
@@ -124,6 +150,15 @@ class KfdProbe:
         """KFD processes with their compute queues (on the GPU at ``bdf`` when its gpu_id is known)."""
         gid = self._gpu_id(bdf)
         out = set()
+        if not os.path.isdir(self.kfd):
+            # a KFD that publishes no per-process directory (a guest's): a process's queues cannot be
+            # counted, so it is ready once it has the GPU's doorbells mapped — its first queue exists
+            for d in os.listdir(self.proc):
+                if d.isdigit():
+                    gids = kfd_doorbell_gpu_ids(int(d), self.proc)
+                    if (gids if gid is None else gid in gids):
+                        out.add(int(d))
+            return frozenset(out)
         for d in glob.glob(os.path.join(self.kfd, "*")):
             pid = os.path.basename(d)
             if not pid.isdigit():
