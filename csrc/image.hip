@@ -17,6 +17,8 @@
 //  * Tracking (image_track.h): track_update_f32, the detections of successive frames associated in device state.
 //  * Drawing (image_overlay.h): overlay_k, the detections painted into the frame's own planes — the one kernel here
 //    that writes a surface.
+//  * Pixelating (image_mosaic.h): mosaic_k, the cells a selected detection touches replaced by their mean, in place —
+//    the one kernel here that reads a surface and writes it.
 //  * Entries. The extern "C" functions at the end check every argument of an outside caller, fill the kernel's
 //    arguments and launch; the arguments all image entries share travel as one struct (Common).
 #include <hip/hip_runtime.h>
@@ -31,6 +33,7 @@
 #include "image_track.h"
 #include "image_stage.h"
 #include "image_overlay.h"
+#include "image_mosaic.h"
 #include "image_yuv.h"
 
 namespace {
@@ -300,6 +303,12 @@ int fail(const char* msg) {
   return -1;
 }
 
+// a refusal of an entry that shares its checks with another: "<who><msg>"
+int fail(const char* who, const std::string& msg) {
+  g_err = who + msg;
+  return -1;
+}
+
 // an image kernel on grid workgroups of 256 threads; what: the entry's name in the error a failed launch leaves
 template <class... A>
 int launch(Kernel<A...> kernel, int grid, void* stream, const char* what, const ImgArgs& k, const A&... n) {
@@ -523,19 +532,43 @@ int yuv_launch(const NosYuvSrc& s, bool hdr, const ImgArgs& k, const YuvHdrArgs&
   if (s.chroma == 1) return yuv_launch_as<YuvBilinearArgs>(s, k, n, f, grid, stream, what);
   return yuv_launch_as<YuvArgs>(s, k, n, f, grid, stream, what);
 }
+// What the overlay and mosaic entries check of one frame's lists, of the [L] table of labels and of the frame's size.
+int list_args(const char* who, int h, int w, const int* count, const float* scores, const int* labels,
+              const float* boxes, const int* track_id, const int* track_hits, int N, const void* table, int L,
+              int min_hits) {
+  const char* msg = nullptr;
+  if (!count || !scores || !labels || !boxes || !table) msg = ": null operand";
+  else if ((track_id == nullptr) != (track_hits == nullptr)) msg = ": track_id and track_hits go together";
+  else if (h <= 0 || w <= 0 || h > (1 << 15) || w > (1 << 15)) msg = ": a frame of 1..32768 rows and columns";
+  else if (N <= 0 || N > OMAX) msg = ": 0 < rows <= 1024";
+  else if (L <= 0 || min_hits < 1) msg = ": labels > 0, min_hits >= 1";
+  return msg ? fail(who, msg) : 0;
+}
+
 // What both overlay entries check of the lists, the tables and the parameters, and fill of k.
 int overlay_args(OverlayArgs& k, int h, int w, const int* count, const float* scores, const int* labels,
                  const float* boxes, const int* track_id, const int* track_hits, int N, const void* modes, int L,
                  const int* codes, int K, const int* font, int thickness, int scale, int min_hits) {
-  if (!count || !scores || !labels || !boxes || !modes || !codes || !font) return fail("overlay: null operand");
-  if ((track_id == nullptr) != (track_hits == nullptr)) return fail("overlay: track_id and track_hits go together");
-  if (h <= 0 || w <= 0 || h > (1 << 15) || w > (1 << 15)) return fail("overlay: a frame of 1..32768 rows and columns");
-  if (N <= 0 || N > OMAX) return fail("overlay: 0 < rows <= 1024");
-  if (L <= 0 || K <= 0 || K > OVERLAY_MAX_K) return fail("overlay: labels > 0, 0 < colours <= 1024");
-  if (thickness < 1 || thickness > OVERLAY_MAX_T || scale < 0 || scale > OVERLAY_MAX_S || min_hits < 1)
-    return fail("overlay: 1 <= thickness <= 2^20, 0 <= scale <= 1024, min_hits >= 1");
+  if (!codes || !font) return fail("overlay: null operand");
+  if (const int rc = list_args("overlay", h, w, count, scores, labels, boxes, track_id, track_hits, N, modes, L, min_hits))
+    return rc;
+  if (K <= 0 || K > OVERLAY_MAX_K) return fail("overlay: 0 < colours <= 1024");
+  if (thickness < 1 || thickness > OVERLAY_MAX_T || scale < 0 || scale > OVERLAY_MAX_S)
+    return fail("overlay: 1 <= thickness <= 2^20, 0 <= scale <= 1024");
   k = OverlayArgs{count, scores, labels, boxes, track_id, track_hits, static_cast<const uint8_t*>(modes), codes, font,
                   N, L, K, thickness, scale, min_hits, h, w};
+  return 0;
+}
+
+// What both mosaic entries check and fill of k (mask is the surface's, filled by the entry).
+int mosaic_args(MosaicArgs& k, int h, int w, const int* count, const float* scores, const int* labels,
+                const float* boxes, const int* track_id, const int* track_hits, int N, const void* select, int L,
+                int min_hits, int cell) {
+  if (const int rc = list_args("mosaic", h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits))
+    return rc;
+  if (cell < MOSAIC_MIN_CELL || cell > MTILE || (cell & (cell - 1))) return fail("mosaic: a cell of 4, 8, 16, 32 or 64 pixels");
+  k = MosaicArgs{count, scores, labels, boxes, track_id, track_hits, static_cast<const uint8_t*>(select), N, L, min_hits,
+                 h, w, cell, 255};
   return 0;
 }
 
@@ -545,6 +578,35 @@ int overlay_launch(const OverlayArgs& k, const Dst& dst, void* stream, const cha
   const int grid = ((k.h + OTH - 1) / OTH) * ((k.w + OTW - 1) / OTW);
   hipLaunchKernelGGL(overlay_k<Dst>, dim3(grid), dim3(OT), 0, reinterpret_cast<hipStream_t>(stream), k, dst);
   return check(what);
+}
+
+// mosaic_k on one workgroup per tile of the h x w frame
+template <class Dst>
+int mosaic_launch(const MosaicArgs& k, const Dst& dst, void* stream, const char* what) {
+  const int grid = ((k.h + MTILE - 1) / MTILE) * ((k.w + MTILE - 1) / MTILE);
+  hipLaunchKernelGGL(mosaic_k<Dst>, dim3(grid), dim3(MT), 0, reinterpret_cast<hipStream_t>(stream), k, dst);
+  return check(what);
+}
+
+// The checks both packed entries (who: overlay_packed, mosaic_packed) make of the image and its order; fills dst.
+int packed_dst(const char* who, PackedDst& dst, void* img, const void* lo, const void* hi, long long pitch,
+               const char* order, int h, int w) {
+  PackedArgs o{};
+  const int C = packed_order(order, o);
+  if (!C) return fail(who, ": unknown channel order (rgb, bgr, rgba or bgra)");
+  dst = PackedDst{plane_arg(img, lo, hi, pitch, 0), C, o.r};
+  if (pitch < (long long)w * C) return fail(who, ": the row pitch is smaller than a row's bytes");
+  if (!stride_range(dst.s)) return fail(who, ": pitch out of range");
+  if (!inside(1, dst.s, h, (long long)w * C)) return fail(who, ": the image does not lie inside its storage bounds");
+  return 0;
+}
+
+// The checks both YUV entries (who: overlay_yuv, mosaic_yuv) make of the descriptor's format and planes; fills d.
+int yuv_dst(const char* who, YuvDst& d, const NosYuvSrc& s, int h, int w) {
+  long long cw = 0, ch = 0;
+  if (yuv_format(s) || yuv_planes(s, 1, h, w, d.pl, cw, ch)) return fail(who, ": the surface: " + g_err);
+  d.layout = s.layout, d.hsub = s.hsub, d.vsub = s.vsub, d.sb = s.sample_bytes, d.shift = s.shift, d.order = s.order;
+  return 0;
 }
 }  // namespace
 
@@ -846,17 +908,12 @@ int nos_overlay_packed(void* img, const void* lo, const void* hi, long long pitc
                        const int* track_id, const int* track_hits, int N, const void* modes, int L, const int* codes,
                        int K, const int* font, int thickness, int scale, int min_hits, void* stream) {
   if (!img || !order) return fail("overlay: null operand");
-  PackedArgs o{};
-  const int C = packed_order(order, o);
-  if (!C) return fail("overlay_packed: unknown channel order (rgb, bgr, rgba or bgra)");
   OverlayArgs k{};
   if (const int rc = overlay_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, modes, L, codes, K,
                                   font, thickness, scale, min_hits))
     return rc;
-  const PackedDst dst{plane_arg(img, lo, hi, pitch, 0), C, o.r};
-  if (pitch < (long long)w * C) return fail("overlay_packed: the row pitch is smaller than a row's bytes");
-  if (!stride_range(dst.s)) return fail("overlay_packed: pitch out of range");
-  if (!inside(1, dst.s, h, (long long)w * C)) return fail("overlay_packed: the image does not lie inside its storage bounds");
+  PackedDst dst{};
+  if (const int rc = packed_dst("overlay_packed", dst, img, lo, hi, pitch, order, h, w)) return rc;
   return overlay_launch(k, dst, stream, "overlay_packed");
 }
 
@@ -874,14 +931,46 @@ int nos_overlay_yuv(const NosYuvSrc* dst, int h, int w, const int* count, const 
                                   font, thickness, scale, min_hits))
     return rc;
   YuvDst d{};
-  long long cw = 0, ch = 0;
-  if (yuv_format(*dst) || yuv_planes(*dst, 1, h, w, d.pl, cw, ch)) {
-    g_err = "overlay_yuv: the surface: " + g_err;
-    return -1;
-  }
-  d.layout = dst->layout, d.hsub = dst->hsub, d.vsub = dst->vsub, d.sb = dst->sample_bytes, d.shift = dst->shift;
-  d.order = dst->order;
+  if (const int rc = yuv_dst("overlay_yuv", d, *dst, h, w)) return rc;
   return overlay_launch(k, d, stream, "overlay_yuv");
+}
+
+int nos_mosaic_tile_rows() { return MTILE; }
+int nos_mosaic_tile_columns() { return MTILE; }
+
+// The detections of the labels select [L] (uint8, non-zero: pixelate) marks, pixelated in packed pixels img: every cell
+// of cell x cell pixels (4, 8, 16, 32 or 64, on the lattice from pixel (0, 0)) that a selected row's rectangle touches
+// gets, per colour byte, the rounded mean of its bytes inside the frame (image_mosaic.h). The image, the lists and the
+// checks are nos_overlay_packed's; nothing is launched unless every check passes, and no byte outside the marked cells'
+// colour bytes is written.
+int nos_mosaic_packed(void* img, const void* lo, const void* hi, long long pitch, const char* order, int h, int w,
+                      const int* count, const float* scores, const int* labels, const float* boxes,
+                      const int* track_id, const int* track_hits, int N, const void* select, int L, int min_hits,
+                      int cell, void* stream) {
+  if (!img || !order) return fail("mosaic: null operand");
+  MosaicArgs k{};
+  if (const int rc = mosaic_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits, cell))
+    return rc;
+  PackedDst dst{};
+  if (const int rc = packed_dst("mosaic_packed", dst, img, lo, hi, pitch, order, h, w)) return rc;
+  return mosaic_launch(k, dst, stream, "mosaic_packed");
+}
+
+// The same in the one h x w frame of any YUV surface NosYuvSrc describes, as nos_overlay_yuv takes it: per sample plane
+// the mean of the codes ((word >> shift) & (2^depth - 1) of a 16-bit sample) whose owner pixel lies in the cell, stored
+// to every one of them, 16-bit samples as whole words.
+int nos_mosaic_yuv(const NosYuvSrc* dst, int h, int w, const int* count, const float* scores, const int* labels,
+                   const float* boxes, const int* track_id, const int* track_hits, int N, const void* select, int L,
+                   int min_hits, int cell, void* stream) {
+  if (!dst) return fail("mosaic: null operand");
+  if (dst->size != int(sizeof(NosYuvSrc))) return fail("mosaic_yuv: descriptor size mismatch (NosYuvSrc of another build)");
+  MosaicArgs k{};
+  if (const int rc = mosaic_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits, cell))
+    return rc;
+  YuvDst d{};
+  if (const int rc = yuv_dst("mosaic_yuv", d, *dst, h, w)) return rc;
+  k.mask = (1 << dst->depth) - 1;
+  return mosaic_launch(k, d, stream, "mosaic_yuv");
 }
 
 }  // extern "C"

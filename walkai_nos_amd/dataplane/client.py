@@ -36,7 +36,9 @@ the capture, so the timed loop starts at frame 0; the JSON line then carries a `
 those of them seen in ``--track-min-hits`` frames), the ids issued, the births dropped for lack of a slot, the frames.
 ``--annotate`` draws the detections into the frame (``YolosSmall.annotate_image`` / ``annotate_tiled``, one more launch
 inside the captured graph; with ``--track`` the tags are the ids): boxes ``--annotate-thickness`` thick, tags of glyph
-dots ``--annotate-scale`` pixels large or none with ``--no-tags``, the labels of ``--redact L1,L2,...`` filled instead.
+dots ``--annotate-scale`` pixels large or none with ``--no-tags``, the labels of ``--redact L1,L2,...`` filled instead
+and those of ``--pixelate L1,L2,...`` pixelated (``ops.image.mosaic``, a launch before the drawing) in cells of
+``--pixelate-cell`` pixels (4, 8, 16, 32 or 64; by default by the frame's size). A label is redacted or pixelated.
 The client builds a second surface of the same layout over a second buffer; inside the graph the source buffer is
 copied there and painted there, so the synthetic frame stays the same from replay to replay. The JSON line then carries
 ``"annotate": {"changed_bytes": ...}``, the bytes of the second buffer that differ from the source, counted once on the
@@ -138,9 +140,12 @@ def main(argv=None) -> int:
     ap.add_argument("--annotate-scale", type=int, default=None,
                     help="--annotate: the pixels of a glyph's dot (default: the frame's shorter side / 360, at least 1)")
     ap.add_argument("--redact", default="", help="--annotate: L1,L2,... labels that are filled, not outlined")
+    ap.add_argument("--pixelate", default="", help="--annotate: L1,L2,... labels whose boxes are pixelated, not drawn")
+    ap.add_argument("--pixelate-cell", type=int, default=None,
+                    help="--pixelate: the side of a mosaic cell, 4, 8, 16, 32 or 64 pixels (default: by the frame's size)")
     ap.add_argument("--no-tags", action="store_true", help="--annotate: boxes without id tags")
     args = ap.parse_args(argv)
-    redact = ()
+    redact = pixelate = ()
     if args.annotate:
         if not args.end_to_end:
             ap.error("--annotate takes --end-to-end")
@@ -156,8 +161,20 @@ def main(argv=None) -> int:
             redact = (-1,)
         if any(not 0 <= v < 91 for v in redact):
             ap.error(f"--redact {args.redact!r} is not L1,L2,... with labels in 0..90")
-    elif args.annotate_thickness is not None or args.annotate_scale is not None or args.redact or args.no_tags:
-        ap.error("--annotate-thickness, --annotate-scale, --redact and --no-tags take --annotate")
+        try:
+            pixelate = tuple(int(v) for v in args.pixelate.split(",")) if args.pixelate else ()
+        except ValueError:
+            pixelate = (-1,)
+        if any(not 0 <= v < 91 for v in pixelate):
+            ap.error(f"--pixelate {args.pixelate!r} is not L1,L2,... with labels in 0..90")
+        if set(redact) & set(pixelate):
+            ap.error(f"--redact and --pixelate both name {sorted(set(redact) & set(pixelate))}: a label is one or the other")
+        if args.pixelate_cell is not None and (not pixelate or args.pixelate_cell not in (4, 8, 16, 32, 64)):
+            ap.error(f"--pixelate-cell {args.pixelate_cell} takes --pixelate and is 4, 8, 16, 32 or 64")
+    elif args.annotate_thickness is not None or args.annotate_scale is not None or args.redact or args.no_tags \
+            or args.pixelate or args.pixelate_cell is not None:
+        ap.error("--annotate-thickness, --annotate-scale, --redact, --pixelate, --pixelate-cell and --no-tags take "
+                 "--annotate")
     if args.track:
         if not args.end_to_end:
             ap.error("--track takes --end-to-end")
@@ -253,7 +270,7 @@ def main(argv=None) -> int:
             from ..models.workload.overlay import Overlay
             overlay = Overlay(thickness=args.annotate_thickness, scale=args.annotate_scale, tags=not args.no_tags,
                               redact=redact, min_hits=args.track_min_hits if args.track else 1,
-                              num_labels=model.c.num_labels)
+                              num_labels=model.c.num_labels, pixelate=pixelate, cell=args.pixelate_cell)
             painted = torch.empty_like(buf)     # a second surface of the same layout over a second buffer
             target = surface(painted)
 

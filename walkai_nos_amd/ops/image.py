@@ -74,6 +74,11 @@ which is also what runs on the CPU, with the ``torch`` backend and past a layout
   on the host in fp64. No RGB frame, no host sync, no copy; :func:`overlay_reference` is the torch composition. Alpha
   blending, antialiased lines, class names or any glyph but digits, PQ / HLG surfaces, batches above one and more than
   1024 rows are not offered.
+* :func:`mosaic` — the detections of selected labels pixelated in the frame's own planes by one launch, on the same
+  surfaces: every cell of a lattice of :data:`MOSAIC_CELLS` pixels that a selected box touches takes the rounded mean
+  of its samples, per sample plane, in exact integers. :func:`mosaic_cells` is the mask of marked cells and
+  :func:`mosaic_reference` the torch composition. Blur, other cell sizes, PQ / HLG surfaces, batches and cells
+  anchored to the box instead of the frame are not offered.
 """
 from __future__ import annotations
 
@@ -145,9 +150,15 @@ def _L() -> ctypes.CDLL:
             drawn = [vp] * 6 + [i32, vp, i32, vp, i32, vp, i32, i32, i32, vp]
             L.nos_overlay_packed.argtypes = [vp, vp, vp, i64, ctypes.c_char_p, i32, i32] + drawn
             L.nos_overlay_yuv.argtypes = [src, i32, i32] + drawn
+            # the lists and the parameters both mosaic entries take behind their surface
+            tiled = [vp] * 6 + [i32, vp, i32, i32, i32, vp]
+            L.nos_mosaic_packed.argtypes = [vp, vp, vp, i64, ctypes.c_char_p, i32, i32] + tiled
+            L.nos_mosaic_yuv.argtypes = [src, i32, i32] + tiled
             L.nos_image_last_error.restype = ctypes.c_char_p
             if (L.nos_overlay_tile_rows(), L.nos_overlay_tile_columns()) != OVERLAY_TILE:
                 raise NativeUnavailable(f"{LIB} was built with another overlay tile than ops/image.py expects")
+            if (L.nos_mosaic_tile_rows(), L.nos_mosaic_tile_columns()) != MOSAIC_TILE:
+                raise NativeUnavailable(f"{LIB} was built with another mosaic tile than ops/image.py expects")
             if (L.nos_image_taps(), L.nos_image_max_footprint(), L.nos_image_max_patch(),
                     L.nos_image_nv12_max_footprint(), L.nos_image_yuv420p_max_footprint(),
                     L.nos_image_packed_max_footprint(), L.nos_image_yuv_max_footprint()) != \
@@ -1843,15 +1854,8 @@ def _overlay_font(device: torch.device) -> torch.Tensor:
     return _overlay_table("font", OVERLAY_FONT, device)
 
 
-def _overlay_check(surface: OverlaySurface, count, scores, labels, boxes, track_id, track_hits, thickness, scale, modes,
-                   min_hits, codes) -> tuple:
-    """The arguments of :func:`overlay` checked, ``ValueError`` before any launch; the lists as ``count [1]``,
-    ``scores [N]``, ``labels [N]``, ``boxes [N, 4]``, ids and hits ``[N]`` or None (``[1, N]`` views are flattened)."""
-    who = "overlay"
-    if not 1 <= int(thickness) <= OVERLAY_MAX_THICKNESS:
-        raise ValueError(f"{who}: thickness {thickness!r} is not in 1..{OVERLAY_MAX_THICKNESS}")
-    if not 0 <= int(scale) <= OVERLAY_MAX_SCALE:
-        raise ValueError(f"{who}: scale {scale!r} is not in 0..{OVERLAY_MAX_SCALE} (0: no tags)")
+def _overlay_lists(who: str, count, scores, labels, boxes, track_id, track_hits, min_hits) -> tuple:
+    """What :func:`overlay` and :func:`mosaic` check of one frame's lists and of ``min_hits``; the lists flattened."""
     if not int(min_hits) >= 1:
         raise ValueError(f"{who}: min_hits {min_hits!r} is not a number of frames from 1 up")
     if (track_id is None) != (track_hits is None):
@@ -1871,6 +1875,20 @@ def _overlay_check(surface: OverlaySurface, count, scores, labels, boxes, track_
             or count.dtype not in ints or (track_id is not None and (track_id.dtype not in ints
                                                                     or track_hits.dtype not in ints)):
         raise ValueError(f"{who}: floating-point scores and boxes, int32 or int64 count, labels, ids and hits")
+    return count, scores, labels, boxes, track_id, track_hits
+
+
+def _overlay_check(surface: OverlaySurface, count, scores, labels, boxes, track_id, track_hits, thickness, scale, modes,
+                   min_hits, codes) -> tuple:
+    """The arguments of :func:`overlay` checked, ``ValueError`` before any launch; the lists as ``count [1]``,
+    ``scores [N]``, ``labels [N]``, ``boxes [N, 4]``, ids and hits ``[N]`` or None (``[1, N]`` views are flattened)."""
+    who = "overlay"
+    if not 1 <= int(thickness) <= OVERLAY_MAX_THICKNESS:
+        raise ValueError(f"{who}: thickness {thickness!r} is not in 1..{OVERLAY_MAX_THICKNESS}")
+    if not 0 <= int(scale) <= OVERLAY_MAX_SCALE:
+        raise ValueError(f"{who}: scale {scale!r} is not in 0..{OVERLAY_MAX_SCALE} (0: no tags)")
+    count, scores, labels, boxes, track_id, track_hits = _overlay_lists(who, count, scores, labels, boxes, track_id,
+                                                                        track_hits, min_hits)
     if not isinstance(modes, torch.Tensor) or modes.dtype != torch.uint8 or modes.dim() != 1 or modes.numel() < 1:
         raise ValueError(f"{who}: modes is a uint8 [L] tensor of 0 (not drawn), 1 (outline and tag), 2 (redacted)")
     if not isinstance(codes, torch.Tensor) or codes.dtype != torch.int32 or codes.dim() != 2 or codes.shape[1] != 3 \
@@ -2018,4 +2036,150 @@ def overlay(target, count: torch.Tensor, scores: torch.Tensor, labels: torch.Ten
         src = yuv_src(*surface.yuv, (0,) * 12)
         rc = _L().nos_overlay_yuv(ctypes.byref(src), surface.h, surface.w, *tail)
     _check(rc, "overlay")
+    return target
+
+
+# ---- detections pixelated in the frame -----------------------------------------------------------------
+#: the sides of a mosaic cell in luma pixels, and the kernel's tile (``csrc/image_mosaic.h``): every cell divides it
+MOSAIC_CELLS = (4, 8, 16, 32, 64)
+MOSAIC_TILE = (64, 64)
+
+
+def _mosaic_check(surface: OverlaySurface, count, scores, labels, boxes, track_id, track_hits, min_hits, select,
+                  cell) -> tuple:
+    """The arguments of :func:`mosaic` checked, ``ValueError`` before any launch; the lists as :func:`_overlay_check`
+    returns them."""
+    who = "mosaic"
+    if cell not in MOSAIC_CELLS:
+        raise ValueError(f"{who}: cell {cell!r} is none of {MOSAIC_CELLS}")
+    lists = _overlay_lists(who, count, scores, labels, boxes, track_id, track_hits, min_hits)
+    if not isinstance(select, torch.Tensor) or select.dtype != torch.uint8 or select.dim() != 1 or select.numel() < 1:
+        raise ValueError(f"{who}: select is a uint8 [L] tensor, non-zero where a label is pixelated")
+    for name, t in zip(("count", "scores", "labels", "boxes", "track_id", "track_hits", "select"), lists + (select,)):
+        if t is not None and t.device != surface.device:
+            raise ValueError(f"{who}: the target is on {surface.device}, {name} on {t.device}")
+    return (lists[0].reshape(1),) + lists[1:]
+
+
+def mosaic_cells(h: int, w: int, count, scores, labels, boxes, track_id, track_hits, min_hits: int,
+                 select: torch.Tensor, cell: int) -> torch.Tensor:
+    """Rules 1 and 2 of :func:`mosaic` on the lists' device, without a host sync and without a loop over the rows: bool
+    ``[ceil(h / cell), ceil(w / cell)]``, the marked cells. A selected row's rectangle, clipped to the frame, spans a
+    range of cell rows and one of cell columns; the mask is where the sum over rows of their outer product is not 0."""
+    dev, N, cell = scores.device, scores.shape[0], int(cell)
+    L = select.shape[0]
+    lb = labels.to(torch.int64)
+    chosen = (lb >= 0) & (lb < L) & (select[lb.clamp(0, L - 1)] != 0)
+    bx = boxes.to(torch.float32)
+    finite = torch.isfinite(bx).all(dim=1)
+    c = torch.where(finite[:, None], bx, 0.0).clamp(-OVERLAY_CLAMP, OVERLAY_CLAMP)
+    x0, y0 = torch.floor(c[:, 0]).to(torch.int32), torch.floor(c[:, 1]).to(torch.int32)
+    x1, y1 = torch.ceil(c[:, 2]).to(torch.int32) - 1, torch.ceil(c[:, 3]).to(torch.int32) - 1
+    n = count.reshape(1)[0].clamp(0, N)
+    ok = (torch.arange(N, device=dev) < n) & (scores.to(torch.float32) > 0) & chosen & finite & (x1 >= x0) & (y1 >= y0)
+    if track_id is not None:
+        ok = ok & (track_id > 0) & (track_hits >= int(min_hits))
+    x0, y0, x1, y1 = x0.clamp(min=0), y0.clamp(min=0), x1.clamp(max=w - 1), y1.clamp(max=h - 1)
+    ok = ok & (x1 >= x0) & (y1 >= y0)
+    ci = torch.arange(-(-h // cell), device=dev, dtype=torch.int32)[None, :]
+    cj = torch.arange(-(-w // cell), device=dev, dtype=torch.int32)[None, :]
+    rows = ok[:, None] & (ci >= torch.div(y0, cell, rounding_mode="floor")[:, None]) \
+        & (ci <= torch.div(y1, cell, rounding_mode="floor")[:, None])
+    cols = (cj >= torch.div(x0, cell, rounding_mode="floor")[:, None]) \
+        & (cj <= torch.div(x1, cell, rounding_mode="floor")[:, None])
+    return (rows.to(torch.float32).t() @ cols.to(torch.float32)) > 0       # (counts up to N: exact in fp32)
+
+
+def mosaic_reference(target, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor,
+                     track_id: Optional[torch.Tensor] = None, track_hits: Optional[torch.Tensor] = None, *,
+                     min_hits: int = 1, select: torch.Tensor, cell: int):
+    """The torch composition of :func:`mosaic`, with the same effect on ``target`` in place and without a host sync:
+    :func:`mosaic_cells`, then per sample plane the codes and as many ones padded to whole cells, summed per cell by a
+    reshape, ``m = (sum + n // 2) // n`` spread back over the cell and stored through the plane's strided view where the
+    cell is marked."""
+    surface = overlay_surface(target)
+    lists = _mosaic_check(surface, count, scores, labels, boxes, track_id, track_hits, min_hits, select, cell)
+    if lists[1].shape[0] == 0:
+        return target
+    cell = int(cell)
+    marked = mosaic_cells(surface.h, surface.w, *lists, min_hits, select, cell)
+    depth = 8 if surface.yuv is None else surface.yuv[3]
+    for view, _, hs, vs in surface.samples:
+        if view.dtype == torch.uint8:
+            bits, codes = view, view.to(torch.int32)
+        else:       # 16-bit words: the same bits as int16, read as yuv_codes does
+            bits = view if view.dtype == torch.int16 else view.view(torch.int16)
+            codes = ((bits.to(torch.int32) & 0xffff) >> surface.shift) & ((1 << depth) - 1)
+        ph, pw = codes.shape
+        cv, cw = cell >> vs, cell >> hs
+        gi, gj = marked.shape
+        pad = (0, gj * cw - pw, 0, gi * cv - ph)
+        total = F.pad(codes, pad).reshape(gi, cv, gj, cw).sum(dim=(1, 3))
+        n = F.pad(torch.ones_like(codes), pad).reshape(gi, cv, gj, cw).sum(dim=(1, 3))
+        m = torch.div(total + torch.div(n, 2, rounding_mode="floor"), n, rounding_mode="floor") << surface.shift
+        spread = lambda t: t.repeat_interleave(cv, dim=0).repeat_interleave(cw, dim=1)[:ph, :pw]     # noqa: E731
+        m, on = spread(m), spread(marked)
+        if view.dtype == torch.uint8:
+            bits.copy_(torch.where(on, m.to(torch.uint8), bits))
+        else:
+            bits.copy_(torch.where(on, ((m + 32768) % 65536 - 32768).to(torch.int16), bits))
+    return target
+
+
+def mosaic(target, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor,
+           track_id: Optional[torch.Tensor] = None, track_hits: Optional[torch.Tensor] = None, *, min_hits: int = 1,
+           select: torch.Tensor, cell: int):
+    """One frame's detections — the lists :func:`overlay` takes, and optionally ``track_id``, ``track_hits`` —
+    pixelated in ``target`` (:func:`overlay_surface`: SDR, one frame) in place, with no host synchronisation, no RGB
+    frame and no copy; returns ``target``. ``select``: uint8 ``[L]`` on the device, non-zero where a label is
+    pixelated; ``cell``: one of :data:`MOSAIC_CELLS`, the side of a cell in luma pixels. The rule, in exact integers:
+
+    1. Row ``r`` is selected exactly as rule 1 of :func:`overlay` draws a row, with ``select[labels[r]] != 0`` in place
+       of the mode: ``r < clamp(count, 0, N)``, ``scores[r] > 0`` (a NaN is not), ``0 <= labels[r] < L``, all four
+       coordinates finite, with ids ``track_id[r] > 0`` and ``track_hits[r] >= min_hits``, and its rectangle not empty.
+       The rectangle is :func:`overlay`'s rule 2: each coordinate clamped in fp32 to ``[-2^20, 2^20]``, columns
+       ``floor(x0) .. ceil(x1) - 1`` and rows ``floor(y0) .. ceil(y1) - 1``, inclusive.
+    2. Cells lie on a lattice anchored at the frame's pixel (0, 0): cell ``(i, j)`` covers rows ``i cell .. min((i + 1)
+       cell, h) - 1`` and the columns likewise. A cell is marked when the rectangle of some selected row, clipped to
+       the frame, shares at least one pixel with it. Marked cells are pixelated whole: the painted region is the union
+       of the cells a box touches, never part of a cell.
+    3. For each marked cell and each sample plane of the surface (``OverlaySurface.samples`` with their ``hsub`` /
+       ``vsub``): the cell's samples are those whose owning luma pixel ``(cy << vsub, cx << hsub)`` lies in the cell,
+       ``n`` their number (smaller in clipped edge cells), a sample's code what :func:`yuv_codes` reads (the byte, or
+       ``(word >> shift) & mask`` of a 16-bit word), ``m = (sum + n // 2) // n``, and every one of those samples is
+       stored as ``m`` (a 16-bit word whole, as ``m << shift``). Packed pixels: each of the three colour bytes gets its
+       own mean; a fourth byte reaches no result and is never written.
+    4. No other byte is written: not the unmarked cells, not the pitch padding, not the parent of a crop. Applying the
+       rule twice changes nothing the second time.
+
+    ``cell`` is even and ``cell >> hsub >= 2``, so a chroma cell lies exactly under its luma cell on 4:2:0 and 4:2:2 and
+    a YUY2 macropixel never straddles two cells.
+
+    One HIP launch (a workgroup per :data:`MOSAIC_TILE` of luma pixels, ``mosaic_k``) for fp32 / int32 lists up to 1024
+    rows on the GPU; past that, for other dtypes, on the CPU and with the ``torch`` backend :func:`mosaic_reference`.
+    Blur, cells of other sizes, PQ / HLG surfaces, batches above one and cells anchored to the box instead of the frame
+    are not offered."""
+    surface = overlay_surface(target)
+    lists = _mosaic_check(surface, count, scores, labels, boxes, track_id, track_hits, min_hits, select, cell)
+    count, scores, labels, boxes, track_id, track_hits = lists
+    N = scores.shape[0]
+    i32 = torch.int32
+    if not _use_hip(scores) or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or labels.dtype != i32 \
+            or count.dtype != i32 or (track_id is not None and (track_id.dtype != i32 or track_hits.dtype != i32)) \
+            or N > MAX_ROWS or N < 1:
+        return mosaic_reference(target, *lists, min_hits=min_hits, select=select, cell=cell)
+    scores, labels, boxes, select = scores.contiguous(), labels.contiguous(), boxes.contiguous(), select.contiguous()
+    ids = (None, None) if track_id is None else (track_id.contiguous(), track_hits.contiguous())
+    tail = (count.data_ptr(), scores.data_ptr(), labels.data_ptr(), boxes.data_ptr(),
+            None if ids[0] is None else ids[0].data_ptr(), None if ids[1] is None else ids[1].data_ptr(), N,
+            select.data_ptr(), select.shape[0], int(min_hits), int(cell), torch.cuda.current_stream().cuda_stream)
+    if surface.packed is not None:
+        data, order = surface.packed
+        lo, hi = _storage_bounds(data)
+        pitch = data.stride(1) if data.shape[1] > 1 else data.shape[2] * data.shape[3]
+        rc = _L().nos_mosaic_packed(data.data_ptr(), lo, hi, pitch, order.encode(), surface.h, surface.w, *tail)
+    else:
+        src = yuv_src(*surface.yuv, (0,) * 12)
+        rc = _L().nos_mosaic_yuv(ctypes.byref(src), surface.h, surface.w, *tail)
+    _check(rc, "mosaic")
     return target
