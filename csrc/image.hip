@@ -19,6 +19,8 @@
 //    that writes a surface.
 //  * Pixelating (image_mosaic.h): mosaic_k, the cells a selected detection touches replaced by their mean, in place —
 //    the one kernel here that reads a surface and writes it.
+//  * Blurring (image_blur.h): blur_snapshot_k and blur_k, the detections of selected labels blurred in place through a
+//    shadow copy of what a blur can read: two launches, no traffic between workgroups.
 //  * Entries. The extern "C" functions at the end check every argument of an outside caller, fill the kernel's
 //    arguments and launch; the arguments all image entries share travel as one struct (Common).
 #include <hip/hip_runtime.h>
@@ -34,6 +36,7 @@
 #include "image_stage.h"
 #include "image_overlay.h"
 #include "image_mosaic.h"
+#include "image_blur.h"
 #include "image_yuv.h"
 
 namespace {
@@ -608,6 +611,61 @@ int yuv_dst(const char* who, YuvDst& d, const NosYuvSrc& s, int h, int w) {
   d.layout = s.layout, d.hsub = s.hsub, d.vsub = s.vsub, d.sb = s.sample_bytes, d.shift = s.shift, d.order = s.order;
   return 0;
 }
+// The rows and the row bytes of the np planes of a YUV surface of h x w whose format is known (yuv_planes' own).
+int yuv_plane_sizes(const NosYuvSrc& s, int h, int w, long long* rows, long long* rowbytes) {
+  const long long SB = s.sample_bytes, cw = (w + (1LL << s.hsub) - 1) >> s.hsub, ch = (h + (1LL << s.vsub) - 1) >> s.vsub;
+  const bool packed = s.layout == YUV_PACKED;
+  rows[0] = h, rows[1] = rows[2] = ch;
+  rowbytes[0] = packed ? 4 * ((w + 1LL) / 2) : w * SB, rowbytes[1] = s.layout == YUV_SEMI ? 2 * cw * SB : cw * SB;
+  rowbytes[2] = cw * SB;
+  return packed ? 1 : s.layout == YUV_SEMI ? 2 : 3;
+}
+
+// The shadow of np planes (image_blur.h): plane i lies behind plane i - 1 at its own pitch, at its own address modulo
+// 4. Returns the bytes a shadow needs at most; with a shadow, fills out[i].p (the rest of out[i] is pl[i]'s).
+long long blur_shadow(const PlaneArg* pl, const long long* rows, const long long* rowbytes, int np, void* shadow,
+                      PlaneArg* out) {
+  long long at = 0;
+  for (int i = 0; i < np; ++i) {
+    if (shadow) {
+      uint8_t* q = static_cast<uint8_t*>(shadow) + at;
+      q += (reinterpret_cast<uintptr_t>(pl[i].p) - reinterpret_cast<uintptr_t>(q)) & 3;
+      out[i] = pl[i], out[i].p = q;
+    }
+    at += (rows[i] - 1) * pl[i].pitch + rowbytes[i] + 4;
+  }
+  return at;
+}
+
+// The rows of a band (image_blur.h) at `radius` with partials of pb bytes: 64 where the codes and partials of 64 rows
+// fit BLUR_BAND_LDS, else 32.
+constexpr int BLUR_BAND_LDS = 48 << 10;
+int blur_band(int radius, int pb) { return blur_lds(BTILE, radius, radius, pb) <= BLUR_BAND_LDS ? BTILE : BTILE / 2; }
+
+// What both blur entries check and fill of k (mask and band are filled by the entry).
+int blur_args(BlurArgs& k, int h, int w, const int* count, const float* scores, const int* labels, const float* boxes,
+              const int* track_id, const int* track_hits, int N, const void* select, int L, int min_hits, int radius,
+              const void* taps, const void* shadow) {
+  if (radius < 1 || radius > BLUR_MAX_RADIUS) return fail("blur: a radius of 1..32 pixels");
+  if (const int rc = list_args("blur", h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits))
+    return rc;
+  if (!taps || !shadow) return fail("blur: null operand");
+  k.m = MosaicArgs{count, scores, labels, boxes, track_id, track_hits, static_cast<const uint8_t*>(select), N, L, min_hits,
+                   h, w, 0, 255};
+  k.taps = static_cast<const int16_t*>(taps), k.radius = radius, k.band = blur_band(radius, 2);
+  return 0;
+}
+
+// blur_snapshot_k, then blur_k, each on one workgroup per tile of the h x w frame
+template <class Dst>
+int blur_launch(const BlurArgs& k, const Dst& dst, const Dst& shadow, int pb, void* stream, const char* what) {
+  const int grid = ((k.m.h + BTILE - 1) / BTILE) * ((k.m.w + BTILE - 1) / BTILE);
+  hipLaunchKernelGGL(blur_snapshot_k<Dst>, dim3(grid), dim3(BT), 0, reinterpret_cast<hipStream_t>(stream), k, dst, shadow);
+  if (const int rc = check(what)) return rc;
+  hipLaunchKernelGGL(blur_k<Dst>, dim3(grid), dim3(BT), blur_lds(k.band, k.radius, k.radius, pb),
+                     reinterpret_cast<hipStream_t>(stream), k, dst, shadow);
+  return check(what);
+}
 }  // namespace
 
 extern "C" {
@@ -971,6 +1029,77 @@ int nos_mosaic_yuv(const NosYuvSrc* dst, int h, int w, const int* count, const f
   if (const int rc = yuv_dst("mosaic_yuv", d, *dst, h, w)) return rc;
   k.mask = (1 << dst->depth) - 1;
   return mosaic_launch(k, d, stream, "mosaic_yuv");
+}
+
+int nos_blur_max_radius() { return BLUR_MAX_RADIUS; }
+
+// The bytes of the shadow nos_blur_packed takes for an image of h x w pixels of the order's bytes at `pitch`; -1 for an
+// unknown order or a pitch below a row's bytes.
+long long nos_blur_shadow_packed(long long pitch, const char* order, int h, int w) {
+  PackedArgs o{};
+  const int C = order ? packed_order(order, o) : 0;
+  if (!C || h <= 0 || w <= 0 || pitch < (long long)w * C) return fail("blur_packed: the shadow of an unknown image");
+  const PlaneArg pl = plane_arg(nullptr, nullptr, nullptr, pitch, 0);
+  const long long rows = h, rowbytes = (long long)w * C;
+  return blur_shadow(&pl, &rows, &rowbytes, 1, nullptr, nullptr);
+}
+
+// The same for the surface nos_blur_yuv takes.
+long long nos_blur_shadow_yuv(const NosYuvSrc* dst, int h, int w) {
+  if (!dst || dst->size != int(sizeof(NosYuvSrc))) return fail("blur_yuv: descriptor size mismatch (NosYuvSrc of another build)");
+  YuvDst d{};
+  if (const int rc = yuv_dst("blur_yuv", d, *dst, h, w)) return rc;
+  long long rows[3], rowbytes[3];
+  const int np = yuv_plane_sizes(*dst, h, w, rows, rowbytes);
+  return blur_shadow(d.pl, rows, rowbytes, np, nullptr, nullptr);
+}
+
+// The detections of the labels select [L] (uint8, non-zero: blur) marks, blurred in packed pixels img: every pixel of a
+// selected row's rectangle gets, per colour byte, the separable Gaussian of integer taps (taps: int16 [2][65] on the
+// device, the taps of `radius` and of radius >> 1, each summing to 256) over the bytes the image held before the call,
+// indices clamped at its edges (image_blur.h). shadow: shadow_bytes >= nos_blur_shadow_packed's of device memory the
+// call may overwrite. The image, the lists and the checks are nos_mosaic_packed's; nothing is launched unless every
+// check passes, and no byte outside the painted pixels' colour bytes is written.
+int nos_blur_packed(void* img, const void* lo, const void* hi, long long pitch, const char* order, int h, int w,
+                    const int* count, const float* scores, const int* labels, const float* boxes, const int* track_id,
+                    const int* track_hits, int N, const void* select, int L, int min_hits, int radius, const void* taps,
+                    void* shadow, long long shadow_bytes, void* stream) {
+  if (!img || !order) return fail("blur: null operand");
+  BlurArgs k{};
+  if (const int rc = blur_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits,
+                               radius, taps, shadow))
+    return rc;
+  PackedDst dst{};
+  if (const int rc = packed_dst("blur_packed", dst, img, lo, hi, pitch, order, h, w)) return rc;
+  const long long rows = h, rowbytes = (long long)w * dst.C;
+  PackedDst sh = dst;
+  if (blur_shadow(&dst.s, &rows, &rowbytes, 1, shadow, &sh.s) > shadow_bytes)
+    return fail("blur_packed: the shadow is smaller than nos_blur_shadow_packed asks");
+  return blur_launch(k, dst, sh, 2, stream, "blur_packed");
+}
+
+// The same in the one h x w frame of any YUV surface NosYuvSrc describes, as nos_mosaic_yuv takes it: per sample plane
+// the codes ((word >> shift) & (2^depth - 1) of a 16-bit sample) blurred at the plane's own resolution with the taps of
+// radius >> hsub and radius >> vsub, stored where the sample's owner pixel is painted, 16-bit samples as whole words.
+int nos_blur_yuv(const NosYuvSrc* dst, int h, int w, const int* count, const float* scores, const int* labels,
+                 const float* boxes, const int* track_id, const int* track_hits, int N, const void* select, int L,
+                 int min_hits, int radius, const void* taps, void* shadow, long long shadow_bytes, void* stream) {
+  if (!dst) return fail("blur: null operand");
+  if (dst->size != int(sizeof(NosYuvSrc))) return fail("blur_yuv: descriptor size mismatch (NosYuvSrc of another build)");
+  BlurArgs k{};
+  if (const int rc = blur_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits,
+                               radius, taps, shadow))
+    return rc;
+  YuvDst d{};
+  if (const int rc = yuv_dst("blur_yuv", d, *dst, h, w)) return rc;
+  long long rows[3], rowbytes[3];
+  const int np = yuv_plane_sizes(*dst, h, w, rows, rowbytes);
+  YuvDst sh = d;
+  if (blur_shadow(d.pl, rows, rowbytes, np, shadow, sh.pl) > shadow_bytes)
+    return fail("blur_yuv: the shadow is smaller than nos_blur_shadow_yuv asks");
+  const int pb = dst->sample_bytes == 2 ? 4 : 2;
+  k.m.mask = (1 << dst->depth) - 1, k.band = blur_band(radius, pb);
+  return blur_launch(k, d, sh, pb, stream, "blur_yuv");
 }
 
 }  // extern "C"

@@ -55,6 +55,13 @@ overlay rows' method: ``ops.image.mosaic`` (``*_hip_us``) against ``mosaic_refer
 ``ops.image.overlay`` filling the same rows (``*_fill_us``: what a redaction costs that reads nothing), the frame restored
 from a saved copy inside the timed graph on all sides (``*_restore_us``). On the whole GPU
 ``mosaic_annotate_image_pixelate_thr0_ms`` stands beside ``mosaic_annotate_image_redact_thr0_ms``.
+
+Four rows time the blur (``--rows blur`` runs them alone): ``blur_n100_1080p_nv12_*`` and ``blur_n400_2160p_nv12_*``,
+``_rgb_*``, ``_p010_*``, the same scene at ``Overlay``'s default radius, by the mosaic rows' method: ``ops.image.blur``
+(``*_hip_us``: the snapshot and the blur launch) against ``blur_reference`` (``*_torch_us``) and against
+``ops.image.mosaic`` of the same rows at the default cell (``*_mosaic_us``: the price of the halo and of the second
+launch), the frame restored inside the timed graph on all sides (``*_restore_us``). On the whole GPU
+``blur_annotate_image_blur_thr0_ms`` stands beside ``blur_annotate_image_pixelate_thr0_ms``.
 """
 from __future__ import annotations
 
@@ -103,8 +110,9 @@ def main() -> int:
     ap.add_argument("--out", default="gpurun_out/kbench.json")
     ap.add_argument("--only", choices=("all", "attn", "gemm", "model", "modes", "image"), default="all")
     ap.add_argument("--slices", default="spx,dpx,qpx,cpx")
-    ap.add_argument("--rows", choices=("all", "tiles", "track", "overlay", "mosaic"), default="all",
-                    help="image: every row, or the tiled-detection rows alone, or the tracker's, the overlay's or the mosaic's")
+    ap.add_argument("--rows", choices=("all", "tiles", "track", "overlay", "mosaic", "blur"), default="all",
+                    help="image: every row, or the tiled-detection rows alone, or the tracker's, the overlay's, the "
+                         "mosaic's or the blur's")
     ap.add_argument("--partitions", type=int, default=0, help="modes: run only this many partitions of each mode")
     ap.add_argument("--free-s", type=float, default=0.0,
                     help="modes: serve free-running (one thread per pod, as the bench) for this many seconds "
@@ -383,6 +391,8 @@ def image_bench(a) -> int:
                 overlay_rows(r, s, a.iters, rounds, whole_gpu=cus is None)
             if a.rows in ("all", "mosaic"):
                 mosaic_rows(r, s, a.iters, rounds, whole_gpu=cus is None)
+            if a.rows in ("all", "blur"):
+                blur_rows(r, s, a.iters, rounds, whole_gpu=cus is None)
             if not full:
                 print(json.dumps(r), flush=True)
                 results.append(r)
@@ -752,6 +762,76 @@ def mosaic_rows(r, s, iters, rounds, whole_gpu):
     for k, vs in t.items():
         r[f"mosaic_annotate_image_{k}_thr0_ms"] = round(statistics.median(vs) / 1000.0, 3)
     r["mosaic_model_rounds_ms"] = {k: [round(v / 1000.0, 3) for v in vs] for k, vs in t.items()}
+
+
+def blur_rows(r, s, iters, rounds, whole_gpu):
+    """The blur (see the module docstring): ``blur_*_hip_us`` against ``*_torch_us`` and ``*_mosaic_us``, all with the
+    restore of the frame that ``*_restore_us`` times alone; ``*_scene`` says what was blurred."""
+    import statistics
+
+    from walkai_nos_amd.models.workload import surfaces
+    from walkai_nos_amd.models.workload.overlay import Overlay
+    from walkai_nos_amd.models.workload.processor import Nv12
+    from walkai_nos_amd.models.workload.yolos import YolosSmall
+    from walkai_nos_amd.ops import image as I
+    g = torch.Generator().manual_seed(5)
+    for name, n, h, w, fmt in (("n100_1080p_nv12", 100, 1080, 1920, "nv12"), ("n400_2160p_nv12", 400, 2160, 3840, "nv12"),
+                               ("n400_2160p_rgb", 400, 2160, 3840, "rgb"), ("n400_2160p_p010", 400, 2160, 3840, "p010")):
+        if fmt == "rgb":
+            buf = torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8).cuda()
+            frame = buf
+        else:
+            pitch = -(-w * (2 if fmt == "p010" else 1) // 256) * 256
+            buf = torch.randint(0, 256, (pitch * h * 3 // 2,), generator=g, dtype=torch.uint8).cuda()
+            frame = Nv12.from_buffer(buf, h, w, pitch) if fmt == "nv12" else surfaces.from_buffer(fmt, buf, h, w, pitch)
+        saved = buf.clone()
+        lists, modes = overlay_scene(n, h, w, redact=True)
+        lists = [t.cuda() for t in lists]
+        select = (modes == 2).to(torch.uint8).cuda()        # the redacted labels, a quarter of the rows
+        ov = Overlay(blur=(0,), pixelate=(1,))
+        radius, cell = ov.radius_size(h, w), ov.cell_size(h, w)
+        calls = {"hip": lambda: I.blur(frame, *lists, select=select, radius=radius),
+                 "torch": lambda: I.blur_reference(frame, *lists, select=select, radius=radius),
+                 "mosaic": lambda: I.mosaic(frame, *lists, select=select, cell=cell),
+                 "restore": lambda: None}
+
+        def run(k):
+            buf.copy_(saved)
+            return calls[k]()
+        with torch.cuda.stream(s):
+            run("hip")
+            a = buf.clone()
+            run("torch")
+            same = torch.equal(a, buf)
+            painted = int(I.mosaic_cells(h, w, *lists, 1, select, 1).sum())
+            s.synchronize()
+        t = {k: [] for k in calls}
+        for _ in range(rounds):
+            for k in calls:
+                t[k].append(timeit(lambda: run(k), s, iters if k != "torch" else max(2, iters // 5)))
+        for k, vs in t.items():
+            r[f"blur_{name}_{k}_us"] = round(statistics.median(vs), 1)
+        r[f"blur_{name}_rounds_us"] = {k: [round(v, 1) for v in vs] for k, vs in t.items()}
+        print(f"[kbench] blur_{name}: hip {t['hip']} torch {t['torch']} mosaic {t['mosaic']} us", file=sys.stderr, flush=True)
+        r[f"blur_{name}_scene"] = {"rows": n, "selected": n // 4, "frame": [h, w], "radius": radius, "cell": cell,
+                                   "painted_pixels": painted, "frame_bytes": int(buf.numel()),
+                                   "hip_equals_torch": bool(same)}
+    if not whole_gpu:
+        return
+    small = torch.randint(0, 256, (480, 640, 3), generator=g, dtype=torch.uint8).cuda()
+    out = torch.empty_like(small)
+    with torch.cuda.stream(s), torch.no_grad():
+        m = YolosSmall().cuda().eval()
+        third = tuple(range(0, 91, 3))
+        ov = {"blur": Overlay(blur=third), "pixelate": Overlay(pixelate=third)}
+        t = {k: [] for k in ov}
+        for _ in range(rounds):
+            for k in ov:
+                t[k].append(timeit(lambda: m.annotate_image(small, ov[k], 0.0, None, out), s, max(2, iters // 5)))
+        s.synchronize()
+    for k, vs in t.items():
+        r[f"blur_annotate_image_{k}_thr0_ms"] = round(statistics.median(vs) / 1000.0, 3)
+    r["blur_model_rounds_ms"] = {k: [round(v / 1000.0, 3) for v in vs] for k, vs in t.items()}
 
 
 def free_running(slots, seconds: float) -> int:

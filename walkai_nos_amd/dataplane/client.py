@@ -38,7 +38,9 @@ those of them seen in ``--track-min-hits`` frames), the ids issued, the births d
 inside the captured graph; with ``--track`` the tags are the ids): boxes ``--annotate-thickness`` thick, tags of glyph
 dots ``--annotate-scale`` pixels large or none with ``--no-tags``, the labels of ``--redact L1,L2,...`` filled instead
 and those of ``--pixelate L1,L2,...`` pixelated (``ops.image.mosaic``, a launch before the drawing) in cells of
-``--pixelate-cell`` pixels (4, 8, 16, 32 or 64; by default by the frame's size). A label is redacted or pixelated.
+``--pixelate-cell`` pixels (4, 8, 16, 32 or 64; by default by the frame's size), those of ``--blur L1,L2,...`` blurred
+(``ops.image.blur``, behind the mosaic) at ``--blur-radius`` pixels (1..32; by default by the frame's size). A label is
+redacted, pixelated or blurred, exactly one.
 The client builds a second surface of the same layout over a second buffer; inside the graph the source buffer is
 copied there and painted there, so the synthetic frame stays the same from replay to replay. The JSON line then carries
 ``"annotate": {"changed_bytes": ...}``, the bytes of the second buffer that differ from the source, counted once on the
@@ -143,9 +145,12 @@ def main(argv=None) -> int:
     ap.add_argument("--pixelate", default="", help="--annotate: L1,L2,... labels whose boxes are pixelated, not drawn")
     ap.add_argument("--pixelate-cell", type=int, default=None,
                     help="--pixelate: the side of a mosaic cell, 4, 8, 16, 32 or 64 pixels (default: by the frame's size)")
+    ap.add_argument("--blur", default="", help="--annotate: L1,L2,... labels whose boxes are blurred, not drawn")
+    ap.add_argument("--blur-radius", type=int, default=None,
+                    help="--blur: the radius of the Gaussian in pixels, 1..32 (default: by the frame's size)")
     ap.add_argument("--no-tags", action="store_true", help="--annotate: boxes without id tags")
     args = ap.parse_args(argv)
-    redact = pixelate = ()
+    redact = pixelate = blur = ()
     if args.annotate:
         if not args.end_to_end:
             ap.error("--annotate takes --end-to-end")
@@ -171,10 +176,21 @@ def main(argv=None) -> int:
             ap.error(f"--redact and --pixelate both name {sorted(set(redact) & set(pixelate))}: a label is one or the other")
         if args.pixelate_cell is not None and (not pixelate or args.pixelate_cell not in (4, 8, 16, 32, 64)):
             ap.error(f"--pixelate-cell {args.pixelate_cell} takes --pixelate and is 4, 8, 16, 32 or 64")
+        try:
+            blur = tuple(int(v) for v in args.blur.split(",")) if args.blur else ()
+        except ValueError:
+            blur = (-1,)
+        if any(not 0 <= v < 91 for v in blur):
+            ap.error(f"--blur {args.blur!r} is not L1,L2,... with labels in 0..90")
+        if set(blur) & (set(redact) | set(pixelate)):
+            ap.error(f"--blur and --redact or --pixelate both name {sorted(set(blur) & (set(redact) | set(pixelate)))}: "
+                     "a label is redacted, pixelated or blurred, exactly one")
+        if args.blur_radius is not None and (not blur or not 1 <= args.blur_radius <= 32):
+            ap.error(f"--blur-radius {args.blur_radius} takes --blur and is 1..32")
     elif args.annotate_thickness is not None or args.annotate_scale is not None or args.redact or args.no_tags \
-            or args.pixelate or args.pixelate_cell is not None:
-        ap.error("--annotate-thickness, --annotate-scale, --redact, --pixelate, --pixelate-cell and --no-tags take "
-                 "--annotate")
+            or args.pixelate or args.pixelate_cell is not None or args.blur or args.blur_radius is not None:
+        ap.error("--annotate-thickness, --annotate-scale, --redact, --pixelate, --pixelate-cell, --blur, --blur-radius "
+                 "and --no-tags take --annotate")
     if args.track:
         if not args.end_to_end:
             ap.error("--track takes --end-to-end")
@@ -270,7 +286,8 @@ def main(argv=None) -> int:
             from ..models.workload.overlay import Overlay
             overlay = Overlay(thickness=args.annotate_thickness, scale=args.annotate_scale, tags=not args.no_tags,
                               redact=redact, min_hits=args.track_min_hits if args.track else 1,
-                              num_labels=model.c.num_labels, pixelate=pixelate, cell=args.pixelate_cell)
+                              num_labels=model.c.num_labels, pixelate=pixelate, cell=args.pixelate_cell,
+                              blur=blur, blur_radius=args.blur_radius)
             painted = torch.empty_like(buf)     # a second surface of the same layout over a second buffer
             target = surface(painted)
 

@@ -487,9 +487,9 @@ class YolosSmall(nn.Module):
 
     def annotate_image(self, frame, overlay, threshold: float = 0.5, tracker=None, target=None) -> Dict[str, object]:
         """:meth:`detect_image` — :meth:`track_image` with a ``tracker`` — and ``overlay.draw`` (``overlay.Overlay``)
-        into ``target``: the same dict with ``"frame"``, the painted target, added. One more launch (two where the
-        overlay pixelates labels: the mosaic, then the drawing) and no host synchronisation: frame in, annotated
-        (redacted, pixelated) frame out is still one capturable graph. ``target`` is a
+        into ``target``: the same dict with ``"frame"``, the painted target, added. One more launch (more where the
+        overlay pixelates or blurs labels: the mosaic, the blur's two, then the drawing) and no host synchronisation:
+        frame in, annotated (redacted, pixelated, blurred) frame out is still one capturable graph. ``target`` is a
         surface of the frame's size (the boxes are in the frame's pixels) and defaults to ``frame`` itself, painted in
         place: a decoder writes the next frame over it before the next replay. With ``target=None`` a replay on an
         unchanged buffer therefore detects on the annotated frame, not on the one that was put there."""
@@ -500,7 +500,7 @@ class YolosSmall(nn.Module):
                        threshold: float = 0.5, match: str = "ios", match_threshold: float = 0.5, tracker=None,
                        target=None) -> Dict[str, object]:
         """:meth:`detect_tiled` — :meth:`track_tiled` with a ``tracker`` — and ``overlay.draw`` of the merged list into
-        ``target``, as :meth:`annotate_image` (the mosaic of an overlay that pixelates labels included): with
+        ``target``, as :meth:`annotate_image` (the mosaic and the blur of an overlay that pixelates or blurs labels included): with
         ``target=None`` the frame itself is painted, and a replay on an unchanged buffer detects on the annotated
         frame."""
         if tracker is None:

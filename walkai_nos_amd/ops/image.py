@@ -77,8 +77,12 @@ which is also what runs on the CPU, with the ``torch`` backend and past a layout
 * :func:`mosaic` — the detections of selected labels pixelated in the frame's own planes by one launch, on the same
   surfaces: every cell of a lattice of :data:`MOSAIC_CELLS` pixels that a selected box touches takes the rounded mean
   of its samples, per sample plane, in exact integers. :func:`mosaic_cells` is the mask of marked cells and
-  :func:`mosaic_reference` the torch composition. Blur, other cell sizes, PQ / HLG surfaces, batches and cells
-  anchored to the box instead of the frame are not offered.
+  :func:`mosaic_reference` the torch composition. Other cell sizes, PQ / HLG surfaces, batches and cells anchored to
+  the box instead of the frame are not offered.
+* :func:`blur` — the boxes of selected labels blurred in place, on the same surfaces, by a separable Gaussian of integer
+  taps (:func:`blur_taps`, radius 1..:data:`BLUR_MAX_RADIUS` luma pixels), every sample from the frame as it was before
+  the call: two launches through a shadow buffer (``csrc/image_blur.h``). :func:`blur_reference` is the torch
+  composition. Radii above 32, box or other kernels, PQ / HLG surfaces, batches and feathered edges are not offered.
 """
 from __future__ import annotations
 
@@ -154,11 +158,20 @@ def _L() -> ctypes.CDLL:
             tiled = [vp] * 6 + [i32, vp, i32, i32, i32, vp]
             L.nos_mosaic_packed.argtypes = [vp, vp, vp, i64, ctypes.c_char_p, i32, i32] + tiled
             L.nos_mosaic_yuv.argtypes = [src, i32, i32] + tiled
+            # the same for both blur entries: the radius, the taps, the shadow and its bytes
+            blurred = [vp] * 6 + [i32, vp, i32, i32, i32, vp, vp, i64, vp]
+            L.nos_blur_packed.argtypes = [vp, vp, vp, i64, ctypes.c_char_p, i32, i32] + blurred
+            L.nos_blur_yuv.argtypes = [src, i32, i32] + blurred
+            L.nos_blur_shadow_packed.argtypes = [i64, ctypes.c_char_p, i32, i32]
+            L.nos_blur_shadow_yuv.argtypes = [src, i32, i32]
+            L.nos_blur_shadow_packed.restype = L.nos_blur_shadow_yuv.restype = i64
             L.nos_image_last_error.restype = ctypes.c_char_p
             if (L.nos_overlay_tile_rows(), L.nos_overlay_tile_columns()) != OVERLAY_TILE:
                 raise NativeUnavailable(f"{LIB} was built with another overlay tile than ops/image.py expects")
             if (L.nos_mosaic_tile_rows(), L.nos_mosaic_tile_columns()) != MOSAIC_TILE:
                 raise NativeUnavailable(f"{LIB} was built with another mosaic tile than ops/image.py expects")
+            if L.nos_blur_max_radius() != BLUR_MAX_RADIUS:
+                raise NativeUnavailable(f"{LIB} was built with another largest blur radius than ops/image.py expects")
             if (L.nos_image_taps(), L.nos_image_max_footprint(), L.nos_image_max_patch(),
                     L.nos_image_nv12_max_footprint(), L.nos_image_yuv420p_max_footprint(),
                     L.nos_image_packed_max_footprint(), L.nos_image_yuv_max_footprint()) != \
@@ -2157,8 +2170,8 @@ def mosaic(target, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tens
 
     One HIP launch (a workgroup per :data:`MOSAIC_TILE` of luma pixels, ``mosaic_k``) for fp32 / int32 lists up to 1024
     rows on the GPU; past that, for other dtypes, on the CPU and with the ``torch`` backend :func:`mosaic_reference`.
-    Blur, cells of other sizes, PQ / HLG surfaces, batches above one and cells anchored to the box instead of the frame
-    are not offered."""
+    Cells of other sizes, PQ / HLG surfaces, batches above one and cells anchored to the box instead of the frame are
+    not offered; :func:`blur` is the redaction that follows the box."""
     surface = overlay_surface(target)
     lists = _mosaic_check(surface, count, scores, labels, boxes, track_id, track_hits, min_hits, select, cell)
     count, scores, labels, boxes, track_id, track_hits = lists
@@ -2182,4 +2195,155 @@ def mosaic(target, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tens
         src = yuv_src(*surface.yuv, (0,) * 12)
         rc = _L().nos_mosaic_yuv(ctypes.byref(src), surface.h, surface.w, *tail)
     _check(rc, "mosaic")
+    return target
+
+
+# ---- detections blurred in the frame -------------------------------------------------------------------
+#: the largest radius of :func:`blur` in luma pixels (``csrc/image_blur.h``)
+BLUR_MAX_RADIUS = 32
+
+
+def blur_taps(rho: int) -> np.ndarray:
+    """The ``2 rho + 1`` integer taps of radius ``rho``, int32, built in fp64: ``[256]`` for 0; else ``sigma = rho / 2``,
+    ``g_k = exp(-k^2 / (2 sigma^2))``, ``t_k = floor(256 g_k / sum(g) + 0.5)`` for ``k != 0`` and the centre tap the rest,
+    so the sum is exactly 256. Symmetric, every tap at least 1 for ``rho`` up to 32; at large radii the centre may be a
+    count or two below its neighbours."""
+    rho = int(rho)
+    if not 0 <= rho <= BLUR_MAX_RADIUS:
+        raise ValueError(f"blur_taps: radius {rho!r} is not in 0..{BLUR_MAX_RADIUS}")
+    if rho == 0:
+        return np.array([256], dtype=np.int32)
+    k = np.arange(-rho, rho + 1, dtype=np.float64)
+    g = np.exp(-k * k / (2.0 * (rho / 2.0) ** 2))
+    t = np.floor(256.0 * g / g.sum() + 0.5).astype(np.int32)
+    t[rho] = 0
+    t[rho] = 256 - int(t.sum())
+    return t
+
+
+def _blur_table(radius: int, device: torch.device) -> torch.Tensor:
+    """int16 ``[2, 65]`` on ``device``: the taps of ``radius`` and of ``radius >> 1``, zeros behind them; cached per
+    (radius, device) as :func:`overlay_codes` is, so a captured graph copies nothing from the host."""
+    def make():
+        table = np.zeros((2, 2 * BLUR_MAX_RADIUS + 1), dtype=np.int16)
+        for s in range(2):
+            t = blur_taps(radius >> s)
+            table[s, :t.shape[0]] = t
+        return torch.from_numpy(table).to(device)
+    return _overlay_tables.get(("blur", int(radius), str(device)), make)
+
+
+def _blur_check(surface: OverlaySurface, count, scores, labels, boxes, track_id, track_hits, min_hits, select,
+                radius) -> tuple:
+    """The arguments of :func:`blur` checked, ``ValueError`` before any launch; the lists as :func:`_mosaic_check`
+    returns them."""
+    who = "blur"
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= BLUR_MAX_RADIUS:
+        raise ValueError(f"{who}: radius {radius!r} is not an integer in 1..{BLUR_MAX_RADIUS}")
+    lists = _overlay_lists(who, count, scores, labels, boxes, track_id, track_hits, min_hits)
+    if not isinstance(select, torch.Tensor) or select.dtype != torch.uint8 or select.dim() != 1 or select.numel() < 1:
+        raise ValueError(f"{who}: select is a uint8 [L] tensor, non-zero where a label is blurred")
+    for name, t in zip(("count", "scores", "labels", "boxes", "track_id", "track_hits", "select"), lists + (select,)):
+        if t is not None and t.device != surface.device:
+            raise ValueError(f"{who}: the target is on {surface.device}, {name} on {t.device}")
+    return (lists[0].reshape(1),) + lists[1:]
+
+
+def blur_reference(target, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor,
+                   track_id: Optional[torch.Tensor] = None, track_hits: Optional[torch.Tensor] = None, *,
+                   min_hits: int = 1, select: torch.Tensor, radius: int):
+    """The torch composition of :func:`blur`, with the same effect on ``target`` in place and without a host sync or a
+    loop over the rows: the painted pixels are :func:`mosaic_cells` at cell 1 (an outer product of row and column
+    ranges, summed); per sample plane the codes, replicate-padded, go through two fp64 1-D convolutions with the taps of
+    the axis radii (exact: every partial sum is an integer below 2^28), ``(sum + 2^15) // 2^16`` is stored through the
+    plane's strided view where the owner pixel is painted. Every plane is read before it is written."""
+    surface = overlay_surface(target)
+    lists = _blur_check(surface, count, scores, labels, boxes, track_id, track_hits, min_hits, select, radius)
+    if lists[1].shape[0] == 0:
+        return target
+    painted = mosaic_cells(surface.h, surface.w, *lists, min_hits, select, 1)
+    depth = 8 if surface.yuv is None else surface.yuv[3]
+    f64 = torch.float64
+    for view, _, hs, vs in surface.samples:
+        if view.dtype == torch.uint8:
+            bits, codes = view, view.to(torch.int32)
+        else:       # 16-bit words: the same bits as int16, read as yuv_codes does
+            bits = view if view.dtype == torch.int16 else view.view(torch.int16)
+            codes = ((bits.to(torch.int32) & 0xffff) >> surface.shift) & ((1 << depth) - 1)
+        rh, rv = radius >> hs, radius >> vs
+        th, tv = (_overlay_tables.get(("blur64", rho, str(view.device)),
+                                      lambda: torch.from_numpy(blur_taps(rho)).to(device=view.device, dtype=f64))
+                  for rho in (rh, rv))      # cached as the kernel's table is: nothing is copied from the host in a capture
+        x = F.pad(codes.to(f64)[None, None], (rh, rh, rv, rv), mode="replicate")
+        x = F.conv2d(F.conv2d(x, th.reshape(1, 1, 1, -1)), tv.reshape(1, 1, -1, 1))[0, 0]
+        m = torch.div(x + 32768.0, 65536.0, rounding_mode="floor").to(torch.int32) << surface.shift
+        on = painted[::1 << vs, ::1 << hs]
+        if view.dtype == torch.uint8:
+            bits.copy_(torch.where(on, m.to(torch.uint8), bits))
+        else:
+            bits.copy_(torch.where(on, ((m + 32768) % 65536 - 32768).to(torch.int16), bits))
+    return target
+
+
+def blur(target, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor,
+         track_id: Optional[torch.Tensor] = None, track_hits: Optional[torch.Tensor] = None, *, min_hits: int = 1,
+         select: torch.Tensor, radius: int):
+    """One frame's detections — the lists :func:`mosaic` takes — blurred in ``target`` (:func:`overlay_surface`: SDR,
+    one frame) in place, with no host synchronisation and no RGB frame; returns ``target``. ``select``: uint8 ``[L]`` on
+    the device, non-zero where a label is blurred; ``radius``: an integer in ``1..BLUR_MAX_RADIUS`` luma pixels. The
+    rule, in exact integers:
+
+    1. Row ``r`` is selected exactly as rule 1 of :func:`mosaic` selects it, and its rectangle is rule 2 of
+       :func:`overlay`: columns ``floor(x0) .. ceil(x1) - 1`` and rows ``floor(y0) .. ceil(y1) - 1`` after the fp32
+       clamp. The painted pixels are the union of the selected rectangles clipped to the frame: pixels, not cells.
+    2. The taps of an axis radius ``rho`` are :func:`blur_taps`: a Gaussian of ``sigma = rho / 2`` in integers that
+       sum to 256.
+    3. A sample plane (``OverlaySurface.samples`` with its ``hsub`` / ``vsub``) has radius ``radius >> hsub``
+       horizontally and ``radius >> vsub`` vertically; radius 0 on an axis leaves the plane as it is on that axis.
+    4. Sample ``(cy, cx)`` of a plane of ``ph x pw`` samples is written exactly when its owner luma pixel ``(cy <<
+       vsub, cx << hsub)`` is painted (the overlay's ownership rule), as ``m = (sum_j sum_k tv[j] th[k] code[clamp(cy +
+       j, 0, ph - 1)][clamp(cx + k, 0, pw - 1)] + 2^15) >> 16``: one rounding at the end, a code what :func:`yuv_codes`
+       reads (the byte, or ``(word >> shift) & mask``), a 16-bit word stored whole as ``m << shift``.
+    5. Every code on the right-hand side is the frame's content before the call, under other painted boxes too. The
+       clamp is at the edge of the surface given: of a crop view, at the crop's edge.
+    6. Nothing else is written: the three colour bytes of a packed pixel are blurred each on its own and a fourth byte
+       is never written; the chroma neighbours of a YUY2 sample are the macropixels' chroma samples; not the unpainted
+       pixels, not the pitch padding, not the parent of a crop. Unlike the mosaic, applying the rule twice blurs twice.
+
+    Two HIP launches (``blur_snapshot_k`` and ``blur_k``, a workgroup per 64 x 64 tile each) through a shadow buffer
+    allocated here, stream-ordered (inside a graph capture it comes from the graph's pool), for fp32 / int32 lists up to
+    1024 rows on the GPU; past that, for other dtypes, on the CPU and with the ``torch`` backend :func:`blur_reference`.
+    Radii above 32, box or other kernels, PQ / HLG surfaces, batches above one and feathered edges are not offered."""
+    surface = overlay_surface(target)
+    lists = _blur_check(surface, count, scores, labels, boxes, track_id, track_hits, min_hits, select, radius)
+    count, scores, labels, boxes, track_id, track_hits = lists
+    N = scores.shape[0]
+    i32 = torch.int32
+    if not _use_hip(scores) or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or labels.dtype != i32 \
+            or count.dtype != i32 or (track_id is not None and (track_id.dtype != i32 or track_hits.dtype != i32)) \
+            or N > MAX_ROWS or N < 1:
+        return blur_reference(target, *lists, min_hits=min_hits, select=select, radius=radius)
+    scores, labels, boxes, select = scores.contiguous(), labels.contiguous(), boxes.contiguous(), select.contiguous()
+    ids = (None, None) if track_id is None else (track_id.contiguous(), track_hits.contiguous())
+    taps = _blur_table(radius, surface.device)
+    L = _L()
+    if surface.packed is not None:
+        data, order = surface.packed
+        pitch = data.stride(1) if data.shape[1] > 1 else data.shape[2] * data.shape[3]
+        need = L.nos_blur_shadow_packed(pitch, order.encode(), surface.h, surface.w)
+    else:
+        src = yuv_src(*surface.yuv, (0,) * 12)
+        need = L.nos_blur_shadow_yuv(ctypes.byref(src), surface.h, surface.w)
+    _check(min(need, 0), "blur")
+    shadow = torch.empty(need, dtype=torch.uint8, device=surface.device)
+    tail = (count.data_ptr(), scores.data_ptr(), labels.data_ptr(), boxes.data_ptr(),
+            None if ids[0] is None else ids[0].data_ptr(), None if ids[1] is None else ids[1].data_ptr(), N,
+            select.data_ptr(), select.shape[0], int(min_hits), int(radius), taps.data_ptr(), shadow.data_ptr(), need,
+            torch.cuda.current_stream().cuda_stream)
+    if surface.packed is not None:
+        lo, hi = _storage_bounds(data)
+        rc = L.nos_blur_packed(data.data_ptr(), lo, hi, pitch, order.encode(), surface.h, surface.w, *tail)
+    else:
+        rc = L.nos_blur_yuv(ctypes.byref(src), surface.h, surface.w, *tail)
+    _check(rc, "blur")
     return target
