@@ -21,6 +21,8 @@
 //    the one kernel here that reads a surface and writes it.
 //  * Blurring (image_blur.h): blur_snapshot_k and blur_k, the detections of selected labels blurred in place through a
 //    shadow copy of what a blur can read: two launches, no traffic between workgroups.
+//  * Cutting (image_chips.h): chips_k, the detections of selected labels cut out of any source the patch kernel reads and
+//    resampled to one size as RGB bytes — the one kernel here that reads a surface and writes a new tensor.
 //  * Entries. The extern "C" functions at the end check every argument of an outside caller, fill the kernel's
 //    arguments and launch; the arguments all image entries share travel as one struct (Common).
 #include <hip/hip_runtime.h>
@@ -71,6 +73,11 @@ struct ImgArgs {
 // TILES3 / TILES4 / YUV_TILES: the packed and the YUV staging loops over B tiles of one frame.
 enum class Src { RGB, NV12, NV21, YUV420P, PACKED3, PACKED4, YUV, TILES3, TILES4, YUV_TILES };
 constexpr int NG = RS / 12, GROUP_FMAX_W = NG * 4 - 3;
+}  // namespace
+
+#include "image_chips.h"  // behind the source tags: chips_k is instantiated by them
+
+namespace {
 
 // SrcArgs: what the layout's staging loop reads besides ImgArgs (image_stage.h; the contiguous RGB source is
 // ImgArgs::img and takes NoSrc). Y: Src::YUV's and Src::YUV_TILES' Yuv<...>.
@@ -253,43 +260,50 @@ using Kernel = void (*)(ImgArgs, A...);
 template <class A, class Y>
 constexpr Kernel<A> YUV_KERNEL = image_patch_planes_k<IS_TILED<A> ? Src::YUV_TILES : Src::YUV, A, Y>;
 
-// The instantiations of the general YUV front end, by the arguments A the launch passes and a source s that yuv_args
-// (and, for YuvHdrArgs, hdr_args) has checked. YuvArgs, nearest chroma: one per (layout, hsub, sample bytes), nine.
-// YuvBilinearArgs, bilinear chroma: hsub is 1 and packed sources have one sample size, five. YuvHdrArgs, PQ and HLG
-// through the tables: 16-bit samples, planar or semi-planar, 4:4:4 and subsampled with nearest chroma, subsampled
-// with bilinear chroma, six. Tiled<A>: the same over B tiles of one frame.
-template <class A>
-Kernel<A> yuv_kernel(const NosYuvSrc& s) {
+// The instantiations of the general YUV front end, by the arguments A the launch passes and a source s that yuv_source
+// (and, for YuvHdrArgs, hdr_args) has checked: f is called with the source's Yuv<...> tag and says what is
+// instantiated by it. YuvArgs, nearest chroma: one per (layout, hsub, sample bytes), nine. YuvBilinearArgs, bilinear
+// chroma: hsub is 1 and packed sources have one sample size, five. YuvHdrArgs, PQ and HLG through the tables: 16-bit
+// samples, planar or semi-planar, 4:4:4 and subsampled with nearest chroma, subsampled with bilinear chroma, six.
+// The one table of the patch kernel (yuv_kernel) and of the chips (chips_yuv_kernel).
+template <class A, class F>
+auto yuv_dispatch(const NosYuvSrc& s, F f) {
   if constexpr (std::is_base_of_v<YuvHdrArgs, A>) {
     switch ((s.layout == YUV_SEMI ? 3 : 0) + (s.chroma == 1 ? 2 : s.hsub)) {
-      case 0: return YUV_KERNEL<A, Hdr<Yuv<YUV_PLANAR, 0, 2>>>;
-      case 1: return YUV_KERNEL<A, Hdr<Yuv<YUV_PLANAR, 1, 2>>>;
-      case 2: return YUV_KERNEL<A, Hdr<Yuv<YUV_PLANAR, 1, 2, 1>>>;
-      case 3: return YUV_KERNEL<A, Hdr<Yuv<YUV_SEMI, 0, 2>>>;
-      case 4: return YUV_KERNEL<A, Hdr<Yuv<YUV_SEMI, 1, 2>>>;
-      default: return YUV_KERNEL<A, Hdr<Yuv<YUV_SEMI, 1, 2, 1>>>;
+      case 0: return f(Hdr<Yuv<YUV_PLANAR, 0, 2>>{});
+      case 1: return f(Hdr<Yuv<YUV_PLANAR, 1, 2>>{});
+      case 2: return f(Hdr<Yuv<YUV_PLANAR, 1, 2, 1>>{});
+      case 3: return f(Hdr<Yuv<YUV_SEMI, 0, 2>>{});
+      case 4: return f(Hdr<Yuv<YUV_SEMI, 1, 2>>{});
+      default: return f(Hdr<Yuv<YUV_SEMI, 1, 2, 1>>{});
     }
   } else if constexpr (std::is_base_of_v<YuvBilinearArgs, A>) {
     switch (s.layout * 2 + (s.sample_bytes - 1)) {
-      case 0: return YUV_KERNEL<A, Yuv<YUV_PLANAR, 1, 1, 1>>;
-      case 1: return YUV_KERNEL<A, Yuv<YUV_PLANAR, 1, 2, 1>>;
-      case 2: return YUV_KERNEL<A, Yuv<YUV_SEMI, 1, 1, 1>>;
-      case 3: return YUV_KERNEL<A, Yuv<YUV_SEMI, 1, 2, 1>>;
-      default: return YUV_KERNEL<A, Yuv<YUV_PACKED, 1, 1, 1>>;
+      case 0: return f(Yuv<YUV_PLANAR, 1, 1, 1>{});
+      case 1: return f(Yuv<YUV_PLANAR, 1, 2, 1>{});
+      case 2: return f(Yuv<YUV_SEMI, 1, 1, 1>{});
+      case 3: return f(Yuv<YUV_SEMI, 1, 2, 1>{});
+      default: return f(Yuv<YUV_PACKED, 1, 1, 1>{});
     }
   } else {
     switch (s.layout * 4 + s.hsub * 2 + (s.sample_bytes - 1)) {
-      case 0: return YUV_KERNEL<A, Yuv<YUV_PLANAR, 0, 1>>;
-      case 1: return YUV_KERNEL<A, Yuv<YUV_PLANAR, 0, 2>>;
-      case 2: return YUV_KERNEL<A, Yuv<YUV_PLANAR, 1, 1>>;
-      case 3: return YUV_KERNEL<A, Yuv<YUV_PLANAR, 1, 2>>;
-      case 4: return YUV_KERNEL<A, Yuv<YUV_SEMI, 0, 1>>;
-      case 5: return YUV_KERNEL<A, Yuv<YUV_SEMI, 0, 2>>;
-      case 6: return YUV_KERNEL<A, Yuv<YUV_SEMI, 1, 1>>;
-      case 7: return YUV_KERNEL<A, Yuv<YUV_SEMI, 1, 2>>;
-      default: return YUV_KERNEL<A, Yuv<YUV_PACKED, 1, 1>>;
+      case 0: return f(Yuv<YUV_PLANAR, 0, 1>{});
+      case 1: return f(Yuv<YUV_PLANAR, 0, 2>{});
+      case 2: return f(Yuv<YUV_PLANAR, 1, 1>{});
+      case 3: return f(Yuv<YUV_PLANAR, 1, 2>{});
+      case 4: return f(Yuv<YUV_SEMI, 0, 1>{});
+      case 5: return f(Yuv<YUV_SEMI, 0, 2>{});
+      case 6: return f(Yuv<YUV_SEMI, 1, 1>{});
+      case 7: return f(Yuv<YUV_SEMI, 1, 2>{});
+      default: return f(Yuv<YUV_PACKED, 1, 1>{});
     }
   }
+}
+
+// The patch kernel of a checked source: over B tiles of one frame when A is Tiled.
+template <class A>
+Kernel<A> yuv_kernel(const NosYuvSrc& s) {
+  return yuv_dispatch<A>(s, [](auto y) -> Kernel<A> { return YUV_KERNEL<A, decltype(y)>; });
 }
 
 int check(const char* what) {
@@ -471,16 +485,9 @@ int yuv_planes(const NosYuvSrc& s, int sB, int sh, int sw, PlaneArg* pl, long lo
   return 0;
 }
 
-// What the entries of the general YUV front end check and fill: every check of the descriptor and of the common
-// arguments, then the kernel's arguments k and n and the workgroups to launch. sB x sh x sw: the batch and the size
-// of the source the descriptor's planes hold — B x h x w itself, or the one frame that B tiles of h x w are cut from.
-int yuv_args(const NosYuvSrc* src, ImgArgs& k, int& grid, YuvBilinearArgs& n, const Common& c, int sB, int sh, int sw) {
-  if (!src) return fail("image_patch_planes: null operand");
-  if (src->size != int(sizeof(NosYuvSrc)))
-    return fail("image_patch_planes_yuv: descriptor size mismatch (NosYuvSrc of another build)");
-  const NosYuvSrc& s = *src;
-  if (const int rc = image_args(k, grid, c)) return rc;
-  if (c.max_fw > GROUP_FMAX_W) return fail("image_patch_planes_yuv: a patch's source footprint exceeds 69 columns");
+// What every entry that reads a YUV source checks of a descriptor of the right size, and fills of n: the format, the
+// chroma reconstruction, the planes of sB frames of sh x sw inside their storage, the colour table.
+int yuv_source(const NosYuvSrc& s, YuvBilinearArgs& n, int sB, int sh, int sw) {
   if (const int rc = yuv_format(s)) return rc;
   if (s.chroma != 0 && s.chroma != 1)
     return fail("image_patch_planes_yuv: unknown chroma reconstruction (0 nearest, 1 bilinear)");
@@ -501,6 +508,18 @@ int yuv_args(const NosYuvSrc* src, ImgArgs& k, int& grid, YuvBilinearArgs& n, co
   for (int i = 0; i < 4; ++i)
     n.wx[i] = (s.siting & 1 ? cosited : centred)[i], n.wy[i] = (s.siting & 2 ? cosited : centred)[i];
   return 0;
+}
+
+// What the entries of the general YUV front end check and fill: every check of the descriptor and of the common
+// arguments, then the kernel's arguments k and n and the workgroups to launch. sB x sh x sw: the batch and the size
+// of the source the descriptor's planes hold — B x h x w itself, or the one frame that B tiles of h x w are cut from.
+int yuv_args(const NosYuvSrc* src, ImgArgs& k, int& grid, YuvBilinearArgs& n, const Common& c, int sB, int sh, int sw) {
+  if (!src) return fail("image_patch_planes: null operand");
+  if (src->size != int(sizeof(NosYuvSrc)))
+    return fail("image_patch_planes_yuv: descriptor size mismatch (NosYuvSrc of another build)");
+  if (const int rc = image_args(k, grid, c)) return rc;
+  if (c.max_fw > GROUP_FMAX_W) return fail("image_patch_planes_yuv: a patch's source footprint exceeds 69 columns");
+  return yuv_source(*src, n, sB, sh, sw);
 }
 
 // What both HDR entries check of the tables (after yuv_args) and fill of n.
@@ -665,6 +684,45 @@ int blur_launch(const BlurArgs& k, const Dst& dst, const Dst& shadow, int pb, vo
   hipLaunchKernelGGL(blur_k<Dst>, dim3(grid), dim3(BT), blur_lds(k.band, k.radius, k.radius, pb),
                      reinterpret_cast<hipStream_t>(stream), k, dst, shadow);
   return check(what);
+}
+
+// What both chips entries check of the lists, the sizes and the outputs, and fill of k.
+int chips_args(ChipArgs& k, int h, int w, const int* count, const float* scores, const int* labels, const float* boxes,
+               const int* track_id, const int* track_hits, int N, const void* select, int L, int min_hits, int margin,
+               int capacity, int sh, int sw, void* chips, int* rows, int* rects, int* chip_count) {
+  if (const int rc = list_args("chips", h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits))
+    return rc;
+  if (!chips || !rows || !rects || !chip_count) return fail("chips: null operand");
+  if (sh < 1 || sh > CHIP_MAX_SIDE || sw < 1 || sw > CHIP_MAX_SIDE) return fail("chips: chip sides of 1..256 pixels");
+  if (capacity < 1 || capacity > CHIP_MAX_CAPACITY) return fail("chips: a capacity of 1..256 chips");
+  if (margin < 0 || margin > CHIP_MAX_MARGIN) return fail("chips: a margin of 0..64 pixels");
+  if ((long long)h * w > CHIP_MAX_AREA) return fail("chips: a frame of at most 2^24 pixels (the sums are 32 bits)");
+  k.m = MosaicArgs{count, scores, labels, boxes, track_id, track_hits, static_cast<const uint8_t*>(select), N, L, min_hits,
+                   h, w, 0, 255};
+  k.chips = static_cast<uint8_t*>(chips), k.rows = rows, k.rects = rects, k.chip_count = chip_count;
+  k.capacity = capacity, k.sh = sh, k.sw = sw, k.margin = margin;
+  k.band = std::max(1, std::min(sh, CHIP_NACC * CT / 3 / sw));
+  return 0;
+}
+
+template <class A>
+using ChipKernel = void (*)(ChipArgs, A);
+
+// chips_k on one workgroup per (band of output rows, slot); the LDS is the staged rows and the rows of sums
+template <class A>
+int chips_launch(ChipKernel<A> kernel, const ChipArgs& k, const A& n, void* stream, const char* what) {
+  const dim3 grid((k.sh + k.band - 1) / k.band, k.capacity);
+  const size_t lds = size_t(CHIP_ROWS) * (CHIP_ROWW + 3 * k.sw) * sizeof(uint32_t);
+  hipLaunchKernelGGL(kernel, grid, dim3(CT), lds, reinterpret_cast<hipStream_t>(stream), k, n);
+  return check(what);
+}
+
+// The chips kernel of a checked YUV source, from the table the patch kernel is taken from.
+template <class A>
+int chips_launch_yuv(const NosYuvSrc& s, const ChipArgs& k, const YuvHdrArgs& n, void* stream) {
+  const ChipKernel<A> kernel =
+      yuv_dispatch<A>(s, [](auto y) -> ChipKernel<A> { return chips_k<Src::YUV, A, decltype(y)>; });
+  return chips_launch(kernel, k, A(n), stream, "chips_yuv");
 }
 }  // namespace
 
@@ -1100,6 +1158,57 @@ int nos_blur_yuv(const NosYuvSrc* dst, int h, int w, const int* count, const flo
   const int pb = dst->sample_bytes == 2 ? 4 : 2;
   k.m.mask = (1 << dst->depth) - 1, k.band = blur_band(radius, pb);
   return blur_launch(k, d, sh, pb, stream, "blur_yuv");
+}
+
+int nos_chips_max_side() { return CHIP_MAX_SIDE; }
+int nos_chips_max_capacity() { return CHIP_MAX_CAPACITY; }
+int nos_chips_max_margin() { return CHIP_MAX_MARGIN; }
+int nos_chips_column_chunk() { return 4 * CHIP_GROUPS; }
+int nos_chips_row_chunk() { return CHIP_ROWS; }
+
+// The detections of the labels select [L] (uint8, non-zero: cut) marks, cut out of packed pixels img [h][w][C] (order,
+// pitch and [lo, hi) as in nos_image_patch_planes_packed; a crop view is read in place): the rows the rule selects
+// (nos_mosaic_packed's lists and filters; the rectangle grown by `margin` pixels and clipped to the frame, dropped when
+// nothing is left) take slots 0, 1, ... in row order, and each of the first `capacity` gets chips [slot] [sh][sw][3]
+// uint8, the exact area average of its rectangle stretched to sh x sw (image_chips.h), rows [slot] its row and rects
+// [slot] its rectangle (X0, Y0, X1, Y1), exclusive; the other slots get -1, zeros and a chip of zeros; chip_count [1]
+// the slots used. All outputs are device memory, int32 but the chips. Nothing is launched unless every check passes.
+int nos_chips_packed(const void* img, const void* lo, const void* hi, long long pitch, const char* order, int h, int w,
+                     const int* count, const float* scores, const int* labels, const float* boxes, const int* track_id,
+                     const int* track_hits, int N, const void* select, int L, int min_hits, int margin, int capacity,
+                     int sh, int sw, void* chips, int* rows, int* rects, int* chip_count, void* stream) {
+  if (!img || !order) return fail("chips: null operand");
+  ChipArgs k{};
+  if (const int rc = chips_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits,
+                                margin, capacity, sh, sw, chips, rows, rects, chip_count))
+    return rc;
+  PackedDst d{};
+  if (const int rc = packed_dst("chips_packed", d, const_cast<void*>(img), lo, hi, pitch, order, h, w)) return rc;
+  const PackedArgs n{d.s, d.r, 1, 2 - d.r};
+  if (d.C == 4) return chips_launch(chips_k<Src::PACKED4, PackedArgs>, k, n, stream, "chips_packed");
+  return chips_launch(chips_k<Src::PACKED3, PackedArgs>, k, n, stream, "chips_packed");
+}
+
+// The same out of the one h x w frame of any YUV source NosYuvSrc describes, converted as nos_image_patch_planes_yuv
+// converts it (nearest or bilinear chroma at its siting) or, with hdr not null, as nos_image_patch_planes_yuv_hdr does
+// (PQ / HLG through the tables). Every check those entries make of the descriptor, the planes and the tables.
+int nos_chips_yuv(const NosYuvSrc* src, const NosYuvHdr* hdr, int h, int w, const int* count, const float* scores,
+                  const int* labels, const float* boxes, const int* track_id, const int* track_hits, int N,
+                  const void* select, int L, int min_hits, int margin, int capacity, int sh, int sw, void* chips,
+                  int* rows, int* rects, int* chip_count, void* stream) {
+  if (!src) return fail("chips: null operand");
+  if (src->size != int(sizeof(NosYuvSrc))) return fail("chips_yuv: descriptor size mismatch (NosYuvSrc of another build)");
+  if (hdr && hdr->size != int(sizeof(NosYuvHdr)))
+    return fail("chips_yuv: table descriptor size mismatch (NosYuvHdr of another build)");
+  ChipArgs k{};
+  if (const int rc = chips_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits,
+                                margin, capacity, sh, sw, chips, rows, rects, chip_count))
+    return rc;
+  YuvHdrArgs n{};
+  if (yuv_source(*src, n, 1, h, w) || (hdr && hdr_args(*src, *hdr, n))) return fail("chips_yuv", ": the source: " + g_err);
+  if (hdr) return chips_launch_yuv<YuvHdrArgs>(*src, k, n, stream);
+  if (src->chroma == 1) return chips_launch_yuv<YuvBilinearArgs>(*src, k, n, stream);
+  return chips_launch_yuv<YuvArgs>(*src, k, n, stream);
 }
 
 }  // extern "C"

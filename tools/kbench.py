@@ -62,6 +62,14 @@ Four rows time the blur (``--rows blur`` runs them alone): ``blur_n100_1080p_nv1
 ``ops.image.mosaic`` of the same rows at the default cell (``*_mosaic_us``: the price of the halo and of the second
 launch), the frame restored inside the timed graph on all sides (``*_restore_us``). On the whole GPU
 ``blur_annotate_image_blur_thr0_ms`` stands beside ``blur_annotate_image_pixelate_thr0_ms``.
+
+Four rows time the chips (``--rows chips`` runs them alone): ``chips_n100_1080p_nv12_*`` and ``chips_n400_2160p_nv12_*``,
+``_rgb_*``, ``_p010_pq_*``, the overlay rows' lattice scene cut into 64 chips of 128 x 64: ``ops.image.chips``
+(``*_hip_us``, graph replays as every other row) and the frame's ``rgb()`` alone (``*_rgb_us``, graph replays: what a
+pod pays today before it can cut anything). ``chips_reference`` reads the selection on the host and cannot be
+captured, so it is timed eagerly, wall time per call with the stream drained, alternating with the same eager timing
+of the HIP call: on the converted frame (``*_torch_wall_us``), from the frame itself, conversion included
+(``*_rgb_torch_wall_us``: what a pod does today), and ``*_hip_wall_us``.
 """
 from __future__ import annotations
 
@@ -110,9 +118,9 @@ def main() -> int:
     ap.add_argument("--out", default="gpurun_out/kbench.json")
     ap.add_argument("--only", choices=("all", "attn", "gemm", "model", "modes", "image"), default="all")
     ap.add_argument("--slices", default="spx,dpx,qpx,cpx")
-    ap.add_argument("--rows", choices=("all", "tiles", "track", "overlay", "mosaic", "blur"), default="all",
+    ap.add_argument("--rows", choices=("all", "tiles", "track", "overlay", "mosaic", "blur", "chips"), default="all",
                     help="image: every row, or the tiled-detection rows alone, or the tracker's, the overlay's, the "
-                         "mosaic's or the blur's")
+                         "mosaic's, the blur's or the chips'")
     ap.add_argument("--partitions", type=int, default=0, help="modes: run only this many partitions of each mode")
     ap.add_argument("--free-s", type=float, default=0.0,
                     help="modes: serve free-running (one thread per pod, as the bench) for this many seconds "
@@ -393,6 +401,8 @@ def image_bench(a) -> int:
                 mosaic_rows(r, s, a.iters, rounds, whole_gpu=cus is None)
             if a.rows in ("all", "blur"):
                 blur_rows(r, s, a.iters, rounds, whole_gpu=cus is None)
+            if a.rows in ("all", "chips"):
+                chips_rows(r, s, a.iters, rounds)
             if not full:
                 print(json.dumps(r), flush=True)
                 results.append(r)
@@ -832,6 +842,64 @@ def blur_rows(r, s, iters, rounds, whole_gpu):
     for k, vs in t.items():
         r[f"blur_annotate_image_{k}_thr0_ms"] = round(statistics.median(vs) / 1000.0, 3)
     r["blur_model_rounds_ms"] = {k: [round(v / 1000.0, 3) for v in vs] for k, vs in t.items()}
+
+
+def chips_rows(r, s, iters, rounds):
+    """The chips (see the module docstring): ``chips_*_hip_us`` and ``*_rgb_us`` by graph replays, ``*_hip_wall_us``,
+    ``*_torch_wall_us`` and ``*_rgb_torch_wall_us`` eagerly; ``*_scene`` says what was cut."""
+    import statistics
+
+    from walkai_nos_amd.models.workload import surfaces
+    from walkai_nos_amd.models.workload.processor import Nv12
+    from walkai_nos_amd.ops import image as I
+    g = torch.Generator().manual_seed(7)
+    kw = dict(size=(128, 64), capacity=64, select=torch.ones(8, dtype=torch.uint8).cuda())
+
+    def wall(fn, n):
+        with torch.cuda.stream(s):
+            fn()
+            s.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                fn()
+            s.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / n
+    for name, n, h, w, fmt in (("n100_1080p_nv12", 100, 1080, 1920, "nv12"), ("n400_2160p_nv12", 400, 2160, 3840, "nv12"),
+                               ("n400_2160p_rgb", 400, 2160, 3840, "rgb"), ("n400_2160p_p010_pq", 400, 2160, 3840, "p010")):
+        if fmt == "rgb":
+            frame = torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8).cuda()
+            rgb = frame
+        else:
+            pitch = -(-w * (2 if fmt == "p010" else 1) // 256) * 256
+            buf = torch.randint(0, 256, (pitch * h * 3 // 2,), generator=g, dtype=torch.uint8).cuda()
+            frame = Nv12.from_buffer(buf, h, w, pitch) if fmt == "nv12" else \
+                surfaces.from_buffer(fmt, buf, h, w, pitch, matrix="bt2020", transfer="pq")
+            rgb = frame.rgb()[0]
+        lists = [t.cuda() for t in overlay_scene(n, h, w)[0]]
+        with torch.cuda.stream(s):
+            got = [t.clone() for t in I.chips(frame, *lists, **kw)]
+            want = I.chips_reference(frame, *lists, **kw)
+            same = all(torch.equal(a, b) for a, b in zip(got, want))
+            s.synchronize()
+        graphs = {"hip": lambda: I.chips(frame, *lists, **kw), "rgb": lambda: rgb if fmt == "rgb" else frame.rgb()}
+        eager = {"hip_wall": graphs["hip"], "torch_wall": lambda: I.chips_reference(rgb, *lists, **kw),
+                 "rgb_torch_wall": lambda: I.chips_reference(frame, *lists, **kw)}
+        t = {k: [] for k in list(graphs) + list(eager)}
+        for _ in range(rounds):
+            for k, fn in graphs.items():
+                if k != "rgb" or fmt != "rgb":
+                    t[k].append(timeit(fn, s, iters))
+            for k, fn in eager.items():
+                t[k].append(wall(fn, iters if k == "hip_wall" else max(2, iters // 5)))
+        for k, vs in t.items():
+            if vs:
+                r[f"chips_{name}_{k}_us"] = round(statistics.median(vs), 1)
+        r[f"chips_{name}_rounds_us"] = {k: [round(v, 1) for v in vs] for k, vs in t.items()}
+        print(f"[kbench] chips_{name}: {r[f'chips_{name}_rounds_us']}", file=sys.stderr, flush=True)
+        rects = want[2][:int(want[3])].cpu()
+        r[f"chips_{name}_scene"] = {"rows": n, "chips": int(want[3]), "frame": [h, w], "size": [128, 64],
+                                    "box_pixels": int(((rects[:, 2] - rects[:, 0]) * (rects[:, 3] - rects[:, 1])).sum()),
+                                    "hip_equals_torch": bool(same)}
 
 
 def free_running(slots, seconds: float) -> int:

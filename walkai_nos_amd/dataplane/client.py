@@ -45,6 +45,11 @@ The client builds a second surface of the same layout over a second buffer; insi
 copied there and painted there, so the synthetic frame stays the same from replay to replay. The JSON line then carries
 ``"annotate": {"changed_bytes": ...}``, the bytes of the second buffer that differ from the source, counted once on the
 host after the loop. It is refused with ``--transfer pq|hlg``: an SDR colour has no code on such a surface.
+``--chips L1,L2,...|all`` cuts the boxes of those labels out of the frame (``YolosSmall.chip_image`` / ``chip_tiled``, one
+more launch inside the captured graph) as RGB chips of ``--chip-size H,W`` (default 128,64), at most ``--chip-capacity``
+(default 64) a frame, each box grown by ``--chip-margin`` pixels first; it goes with ``--tiles``, ``--track``, every
+``--pixel-format`` and ``--transfer``. With ``--annotate`` the chips are cut before the frame is painted. The JSON line
+then carries ``"chips": {"count": ..., "nonzero_bytes": ...}`` of the last inference.
 """
 from __future__ import annotations
 
@@ -149,7 +154,30 @@ def main(argv=None) -> int:
     ap.add_argument("--blur-radius", type=int, default=None,
                     help="--blur: the radius of the Gaussian in pixels, 1..32 (default: by the frame's size)")
     ap.add_argument("--no-tags", action="store_true", help="--annotate: boxes without id tags")
+    ap.add_argument("--chips", default="", help="--end-to-end: L1,L2,... or all: cut those labels' boxes out as RGB chips")
+    ap.add_argument("--chip-size", default=None, help="--chips: H,W of every chip, 1..256 each (default 128,64)")
+    ap.add_argument("--chip-capacity", type=int, default=None, help="--chips: the chips of one frame, 1..256 (default 64)")
+    ap.add_argument("--chip-margin", type=int, default=None, help="--chips: pixels added around a box, 0..64 (default 0)")
     args = ap.parse_args(argv)
+    chip_labels = chip_size = None
+    if args.chips:
+        if not args.end_to_end:
+            ap.error("--chips takes --end-to-end")
+        try:
+            chip_labels = None if args.chips == "all" else tuple(int(v) for v in args.chips.split(","))
+            chip_size = tuple(int(v) for v in (args.chip_size or "128,64").split(","))
+        except ValueError:
+            chip_labels, chip_size = (-1,), ()
+        if chip_labels is not None and any(not 0 <= v < 91 for v in chip_labels):
+            ap.error(f"--chips {args.chips!r} is not all or L1,L2,... with labels in 0..90")
+        if len(chip_size) != 2 or any(not 1 <= v <= 256 for v in chip_size):
+            ap.error(f"--chip-size {args.chip_size!r} is not H,W with sides in 1..256")
+        if args.chip_capacity is not None and not 1 <= args.chip_capacity <= 256:
+            ap.error(f"--chip-capacity {args.chip_capacity} is not in 1..256")
+        if args.chip_margin is not None and not 0 <= args.chip_margin <= 64:
+            ap.error(f"--chip-margin {args.chip_margin} is not in 0..64")
+    elif args.chip_size is not None or args.chip_capacity is not None or args.chip_margin is not None:
+        ap.error("--chip-size, --chip-capacity and --chip-margin take --chips")
     redact = pixelate = blur = ()
     if args.annotate:
         if not args.end_to_end:
@@ -290,8 +318,23 @@ def main(argv=None) -> int:
                               blur=blur, blur_radius=args.blur_radius)
             painted = torch.empty_like(buf)     # a second surface of the same layout over a second buffer
             target = surface(painted)
+        chips = None
+        if args.chips:
+            from ..models.workload.chips import Chips
+            chips = Chips(chip_size, chip_labels, 64 if args.chip_capacity is None else args.chip_capacity,
+                          args.chip_margin or 0, args.track_min_hits if args.track else 1, model.c.num_labels)
 
         def infer():
+            if chips is not None:
+                if tiles is not None:
+                    det = model.chip_tiled(img, chips, tiles, args.tile_overlap, args.threshold, args.match,
+                                           args.match_threshold, tracker)
+                else:
+                    det = model.chip_image(img, chips, args.threshold, tracker)
+                if overlay is not None:     # cut first, then painted: one detection dict
+                    painted.copy_(buf)
+                    det = {**det, "frame": overlay.draw(det, target)}
+                return det
             if overlay is not None:
                 painted.copy_(buf)
                 if tiles is not None:
@@ -389,6 +432,8 @@ def main(argv=None) -> int:
                             "capacity": tracker.capacity, "motion": args.track_motion}
         if overlay is not None:
             out["annotate"] = {"changed_bytes": int((painted != buf).sum().item())}
+        if chips is not None:
+            out["chips"] = {"count": int(res["chip_count"].item()), "nonzero_bytes": int((res["chips"] != 0).sum().item())}
     if census is not None:
         out["census"] = census
     out["hbm"] = _shim()

@@ -509,6 +509,26 @@ class YolosSmall(nn.Module):
             det = self.track_tiled(frame, tracker, tiles, overlap, threshold, match, match_threshold)
         return {**det, "frame": overlay.draw(det, frame if target is None else target)}
 
+    def chip_image(self, frame, chips, threshold: float = 0.5, tracker=None) -> Dict[str, object]:
+        """:meth:`detect_image` — :meth:`track_image` with a ``tracker`` — and ``chips.cut`` (``chips.Chips``): the same
+        dict with ``chips``, ``chip_rows``, ``chip_rects`` and ``chip_count`` added, the boxes of the chosen labels cut
+        out of the frame at one size as RGB bytes. One more launch and no host synchronisation: frame in, detections and
+        their pictures out is one capturable graph, on every layout, chroma mode and transfer the front end reads."""
+        img = self.processor.as_batch(frame, self.pos_embed.device)
+        det = self.detect_image(img, threshold) if tracker is None else self.track_image(img, tracker, threshold)
+        return chips.cut(det, img)
+
+    def chip_tiled(self, frame, chips, tiles: Tuple[int, int] = (2, 2), overlap: float = 0.2, threshold: float = 0.5,
+                   match: str = "ios", match_threshold: float = 0.5, tracker=None) -> Dict[str, object]:
+        """:meth:`detect_tiled` — :meth:`track_tiled` with a ``tracker`` — and ``chips.cut`` of the merged list out of the
+        whole frame, as :meth:`chip_image`."""
+        img = self.processor.as_batch(frame, self.pos_embed.device)
+        if tracker is None:
+            det = self.detect_tiled(img, tiles, overlap, threshold, match, match_threshold)
+        else:
+            det = self.track_tiled(img, tracker, tiles, overlap, threshold, match, match_threshold)
+        return chips.cut(det, img)
+
     def _target_sizes(self, img: torch.Tensor) -> torch.Tensor:
         """``[B, 2]`` fp32 (height, width) of the original images on their device, cached: a captured
         graph must not copy from the host."""

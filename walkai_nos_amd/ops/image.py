@@ -83,6 +83,11 @@ which is also what runs on the CPU, with the ``torch`` backend and past a layout
   taps (:func:`blur_taps`, radius 1..:data:`BLUR_MAX_RADIUS` luma pixels), every sample from the frame as it was before
   the call: two launches through a shadow buffer (``csrc/image_blur.h``). :func:`blur_reference` is the torch
   composition. Radii above 32, box or other kernels, PQ / HLG surfaces, batches and feathered edges are not offered.
+* :func:`chips` — the read side again: the boxes of selected labels cut out of the frame, each stretched to one size by
+  an exact area average, as RGB bytes ``[capacity, S_h, S_w, 3]`` with the row and the rectangle of every slot, by one
+  launch on every layout, chroma mode and transfer the front end reads, PQ / HLG included (``csrc/image_chips.h``).
+  :func:`chips_reference` is the torch composition. Aspect-preserving or letterboxed chips, bilinear or bicubic
+  enlargement, float or normalised output, rotated boxes, batches and more than 256 chips are not offered.
 """
 from __future__ import annotations
 
@@ -165,6 +170,10 @@ def _L() -> ctypes.CDLL:
             L.nos_blur_shadow_packed.argtypes = [i64, ctypes.c_char_p, i32, i32]
             L.nos_blur_shadow_yuv.argtypes = [src, i32, i32]
             L.nos_blur_shadow_packed.restype = L.nos_blur_shadow_yuv.restype = i64
+            # the lists, the parameters and the four outputs both chips entries take behind their source
+            cut = [vp] * 6 + [i32, vp] + [i32] * 6 + [vp] * 5
+            L.nos_chips_packed.argtypes = [vp, vp, vp, i64, ctypes.c_char_p, i32, i32] + cut
+            L.nos_chips_yuv.argtypes = [src, hdr, i32, i32] + cut
             L.nos_image_last_error.restype = ctypes.c_char_p
             if (L.nos_overlay_tile_rows(), L.nos_overlay_tile_columns()) != OVERLAY_TILE:
                 raise NativeUnavailable(f"{LIB} was built with another overlay tile than ops/image.py expects")
@@ -172,6 +181,9 @@ def _L() -> ctypes.CDLL:
                 raise NativeUnavailable(f"{LIB} was built with another mosaic tile than ops/image.py expects")
             if L.nos_blur_max_radius() != BLUR_MAX_RADIUS:
                 raise NativeUnavailable(f"{LIB} was built with another largest blur radius than ops/image.py expects")
+            if (L.nos_chips_max_side(), L.nos_chips_max_capacity(), L.nos_chips_max_margin()) != \
+                    (CHIP_MAX_SIDE, CHIP_MAX_CAPACITY, CHIP_MAX_MARGIN):
+                raise NativeUnavailable(f"{LIB} was built with other chip limits than ops/image.py expects")
             if (L.nos_image_taps(), L.nos_image_max_footprint(), L.nos_image_max_patch(),
                     L.nos_image_nv12_max_footprint(), L.nos_image_yuv420p_max_footprint(),
                     L.nos_image_packed_max_footprint(), L.nos_image_yuv_max_footprint()) != \
@@ -278,11 +290,12 @@ _tables = GraphCache(16)
 
 
 def invalidate_cache() -> None:
-    """Drop every cached tap table, tile-origin table, HDR table and overlay table, also those a captured graph holds: capture such
+    """Drop every cached tap table, tile-origin table, HDR table, overlay table and chip buffer, also those a captured graph holds: capture such
     graphs again."""
     _tables.clear()
     _hdr_tables.clear()
     _overlay_tables.clear()
+    _chip_buffers.clear()
 
 
 def _make_tables(h: int, w: int, H: int, W: int, p: int, device: torch.device) -> Optional[tuple]:
@@ -2347,3 +2360,226 @@ def blur(target, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor
         rc = L.nos_blur_yuv(ctypes.byref(src), surface.h, surface.w, *tail)
     _check(rc, "blur")
     return target
+
+
+# ---- detections cut out of the frame -------------------------------------------------------------------
+#: the kernel's limits (``csrc/image_chips.h``): a chip's side, the chips of a call, the margin, the frame's pixels
+CHIP_MAX_SIDE, CHIP_MAX_CAPACITY, CHIP_MAX_MARGIN, CHIP_MAX_AREA = 256, 256, 64, 1 << 24
+
+#: the output buffers of :func:`chips` per (device, capacity, size): a captured graph writes them by address, so they
+#: are kept as :data:`_tables` are
+_chip_buffers = GraphCache(16)
+
+
+def _chip_source(frame) -> tuple:
+    """What :func:`chips` knows of a frame, without a copy: ``(B, h, w, device, packed, yuv, rgb)`` — ``packed = (data
+    [B, h, w, C], order)`` or ``yuv = (descriptor, hdr)`` as :func:`_yuv_launch` takes them, and ``rgb``, a callable that
+    gives the converted ``[B, h, w, 3]`` frame. ``frame``: a uint8 ``[h, w, 3]`` (or ``[B, h, w, 3]``) RGB tensor or any
+    frame of ``models/workload``, told apart by its fields as :func:`overlay_surface` does; every chroma mode and
+    transfer is read."""
+    who = "chips"
+    g = lambda name, default: getattr(frame, name, default)    # noqa: E731
+    if isinstance(frame, torch.Tensor) or (hasattr(frame, "data") and hasattr(frame, "order")
+                                           and not hasattr(frame, "width")):
+        data, order = (frame, "rgb") if isinstance(frame, torch.Tensor) else (frame.data, frame.order)
+        if order not in PACKED_ORDERS:
+            raise ValueError(f"{who}: channel order {order!r} is none of {sorted(PACKED_ORDERS)}")
+        C = PACKED_ORDERS[order][0]
+        if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() not in (3, 4) \
+                or data.shape[-1] != C or 0 in data.shape:
+            raise ValueError(f"{who}: {order} takes a uint8 [h, w, {C}] tensor")
+        data = data if data.dim() == 4 else data[None]
+        if not _packed_strides(data):
+            raise ValueError(f"{who}: rows may be pitched, but the bytes of a row are contiguous")
+        return data.shape[0], data.shape[1], data.shape[2], data.device, (data, order), None, \
+            lambda: packed_to_rgb(data, order)
+    matrix, full = g("matrix", "bt601"), bool(g("full_range", False))
+    chroma, siting = g("chroma", "nearest"), g("siting", "left")
+    transfer, peak = g("transfer", "sdr"), g("peak_nits", 1000.0)
+    if hasattr(frame, "data") and hasattr(frame, "width"):
+        source = _yuyv_source(frame.data, frame.width, g("order", "yuyv"), matrix, full, chroma, siting)
+    elif hasattr(frame, "y") and hasattr(frame, "uv"):
+        source = _semiplanar_source(frame.y, frame.uv, g("subsampling", "420"), g("depth", 8), bool(g("msb", False)),
+                                    matrix, full, bool(g("vu", False)), chroma, siting, transfer, peak)
+    elif hasattr(frame, "y") and hasattr(frame, "u") and hasattr(frame, "v"):
+        source = _planar_source(frame.y, frame.u, frame.v, g("subsampling", "420"), g("depth", 8),
+                                bool(g("msb", False)), matrix, full, chroma, siting, transfer, peak)
+    else:
+        raise ValueError(f"{who}: the frame is a uint8 [h, w, 3] tensor or a Packed, Nv12, Yuv420p, YuvPlanar, "
+                         f"YuvSemiPlanar or Yuyv frame, not {type(frame).__name__}")
+    first, (h, w), src, rgb, hdr = source
+    return first.shape[0], h, w, first.device, None, (src, hdr), rgb
+
+
+def _chips_params(size, capacity, margin) -> tuple:
+    """``(S_h, S_w, capacity, margin)`` checked: ``ValueError`` for what no route serves."""
+    who = "chips"
+    try:
+        S_h, S_w = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: size {size!r} is not (rows, columns)") from None
+    if S_h < 1 or S_w < 1:
+        raise ValueError(f"{who}: size {size!r} is not (rows, columns) from 1 up")
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 1:
+        raise ValueError(f"{who}: capacity {capacity!r} is not a number of chips from 1 up")
+    if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or not 0 <= margin <= CHIP_MAX_MARGIN:
+        raise ValueError(f"{who}: margin {margin!r} is not an integer in 0..{CHIP_MAX_MARGIN}")
+    return S_h, S_w, int(capacity), int(margin)
+
+
+def _chips_check(device, count, scores, labels, boxes, track_id, track_hits, min_hits, select) -> tuple:
+    """One frame's lists of :func:`chips` checked, as :func:`_mosaic_check` returns them."""
+    who = "chips"
+    lists = _overlay_lists(who, count, scores, labels, boxes, track_id, track_hits, min_hits)
+    if not isinstance(select, torch.Tensor) or select.dtype != torch.uint8 or select.dim() != 1 or select.numel() < 1:
+        raise ValueError(f"{who}: select is a uint8 [L] tensor, non-zero where a label is cut out")
+    for name, t in zip(("count", "scores", "labels", "boxes", "track_id", "track_hits", "select"), lists + (select,)):
+        if t is not None and t.device != device:
+            raise ValueError(f"{who}: the frame is on {device}, {name} on {t.device}")
+    return (lists[0].reshape(1),) + lists[1:]
+
+
+def chip_rects(h: int, w: int, count, scores, labels, boxes, track_id, track_hits, min_hits: int, select: torch.Tensor,
+               margin: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The selection of :func:`chips` on the lists' device, without a host sync: ``(selected [N] bool, rects [N, 4]
+    int32)`` — :func:`mosaic`'s rule 1, then the rectangle as ``(X0, Y0, X1, Y1)``, exclusive, grown by ``margin`` and
+    clipped to the frame; a row of which nothing is left is not selected."""
+    N, L = scores.shape[0], select.shape[0]
+    lb = labels.to(torch.int64)
+    chosen = (lb >= 0) & (lb < L) & (select[lb.clamp(0, L - 1)] != 0)
+    bx = boxes.to(torch.float32)
+    finite = torch.isfinite(bx).all(dim=1)
+    c = torch.where(finite[:, None], bx, 0.0).clamp(-OVERLAY_CLAMP, OVERLAY_CLAMP)
+    x0, y0 = torch.floor(c[:, 0]).to(torch.int32), torch.floor(c[:, 1]).to(torch.int32)
+    x1, y1 = torch.ceil(c[:, 2]).to(torch.int32), torch.ceil(c[:, 3]).to(torch.int32)
+    n = count.reshape(1)[0].clamp(0, N)
+    ok = (torch.arange(N, device=scores.device) < n) & (scores.to(torch.float32) > 0) & chosen & finite \
+        & (x1 > x0) & (y1 > y0)
+    if track_id is not None:
+        ok = ok & (track_id > 0) & (track_hits >= int(min_hits))
+    m = int(margin)
+    rect = torch.stack(((x0 - m).clamp(min=0), (y0 - m).clamp(min=0), (x1 + m).clamp(max=w), (y1 + m).clamp(max=h)), 1)
+    return ok & (rect[:, 2] > rect[:, 0]) & (rect[:, 3] > rect[:, 1]), rect
+
+
+def chip_weights(n: int, m: int, device=None) -> torch.Tensor:
+    """The area weights of one axis, float64 ``[m, n]``: ``n`` source pixels and ``m`` outputs on a lattice of ``n m``
+    units, ``w[j][s]`` the length of the overlap of output ``[j n, (j + 1) n)`` with pixel ``[s m, (s + 1) m)`` — an
+    integer; a row sums to ``n``."""
+    s = torch.arange(n, device=device, dtype=torch.int64)[None, :]
+    j = torch.arange(m, device=device, dtype=torch.int64)[:, None]
+    return (torch.minimum((s + 1) * m, (j + 1) * n) - torch.maximum(s * m, j * n)).clamp(min=0).to(torch.float64)
+
+
+def _chips_one(rgb: torch.Tensor, lists: tuple, S_h: int, S_w: int, select, capacity: int, margin: int,
+               min_hits: int) -> tuple:
+    """:func:`chips_reference` of one ``[h, w, 3]`` frame and its checked lists."""
+    dev, (h, w) = rgb.device, rgb.shape[:2]
+    chips = torch.zeros((capacity, S_h, S_w, 3), dtype=torch.uint8, device=dev)
+    rows = torch.full((capacity,), -1, dtype=torch.int32, device=dev)
+    rects = torch.zeros((capacity, 4), dtype=torch.int32, device=dev)
+    picked = []
+    if lists[1].shape[0]:
+        ok, rect = chip_rects(h, w, *lists, min_hits, select, margin)
+        picked = torch.nonzero(ok).flatten()[:capacity].tolist()
+        rect = rect.tolist()
+    for k, r in enumerate(picked):
+        X0, Y0, X1, Y1 = rect[r]
+        A = (Y1 - Y0) * (X1 - X0)
+        crop = rgb[Y0:Y1, X0:X1].permute(2, 0, 1).to(torch.float64)
+        total = chip_weights(Y1 - Y0, S_h, dev) @ crop @ chip_weights(X1 - X0, S_w, dev).t()    # [3, S_h, S_w]: exact
+        chips[k] = torch.div(total.to(torch.int64) + A // 2, A, rounding_mode="floor").permute(1, 2, 0).to(torch.uint8)
+        rows[k] = r
+        rects[k] = torch.tensor(rect[r], dtype=torch.int32)
+    return chips, rows, rects, torch.tensor([len(picked)], dtype=torch.int32, device=dev)
+
+
+def chips_reference(frame, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor,
+                    track_id: Optional[torch.Tensor] = None, track_hits: Optional[torch.Tensor] = None, *, size,
+                    select: torch.Tensor, capacity: int, margin: int = 0, min_hits: int = 1):
+    """The torch composition of :func:`chips`, on any device and for any size, capacity and number of rows: the frame
+    converted (its ``rgb()``), :func:`chip_rects`, then per selected row ``Wy @ crop @ Wx^T`` in float64 with
+    :func:`chip_weights` — exact, every term is an integer below 2^53 — and ``(sum + A // 2) // A`` in int64. It reads
+    the selection on the host, so it cannot be captured. A batch of ``B > 1`` frames takes ``count [B]`` and lists
+    ``[B, N, ...]`` and returns the four tensors with a leading ``B``."""
+    B, h, w, device, _, _, rgb = _chip_source(frame)
+    S_h, S_w, capacity, margin = _chips_params(size, capacity, margin)
+    img = rgb()
+    out = []
+    for b in range(B):
+        one = (count, scores, labels, boxes, track_id, track_hits)
+        if B > 1:
+            if count.numel() != B or scores.dim() != 2 or scores.shape[0] != B:
+                raise ValueError(f"chips: a batch of {B} frames takes count [{B}] and lists [{B}, N]")
+            one = tuple(None if t is None else t.reshape(B, *t.shape[1:])[b] for t in one)
+            one = (one[0].reshape(1),) + one[1:]
+        lists = _chips_check(device, *one, min_hits, select)
+        out.append(_chips_one(img[b], lists, S_h, S_w, select, capacity, margin, min_hits))
+    return out[0] if B == 1 else tuple(torch.stack(t) for t in zip(*out))
+
+
+def chips(frame, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor,
+          track_id: Optional[torch.Tensor] = None, track_hits: Optional[torch.Tensor] = None, *, size,
+          select: torch.Tensor, capacity: int, margin: int = 0, min_hits: int = 1):
+    """One frame's detections — the lists :func:`mosaic` takes — cut out of ``frame`` as RGB chips of one size, with no
+    host synchronisation and no RGB frame: ``(chips [capacity, S_h, S_w, 3] uint8, rows [capacity] int32, rects
+    [capacity, 4] int32, chip_count [1] int32)``. ``frame``: a uint8 RGB tensor or any frame of ``models/workload``, in
+    every layout, chroma mode and transfer the front end reads (PQ / HLG too: reading needs no inverse tone map);
+    ``select``: uint8 ``[L]`` on the device, non-zero where a label is cut out; ``size = (S_h, S_w)``. The rule, in
+    exact integers:
+
+    1. The candidates are rows ``0 .. clamp(count, 0, N) - 1``. Row ``r`` is selected exactly as rule 1 of
+       :func:`mosaic` selects it; its rectangle is columns ``floor(x0) .. ceil(x1)`` and rows ``floor(y0) .. ceil(y1)``,
+       exclusive, after the fp32 clamp, and a row whose rectangle is empty is not selected.
+    2. The rectangle is grown by ``margin`` pixels (0..:data:`CHIP_MAX_MARGIN`) on every side and clipped to the
+       frame, ``(X0, Y0, X1, Y1)``; a row of which nothing is left is not selected.
+    3. Selected rows take slots in row order; the first ``capacity`` get a chip. ``rows[k]`` is slot ``k``'s row,
+       ``rects[k]`` its clipped rectangle, ``chip_count = min(selected, capacity)``. Slots from ``chip_count`` on hold
+       ``rows = -1``, a rectangle of zeros and a chip of zeros: every output byte is written by every call.
+    4. The chip is the exact area average of ``frame.rgb()[Y0:Y1, X0:X1]`` stretched to ``S_h x S_w`` — not
+       letterboxed. Per axis, ``n`` source pixels and ``m`` outputs lie on a lattice of ``n m`` units, pixel ``s`` on
+       ``[s m, (s + 1) m)`` and output ``j`` on ``[j n, (j + 1) n)``; ``w[j][s]`` is the length of their overlap
+       (:func:`chip_weights`). A channel's value is ``(sum_sy sum_sx wy wx v + A // 2) // A`` with ``A = bh bw``: the box
+       filter when shrinking, replication with blended seams when enlarging (bilinear enlargement is not offered).
+
+    One HIP launch (``chips_k``: a workgroup per band of output rows and slot, ``csrc/image_chips.h``) into buffers
+    cached per (device, capacity, size) — a later call of the same key overwrites them, and a captured graph keeps
+    them alive — for fp32 / int32 lists of 1..1024 rows, sides of 1..:data:`CHIP_MAX_SIDE`, up to
+    :data:`CHIP_MAX_CAPACITY` chips and frames of up to 2^24 pixels on the GPU; past any of that, for other dtypes, for
+    a batch above one, on the CPU and with the ``torch`` backend :func:`chips_reference`. Aspect-preserving or
+    letterboxed chips, bilinear or bicubic enlargement, float or normalised output and rotated boxes are not offered."""
+    B, h, w, device, packed, yuv, _ = _chip_source(frame)
+    S_h, S_w, capacity, margin = _chips_params(size, capacity, margin)
+    kw = dict(size=(S_h, S_w), select=select, capacity=capacity, margin=margin, min_hits=min_hits)
+    if B != 1:
+        return chips_reference(frame, count, scores, labels, boxes, track_id, track_hits, **kw)
+    lists = _chips_check(device, count, scores, labels, boxes, track_id, track_hits, min_hits, select)
+    count, scores, labels, boxes, track_id, track_hits = lists
+    N = scores.shape[0]
+    i32 = torch.int32
+    if not _use_hip(scores) or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or labels.dtype != i32 \
+            or count.dtype != i32 or (track_id is not None and (track_id.dtype != i32 or track_hits.dtype != i32)) \
+            or N > MAX_ROWS or N < 1 or max(S_h, S_w) > CHIP_MAX_SIDE or capacity > CHIP_MAX_CAPACITY \
+            or h * w > CHIP_MAX_AREA:
+        return chips_reference(frame, *lists, **kw)
+    out = _chip_buffers.get((str(device), capacity, S_h, S_w), lambda: (
+        torch.empty((capacity, S_h, S_w, 3), dtype=torch.uint8, device=device),
+        torch.empty((capacity,), dtype=i32, device=device), torch.empty((capacity, 4), dtype=i32, device=device),
+        torch.empty((1,), dtype=i32, device=device)))
+    scores, labels, boxes, select = scores.contiguous(), labels.contiguous(), boxes.contiguous(), select.contiguous()
+    ids = (None, None) if track_id is None else (track_id.contiguous(), track_hits.contiguous())
+    tail = (count.data_ptr(), scores.data_ptr(), labels.data_ptr(), boxes.data_ptr(),
+            None if ids[0] is None else ids[0].data_ptr(), None if ids[1] is None else ids[1].data_ptr(), N,
+            select.data_ptr(), select.shape[0], int(min_hits), margin, capacity, S_h, S_w,
+            *(t.data_ptr() for t in out), torch.cuda.current_stream().cuda_stream)
+    if packed is not None:
+        data, order = packed
+        lo, hi = _storage_bounds(data)
+        pitch = data.stride(1) if data.shape[1] > 1 else data.shape[2] * data.shape[3]
+        rc = _L().nos_chips_packed(data.data_ptr(), lo, hi, pitch, order.encode(), h, w, *tail)
+    else:
+        src, hdr = yuv
+        tables = None if hdr is None else ctypes.byref(yuv_hdr(*_hdr_device_tables(*hdr, device)))
+        rc = _L().nos_chips_yuv(ctypes.byref(src), tables, h, w, *tail)
+    _check(rc, "chips")
+    return out
