@@ -23,6 +23,9 @@
 //    shadow copy of what a blur can read: two launches, no traffic between workgroups.
 //  * Cutting (image_chips.h): chips_k, the detections of selected labels cut out of any source the patch kernel reads and
 //    resampled to one size as RGB bytes — the one kernel here that reads a surface and writes a new tensor.
+//  * Appearance (image_features.h): chip_features_k, feature_overlap_k and track_features_k — a colour descriptor per
+//    chip, its intersection with every track's, and the descriptor a track keeps — around track_update_app_f32
+//    (image_track.h), the tracker gated and re-identified by them.
 //  * Entries. The extern "C" functions at the end check every argument of an outside caller, fill the kernel's
 //    arguments and launch; the arguments all image entries share travel as one struct (Common).
 #include <hip/hip_runtime.h>
@@ -76,6 +79,7 @@ constexpr int NG = RS / 12, GROUP_FMAX_W = NG * 4 - 3;
 }  // namespace
 
 #include "image_chips.h"  // behind the source tags: chips_k is instantiated by them
+#include "image_features.h"
 
 namespace {
 
@@ -1209,6 +1213,74 @@ int nos_chips_yuv(const NosYuvSrc* src, const NosYuvHdr* hdr, int h, int w, cons
   if (hdr) return chips_launch_yuv<YuvHdrArgs>(*src, k, n, stream);
   if (src->chroma == 1) return chips_launch_yuv<YuvBilinearArgs>(*src, k, n, stream);
   return chips_launch_yuv<YuvArgs>(*src, k, n, stream);
+}
+
+int nos_features_max_stripes() { return FEAT_MAX_STRIPES; }
+int nos_features_max_shift() { return FEAT_MAX_SHIFT; }
+
+// One colour descriptor per chip (chip_features_k, image_features.h): chips [capacity][sh][sw][3] uint8 and rows
+// [capacity] int32 as the chips entries write them -> features [capacity][64 stripes] int32, zeros for a slot whose row is
+// negative; every element is written. stripes: 1, 2, 4 or 8, at most sh.
+int nos_chip_features(const void* chips, const int* rows, int capacity, int sh, int sw, int stripes, int* features,
+                      void* stream) {
+  if (!chips || !rows || !features) return fail("chip_features: null operand");
+  if (sh < 1 || sh > CHIP_MAX_SIDE || sw < 1 || sw > CHIP_MAX_SIDE) return fail("chip_features: chip sides of 1..256 pixels");
+  if (capacity < 1 || capacity > CHIP_MAX_CAPACITY) return fail("chip_features: a capacity of 1..256 chips");
+  if ((stripes != 1 && stripes != 2 && stripes != 4 && stripes != 8) || stripes > sh)
+    return fail("chip_features: 1, 2, 4 or 8 stripes, no more than the chip has rows");
+  hipLaunchKernelGGL(chip_features_k, dim3(stripes, capacity), dim3(FT), 0, reinterpret_cast<hipStream_t>(stream),
+                     static_cast<const uint8_t*>(chips), rows, sh, sw, stripes, features);
+  return check("chip_features");
+}
+
+// Histogram intersection (feature_overlap_k): F [K][D], G [T][D] int32 -> S [K][T] int32, S[k][t] = sum_d min(F, G);
+// every element is written. D is a multiple of 64 up to 512, both matrices start on a 16-byte boundary.
+int nos_feature_overlap(const int* F, const int* G, int K, int T, int D, int* S, void* stream) {
+  if (!F || !G || !S) return fail("feature_overlap: null operand");
+  if (K < 1 || K > OV_MAX_K || T < 1 || T > OV_MAX_T) return fail("feature_overlap: 1..256 chips against 1..1024 tracks");
+  if (D < OV_D || D > FEAT_MAX_D || D % OV_D) return fail("feature_overlap: a length of 64, 128, ... 512");
+  if ((reinterpret_cast<uintptr_t>(F) | reinterpret_cast<uintptr_t>(G)) & 15)
+    return fail("feature_overlap: the matrices start on a 16-byte boundary");
+  hipLaunchKernelGGL(feature_overlap_k, dim3((T + OV_TT - 1) / OV_TT, (K + OV_TK - 1) / OV_TK), dim3(FT), 0,
+                     reinterpret_cast<hipStream_t>(stream), F, G, K, T, D, S);
+  return check("feature_overlap");
+}
+
+// nos_track_update_f32 with appearance (track_update_app_f32): besides its operands S [K][T] int32 as
+// nos_feature_overlap writes it from this frame's descriptors and the state's, rows [K] the chips' rows, has [T] and
+// src [T] of the state; gate_q and reid_q the thresholds on S (reid 0: no re-identification).
+int nos_track_update_app_f32(const int* count, const float* scores, const int* labels, const float* boxes, int N,
+                             float* t_boxes, float* t_vel, int* t_labels, int* t_ids, int* t_hits, int* t_misses,
+                             int* next_id, int* dropped, int T, float match_threshold, int max_age, float birth_threshold,
+                             int motion, float velocity_gain, int* track_id, int* track_hits, const int* S,
+                             const int* rows, int K, int* has, int* src, int gate_q, int reid_q, int reid, void* stream) {
+  if (!count || !scores || !labels || !boxes || !t_boxes || !t_vel || !t_labels || !t_ids || !t_hits || !t_misses ||
+      !next_id || !dropped || !track_id || !track_hits || !S || !rows || !has || !src)
+    return fail("track_update: null operand");
+  if (N <= 0 || N > MMAX || T <= 0 || T > TMAX) return fail("track_update: 0 < rows <= 1024, 0 < slots <= 1024");
+  if (K < 1 || K > OV_MAX_K) return fail("track_update: 1..256 chip slots");
+  if (motion != 0 && motion != 1) return fail("track_update: the motion is 0 (none) or 1 (constant)");
+  if (!(match_threshold >= 0.f) || max_age < 0 || !(velocity_gain >= 0.f && velocity_gain <= 1.f))
+    return fail("track_update: match_threshold >= 0, max_age >= 0, 0 <= velocity_gain <= 1");
+  if (gate_q < 0 || reid_q < 0 || (reid != 0 && reid != 1)) return fail("track_update: thresholds on S from 0 up");
+  const TrackApp ap{S, rows, has, src, K, gate_q, reid_q, reid};
+  hipLaunchKernelGGL(track_update_app_f32, dim3(1), dim3(DT), 0, reinterpret_cast<hipStream_t>(stream), count, scores,
+                     labels, boxes, N, t_boxes, t_vel, t_labels, t_ids, t_hits, t_misses, next_id, dropped, T,
+                     match_threshold, max_age, birth_threshold, motion, velocity_gain, track_id, track_hits, ap);
+  return check("track_update_app_f32");
+}
+
+// The descriptors the tracks keep (track_features_k), after nos_track_update_app_f32: features [K][D] of this frame's
+// chips, ids / src [T] of the state -> feat [T][D] and has [T] updated in place with 2^-shift of the new descriptor.
+int nos_track_features(const int* features, int K, int D, const int* ids, const int* src, int T, int* feat, int* has,
+                       int shift, void* stream) {
+  if (!features || !ids || !src || !feat || !has) return fail("track_features: null operand");
+  if (K < 1 || K > OV_MAX_K || T < 1 || T > TMAX || D < 1 || D > FEAT_MAX_D)
+    return fail("track_features: 1..256 chips, 1..1024 slots, a length up to 512");
+  if (shift < 0 || shift > FEAT_MAX_SHIFT) return fail("track_features: a shift of 0..8");
+  hipLaunchKernelGGL(track_features_k, dim3(T), dim3(128), 0, reinterpret_cast<hipStream_t>(stream), features, K, D, ids,
+                     src, feat, has, shift);
+  return check("track_features");
 }
 
 }  // extern "C"

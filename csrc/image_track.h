@@ -5,6 +5,10 @@
 //    ordered by score (the rank count of merge_detections_f32) and passed one per barrier, each taking the untaken
 //    live track of its label whose predicted box it overlaps most (a workgroup arg-max); what stays unmatched starts
 //    tracks in the free slots (two ballot scans).
+//  * track_update_app_f32 — the same body with appearance (image_features.h's descriptors): a candidate that has a
+//    chip is compared with a track that has a descriptor by S[chip slot][track slot] of feature_overlap_k; the IoU match
+//    is gated by it, and a track that missed at least one frame can be re-identified by it where no box overlaps.
+//    track_update_f32's own instantiation (APP = false) compiles to what it was before the body became a template.
 // Included by image.hip alone, after image_detect.h (box_overlap, DT, DW, MMAX).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,14 +33,37 @@ static_assert(TMAX == DT && MMAX == DT, "one thread per track slot and per detec
 // track_id / track_hits [N], by input row: the id and hits of the row's track after the update, 0 for every other row.
 // Every trip count of a loop that holds a barrier (the number of candidates) and every pivot's outcome is read from
 // LDS by all threads. Static LDS: 12 tables of 1024 words and three of 2 x 16 = 48.4 KB.
-__global__ __launch_bounds__(DT) void track_update_f32(const int* __restrict__ count, const float* __restrict__ scores,
-                                                        const int* __restrict__ labels, const float* __restrict__ boxes,
-                                                        int N, float* __restrict__ t_boxes, float* __restrict__ t_vel,
-                                                        int* __restrict__ t_labels, int* __restrict__ t_ids,
-                                                        int* __restrict__ t_hits, int* __restrict__ t_misses,
-                                                        int* __restrict__ next_id, int* __restrict__ dropped, int T,
-                                                        float mt, int max_age, float bt, int motion, float gain,
-                                                        int* __restrict__ track_id, int* __restrict__ track_hits) {
+//
+// APP: what the appearance variant reads and writes besides. S [K][T] int32 (feature_overlap_k: chips x tracks), rows [K]
+// (chips' rows: the row a chip slot was cut from, negative for an unused slot), has [T] (the track holds a descriptor;
+// zeroed here for a slot that is free or was freed in this frame, whatever is born into it), src [T] (out: the chip slot of the candidate that matched or started the track in this frame, -1 for any other slot
+// and for a candidate without a chip), gate_q / reid_q: the thresholds on S, reid: 0 never re-identify.
+//   comparable  the candidate's row has a chip slot k and has[t] != 0; then sim = S[k][t]
+//   overlaps    IoU > mt, and not comparable or sim >= gate_q            -> the largest IoU wins (ties: the lowest slot)
+//   re-ids      reid, comparable, misses >= 1 before the frame, not overlapping, sim >= reid_q
+//                                                 -> where nothing overlaps the largest sim wins (ties: the lowest slot)
+//   re-id'd     box = the detection's, vel = 0, hits + 1, misses = 0
+// The row -> slot table (s_slot, by row, then q_slot by rank) lives in LDS: static LDS of the variant is 14 tables of
+// 1024 words, w_key 2 x 16 x 8 and two tables of 2 x 16 words = 56.5 KB (57856 bytes by the compiler, 67 VGPRs against
+// 66 without appearance). S[k][tid] of candidate p + 1 is fetched while
+// candidate p is decided (one load in flight across the barrier), so the loop does not wait a memory latency per
+// candidate on top of its barrier.
+struct TrackApp {
+  const int *S, *rows;
+  int *has, *src;
+  int K, gate_q, reid_q, reid;
+};
+
+template <bool APP>
+__device__ __forceinline__ void track_update_body(const int* __restrict__ count, const float* __restrict__ scores,
+                                                  const int* __restrict__ labels, const float* __restrict__ boxes,
+                                                  int N, float* __restrict__ t_boxes, float* __restrict__ t_vel,
+                                                  int* __restrict__ t_labels, int* __restrict__ t_ids,
+                                                  int* __restrict__ t_hits, int* __restrict__ t_misses,
+                                                  int* __restrict__ next_id, int* __restrict__ dropped, int T,
+                                                  float mt, int max_age, float bt, int motion, float gain,
+                                                  int* __restrict__ track_id, int* __restrict__ track_hits,
+                                                  const TrackApp& ap) {
   __shared__ float s_score[MMAX];                               // by row: a candidate's score, 0 for any other row
   __shared__ float q_score[MMAX];                               // by rank among the candidates
   __shared__ int q_label[MMAX], q_row[MMAX], q_id[MMAX], q_hits[MMAX];
@@ -45,6 +72,9 @@ __global__ __launch_bounds__(DT) void track_update_f32(const int* __restrict__ c
   __shared__ float w_iou[2][DW];                                // per wave, double-buffered: one barrier per candidate
   __shared__ int w_slot[2][DW];
   __shared__ int s_wave[2][DW];
+  // APP alone (a table no instantiation uses takes no LDS): the chip slot by row and by rank, the waves' best keys
+  __shared__ int s_slot[APP ? MMAX : 1], q_slot[APP ? MMAX : 1];
+  __shared__ unsigned long long w_key[2][APP ? DW : 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int first_id = next_id[0];                              // read before the first barrier, written after the last
   const int n = min(max(count[0], 0), N);
@@ -55,6 +85,7 @@ __global__ __launch_bounds__(DT) void track_update_f32(const int* __restrict__ c
   }
   if (tid < N) s_score[tid] = si;
   s_born[tid] = -1;
+  if constexpr (APP) s_slot[tid] = -1;
   // slot tid's track, in registers from here to the end
   const bool mine = tid < T;
   float box[4] = {0.f, 0.f, 0.f, 0.f}, vel[4] = {0.f, 0.f, 0.f, 0.f}, pred[4];
@@ -68,6 +99,15 @@ __global__ __launch_bounds__(DT) void track_update_f32(const int* __restrict__ c
 #pragma unroll
   for (int c = 0; c < 4; ++c) pred[c] = motion ? box[c] + vel[c] : box[c];
   __syncthreads();
+  [[maybe_unused]] int src = -1;
+  [[maybe_unused]] bool has = false;
+  if constexpr (APP) {
+    has = mine && ap.has[tid] != 0;
+    if (tid < ap.K) {  // chip slots are rows in ascending order, one slot a row
+      const int r = ap.rows[tid];
+      if (r >= 0 && r < N) s_slot[r] = tid;
+    }
+  }
   // the order: thread i counts the candidates that precede row i, and every thread the candidates
   const bool cand = si > 0.f;
   int rank = 0, ncand = 0;
@@ -86,6 +126,10 @@ __global__ __launch_bounds__(DT) void track_update_f32(const int* __restrict__ c
 #pragma unroll
     for (int c = 0; c < 4; ++c) q_box[rank * 4 + c] = boxes[tid * 4 + c];
   }
+  if constexpr (APP) {
+    __syncthreads();  // s_slot is written (the rank loop above read s_score alone)
+    if (cand) q_slot[rank] = s_slot[tid];
+  }
   __syncthreads();
   // the greedy pass: candidate p against every slot at once. Each wave reduces its 64 slots, lane 0 leaves the wave's
   // best in w_*[p & 1], and after the barrier every thread reads the waves' entries and finds the same winner. The
@@ -93,45 +137,102 @@ __global__ __launch_bounds__(DT) void track_update_f32(const int* __restrict__ c
   // barrier every thread reaches after its reads of p.
   const int nw = (T + 63) >> 6;
   bool taken = false;
-  for (int p = 0; p < ncand; ++p) {
-    const int buf = p & 1;
-    float ov = -1.f;
-    if (live && !taken && lab == q_label[p]) {
-      const float o = box_overlap(q_box + p * 4, pred, 1);
-      if (o > mt) ov = o;
-    }
-    if (wave < nw) {
-      float best = ov;
-      int slot = tid;
-      if (__ballot(ov >= 0.f)) {  // the same in every lane of the wave
+  if constexpr (!APP) {
+    for (int p = 0; p < ncand; ++p) {
+      const int buf = p & 1;
+      float ov = -1.f;
+      if (live && !taken && lab == q_label[p]) {
+        const float o = box_overlap(q_box + p * 4, pred, 1);
+        if (o > mt) ov = o;
+      }
+      if (wave < nw) {
+        float best = ov;
+        int slot = tid;
+        if (__ballot(ov >= 0.f)) {  // the same in every lane of the wave
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const float ob = __shfl_xor(best, o);
-          const int os = __shfl_xor(slot, o);
-          if (ob > best || (ob == best && os < slot)) best = ob, slot = os;
+          for (int o = 32; o > 0; o >>= 1) {
+            const float ob = __shfl_xor(best, o);
+            const int os = __shfl_xor(slot, o);
+            if (ob > best || (ob == best && os < slot)) best = ob, slot = os;
+          }
         }
+        if (lane == 0) w_iou[buf][wave] = best, w_slot[buf][wave] = slot;
       }
-      if (lane == 0) w_iou[buf][wave] = best, w_slot[buf][wave] = slot;
-    }
-    __syncthreads();
-    float best = -1.f;
-    int slot = -1;
-    for (int w = 0; w < nw; ++w) {
-      const float o = w_iou[buf][w];
-      if (o > best) best = o, slot = w_slot[buf][w];  // strictly: the lower wave keeps a tie
-    }
-    if (slot == tid) {  // a winner overlaps by more than mt >= 0, so slot stays -1 when no track qualifies
+      __syncthreads();
+      float best = -1.f;
+      int slot = -1;
+      for (int w = 0; w < nw; ++w) {
+        const float o = w_iou[buf][w];
+        if (o > best) best = o, slot = w_slot[buf][w];  // strictly: the lower wave keeps a tie
+      }
+      if (slot == tid) {  // a winner overlaps by more than mt >= 0, so slot stays -1 when no track qualifies
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float b = q_box[p * 4 + c];
-        if (motion) vel[c] += gain * ((b - box[c]) - vel[c]);
-        box[c] = b;
+        for (int c = 0; c < 4; ++c) {
+          const float b = q_box[p * 4 + c];
+          if (motion) vel[c] += gain * ((b - box[c]) - vel[c]);
+          box[c] = b;
+        }
+        hits += 1;
+        misses = 0;
+        taken = true;
+        q_id[p] = id;
+        q_hits[p] = hits;
       }
-      hits += 1;
-      misses = 0;
-      taken = true;
-      q_id[p] = id;
-      q_hits[p] = hits;
+    }
+  } else {
+    // The same pass with a key in place of the IoU: (2, the IoU's bits) for a track that overlaps, (1, sim) for one that
+    // re-identifies, 0 for neither; an IoU above mt >= 0 is a positive float, whose bits order as integers do.
+    const int* const col = ap.S + tid;
+    int k = ncand > 0 ? q_slot[0] : -1;
+    int sim = mine && k >= 0 ? col[size_t(k) * T] : 0;
+    for (int p = 0; p < ncand; ++p) {
+      const int buf = p & 1;
+      const int kn = p + 1 < ncand ? q_slot[p + 1] : -1;
+      const int simn = mine && kn >= 0 ? col[size_t(kn) * T] : 0;  // in flight until the next iteration
+      unsigned long long key = 0;
+      if (live && !taken && lab == q_label[p]) {
+        const bool comparable = k >= 0 && has;
+        const float o = box_overlap(q_box + p * 4, pred, 1);
+        if (o > mt && (!comparable || sim >= ap.gate_q)) key = 2ull << 32 | __float_as_uint(o);
+        else if (ap.reid && comparable && misses >= 1 && sim >= ap.reid_q) key = 1ull << 32 | unsigned(sim);
+      }
+      if (wave < nw) {
+        unsigned long long best = key;
+        int slot = tid;
+        if (__ballot(key != 0)) {  // the same in every lane of the wave
+#pragma unroll
+          for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long ob = __shfl_xor(best, o);
+            const int os = __shfl_xor(slot, o);
+            if (ob > best || (ob == best && os < slot)) best = ob, slot = os;
+          }
+        }
+        if (lane == 0) w_key[buf][wave] = best, w_slot[buf][wave] = slot;
+      }
+      __syncthreads();
+      unsigned long long best = 0;
+      int slot = -1;
+      for (int w = 0; w < nw; ++w) {
+        const unsigned long long o = w_key[buf][w];
+        if (o > best) best = o, slot = w_slot[buf][w];  // strictly: the lower wave keeps a tie
+      }
+      if (slot == tid) {
+        const bool reid = (best >> 32) == 1;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float b = q_box[p * 4 + c];
+          if (reid) vel[c] = 0.f;
+          else if (motion) vel[c] += gain * ((b - box[c]) - vel[c]);
+          box[c] = b;
+        }
+        hits += 1;
+        misses = 0;
+        taken = true;
+        src = k;
+        q_id[p] = id;
+        q_hits[p] = hits;
+      }
+      k = kn, sim = simn;
     }
   }
   // the live tracks nothing took
@@ -178,6 +279,11 @@ __global__ __launch_bounds__(DT) void track_update_f32(const int* __restrict__ c
       lab = q_label[k], id = q_id[k], hits = 1, misses = 0;
 #pragma unroll
       for (int c = 0; c < 4; ++c) box[c] = q_box[k * 4 + c], vel[c] = 0.f;
+      if constexpr (APP) src = q_slot[k];
+    }
+    if constexpr (APP) {
+      ap.src[tid] = src;
+      if (freed) ap.has[tid] = 0;  // a slot that died in this frame: what is born into it starts without a descriptor
     }
 #pragma unroll
     for (int c = 0; c < 4; ++c) t_boxes[tid * 4 + c] = box[c], t_vel[tid * 4 + c] = vel[c];
@@ -191,5 +297,30 @@ __global__ __launch_bounds__(DT) void track_update_f32(const int* __restrict__ c
     next_id[0] = first_id + born;
     dropped[0] += nb - born;
   }
+}
+
+__global__ __launch_bounds__(DT) void track_update_f32(const int* __restrict__ count, const float* __restrict__ scores,
+                                                        const int* __restrict__ labels, const float* __restrict__ boxes,
+                                                        int N, float* __restrict__ t_boxes, float* __restrict__ t_vel,
+                                                        int* __restrict__ t_labels, int* __restrict__ t_ids,
+                                                        int* __restrict__ t_hits, int* __restrict__ t_misses,
+                                                        int* __restrict__ next_id, int* __restrict__ dropped, int T,
+                                                        float mt, int max_age, float bt, int motion, float gain,
+                                                        int* __restrict__ track_id, int* __restrict__ track_hits) {
+  track_update_body<false>(count, scores, labels, boxes, N, t_boxes, t_vel, t_labels, t_ids, t_hits, t_misses, next_id,
+                           dropped, T, mt, max_age, bt, motion, gain, track_id, track_hits, TrackApp{});
+}
+
+__global__ __launch_bounds__(DT) void track_update_app_f32(const int* __restrict__ count, const float* __restrict__ scores,
+                                                            const int* __restrict__ labels, const float* __restrict__ boxes,
+                                                            int N, float* __restrict__ t_boxes, float* __restrict__ t_vel,
+                                                            int* __restrict__ t_labels, int* __restrict__ t_ids,
+                                                            int* __restrict__ t_hits, int* __restrict__ t_misses,
+                                                            int* __restrict__ next_id, int* __restrict__ dropped, int T,
+                                                            float mt, int max_age, float bt, int motion, float gain,
+                                                            int* __restrict__ track_id, int* __restrict__ track_hits,
+                                                            TrackApp ap) {
+  track_update_body<true>(count, scores, labels, boxes, N, t_boxes, t_vel, t_labels, t_ids, t_hits, t_misses, next_id,
+                          dropped, T, mt, max_age, bt, motion, gain, track_id, track_hits, ap);
 }
 }  // namespace

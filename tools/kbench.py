@@ -70,6 +70,14 @@ pod pays today before it can cut anything). ``chips_reference`` reads the select
 captured, so it is timed eagerly, wall time per call with the stream drained, alternating with the same eager timing
 of the HIP call: on the converted frame (``*_torch_wall_us``), from the frame itself, conversion included
 (``*_rgb_torch_wall_us``: what a pod does today), and ``*_hip_wall_us``.
+
+The appearance rows (``--rows appearance`` runs them alone) time the launches behind ``track_update(...,
+features=...)`` against their torch references, all by graph replays: ``appearance_<scene>_features_*``
+(``chip_features``), ``_overlap_*`` (``feature_overlap``), ``_track_*`` (the three launches of ``track_update`` with
+features, with the state restored before each call: ``_restore_hip_us`` is that copy alone) and ``_store_*``
+(``track_features``), on 64 chips of 128 x 64 against 256 slots, 256 against 1024, and 256 chips of 256 x 256 with 8
+stripes; then ``track_image`` on a 480x640 frame with and without an ``Appearance``
+(``appearance_track_image{,_appearance}_ms``).
 """
 from __future__ import annotations
 
@@ -118,9 +126,10 @@ def main() -> int:
     ap.add_argument("--out", default="gpurun_out/kbench.json")
     ap.add_argument("--only", choices=("all", "attn", "gemm", "model", "modes", "image"), default="all")
     ap.add_argument("--slices", default="spx,dpx,qpx,cpx")
-    ap.add_argument("--rows", choices=("all", "tiles", "track", "overlay", "mosaic", "blur", "chips"), default="all",
+    ap.add_argument("--rows", choices=("all", "tiles", "track", "overlay", "mosaic", "blur", "chips", "appearance"),
+                    default="all",
                     help="image: every row, or the tiled-detection rows alone, or the tracker's, the overlay's, the "
-                         "mosaic's, the blur's or the chips'")
+                         "mosaic's, the blur's, the chips' or the appearance rows")
     ap.add_argument("--partitions", type=int, default=0, help="modes: run only this many partitions of each mode")
     ap.add_argument("--free-s", type=float, default=0.0,
                     help="modes: serve free-running (one thread per pod, as the bench) for this many seconds "
@@ -403,6 +412,8 @@ def image_bench(a) -> int:
                 blur_rows(r, s, a.iters, rounds, whole_gpu=cus is None)
             if a.rows in ("all", "chips"):
                 chips_rows(r, s, a.iters, rounds)
+            if a.rows in ("all", "appearance"):
+                appearance_rows(r, s, a.iters, rounds)
             if not full:
                 print(json.dumps(r), flush=True)
                 results.append(r)
@@ -900,6 +911,75 @@ def chips_rows(r, s, iters, rounds):
         r[f"chips_{name}_scene"] = {"rows": n, "chips": int(want[3]), "frame": [h, w], "size": [128, 64],
                                     "box_pixels": int(((rects[:, 2] - rects[:, 0]) * (rects[:, 3] - rects[:, 1])).sum()),
                                     "hip_equals_torch": bool(same)}
+
+
+def appearance_rows(r, s, iters, rounds):
+    """The appearance launches (see the module docstring), each against its torch reference by graph replays:
+    ``appearance_<size>_{features,overlap,track,store}_{hip,torch}_us``, then ``track_image`` with and without an
+    ``Appearance`` on a 480x640 frame."""
+    import statistics
+
+    from walkai_nos_amd.models.workload.tracker import Appearance, Tracker
+    from walkai_nos_amd.models.workload.yolos import YolosSmall
+    from walkai_nos_amd.ops import image as I
+    g = torch.Generator().manual_seed(11)
+    for name, n, T, K, size, stripes in (("n100_t256_k64", 100, 256, 64, (128, 64), 4),
+                                         ("n400_t1024_k256", 400, 1024, 256, (128, 64), 4),
+                                         ("n400_t1024_k256_s8_256", 400, 1024, 256, (256, 256), 8)):
+        D, total = 64 * stripes, I.feature_total(size)
+        chips = torch.randint(0, 256, (K, *size, 3), generator=g, dtype=torch.uint8).cuda()
+        rows = torch.arange(K, dtype=torch.int32).cuda()
+        lists = [t.cuda() for t in track_scene(n, T)[1]]
+        kw = dict(features=None, feature_rows=rows, appearance_gate=0.3, reid_threshold=0.6, feature_total=total)
+        with torch.cuda.stream(s):
+            feats = I.chip_features(chips, rows, None, stripes).clone()
+            same = torch.equal(feats, I.chip_features_reference(chips, rows, None, stripes))
+            state = I.track_state(T, "cuda", features=D)
+            kw["features"] = feats
+            I.track_update(state, *lists, **kw)                 # a frame, so that tracks hold descriptors
+            saved = [t.clone() for t in state.tensors() + (state.feat, state.has, state.src)]
+            same = same and torch.equal(I.feature_overlap(feats, state.feat),
+                                        I.feature_overlap_reference(feats, state.feat))
+            s.synchronize()
+
+        def restore():
+            for t, v in zip(state.tensors() + (state.feat, state.has, state.src), saved):
+                t.copy_(v)
+        hip = {"features": lambda: I.chip_features(chips, rows, None, stripes),
+               "overlap": lambda: I.feature_overlap(feats, state.feat),
+               "track": lambda: (restore(), I.track_update(state, *lists, **kw)),
+               "store": lambda: I.track_features(state, feats, 2), "restore": restore}
+        ref = {"features": lambda: I.chip_features_reference(chips, rows, None, stripes),
+               "overlap": lambda: I.feature_overlap_reference(feats, state.feat),
+               "track": lambda: (restore(), I.track_update_reference(state, *lists, **kw)),
+               "store": lambda: I.track_features_reference(state, feats, 2)}
+        t = {}
+        for _ in range(rounds):
+            for k, fn in hip.items():
+                t.setdefault(f"{k}_hip", []).append(timeit(fn, s, iters))
+            for k, fn in ref.items():
+                t.setdefault(f"{k}_torch", []).append(timeit(fn, s, max(2, iters // 5 if k != "track" else 2)))
+        for k, vs in t.items():
+            r[f"appearance_{name}_{k}_us"] = round(statistics.median(vs), 1)
+        r[f"appearance_{name}_scene"] = {"rows": n, "slots": T, "chips": K, "size": list(size), "stripes": stripes,
+                                         "hip_equals_torch": bool(same),
+                                         "note": "track_* include restore_*; track is overlap + tracker + store"}
+        print(f"[kbench] appearance_{name}: { {k: round(statistics.median(v), 1) for k, v in t.items()} }",
+              file=sys.stderr, flush=True)
+    with torch.cuda.stream(s), torch.no_grad():
+        m = YolosSmall().cuda().eval()
+        img = torch.randint(0, 256, (480, 640, 3), generator=g, dtype=torch.uint8).cuda()
+        sc = m.detect_image(img, 0.0)["scores"].flatten().sort().values
+        thr = 0.5 * (sc[-51] + sc[-50]).item()
+        plain, looks = Tracker(device="cuda"), Tracker(device="cuda", appearance=Appearance())
+        t = {"track_image": [], "track_image_appearance": []}
+        for _ in range(rounds):
+            t["track_image"].append(timeit(lambda: m.track_image(img, plain, thr), s, max(3, iters // 4)))
+            t["track_image_appearance"].append(timeit(lambda: m.track_image(img, looks, thr), s, max(3, iters // 4)))
+    for k, vs in t.items():
+        r[f"appearance_{k}_ms"] = round(statistics.median(vs) / 1000.0, 3)
+    r["appearance_track_image_rounds_ms"] = {k: [round(v / 1000.0, 3) for v in vs] for k, vs in t.items()}
+    print(f"[kbench] appearance track_image: {r['appearance_track_image_rounds_ms']}", file=sys.stderr, flush=True)
 
 
 def free_running(slots, seconds: float) -> int:

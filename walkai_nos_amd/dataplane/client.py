@@ -34,6 +34,10 @@ launch inside the captured graph, whose replays advance the tracker; ``--track-i
 ``--track-min-hits``, ``--track-capacity``, ``--track-motion``). The tracker is reset after the warm-ups and again after
 the capture, so the timed loop starts at frame 0; the JSON line then carries a ``"track"`` block: the live tracks (and
 those of them seen in ``--track-min-hits`` frames), the ids issued, the births dropped for lack of a slot, the frames.
+``--track-appearance`` lets the tracker compare pictures too (``tracker.Appearance``: its own chips of
+``--track-appearance-size H,W`` cut before tracking, a colour histogram of ``--track-appearance-stripes`` stripes each,
+an IoU match gated at ``--track-appearance-gate`` of a descriptor and a lost track re-identified at ``--track-reid``, 0
+for never); the ``"track"`` block then says how many live tracks hold a descriptor.
 ``--annotate`` draws the detections into the frame (``YolosSmall.annotate_image`` / ``annotate_tiled``, one more launch
 inside the captured graph; with ``--track`` the tags are the ids): boxes ``--annotate-thickness`` thick, tags of glyph
 dots ``--annotate-scale`` pixels large or none with ``--no-tags``, the labels of ``--redact L1,L2,...`` filled instead
@@ -141,6 +145,14 @@ def main(argv=None) -> int:
     ap.add_argument("--track-capacity", type=int, default=256, help="--track: slots of the tracker (1..1024 run in HIP)")
     ap.add_argument("--track-motion", choices=("constant", "none"), default="constant",
                     help="--track: compare a track one frame along its velocity, or where it was")
+    ap.add_argument("--track-appearance", action="store_true", help="--track: compare colour descriptors of the boxes too")
+    ap.add_argument("--track-appearance-size", default="128,64", help="--track-appearance: H,W of the tracker's chips, 1..256 each")
+    ap.add_argument("--track-appearance-stripes", type=int, choices=(1, 2, 4, 8), default=4,
+                    help="--track-appearance: horizontal stripes of a descriptor")
+    ap.add_argument("--track-appearance-gate", type=float, default=0.0,
+                    help="--track-appearance: the fraction of a descriptor an IoU match must share (0: no gate)")
+    ap.add_argument("--track-reid", type=float, default=0.6,
+                    help="--track-appearance: the fraction at which a lost track is continued without overlap (0: never)")
     ap.add_argument("--annotate", action="store_true",
                     help="--end-to-end: draw the detections into a copy of the frame (an overlay launch in the graph)")
     ap.add_argument("--annotate-thickness", type=int, default=None, help="--annotate: a box outline's pixels (default: twice the scale)")
@@ -230,6 +242,19 @@ def main(argv=None) -> int:
             ap.error(f"--track-min-hits {args.track_min_hits} is not a number of frames from 1 up")
         if not 1 <= args.track_capacity <= 1024:
             ap.error(f"--track-capacity {args.track_capacity} is not in 1..1024")
+    looks_size = None
+    if args.track_appearance:
+        if not args.track:
+            ap.error("--track-appearance takes --track")
+        try:
+            looks_size = tuple(int(v) for v in args.track_appearance_size.split(","))
+        except ValueError:
+            looks_size = ()
+        if len(looks_size) != 2 or any(not 1 <= v <= 256 for v in looks_size) or looks_size[0] < args.track_appearance_stripes:
+            ap.error(f"--track-appearance-size {args.track_appearance_size!r} is not H,W with sides in 1..256 and H of "
+                     f"at least the {args.track_appearance_stripes} stripes")
+        if not 0.0 <= args.track_appearance_gate <= 1.0 or not 0.0 <= args.track_reid <= 1.0:
+            ap.error("--track-appearance-gate and --track-reid are fractions in [0, 1]")
     tiles = None
     if args.tiles:
         if not args.end_to_end:
@@ -306,9 +331,13 @@ def main(argv=None) -> int:
             th, tw, origins = model.processor.tile_plan((ih, iw), tiles, args.tile_overlap, model.c.num_detection_tokens)
             hw = model.processor.size((th, tw))
         if args.track:
-            from ..models.workload.tracker import Tracker
+            from ..models.workload.tracker import Appearance, Tracker
+            looks = None
+            if args.track_appearance:
+                looks = Appearance(looks_size, stripes=args.track_appearance_stripes, gate=args.track_appearance_gate,
+                                   reid_threshold=args.track_reid or None, num_labels=model.c.num_labels)
             tracker = Tracker(args.track_capacity, args.track_iou, args.track_max_age, motion=args.track_motion,
-                              min_hits=args.track_min_hits, device=dev)
+                              min_hits=args.track_min_hits, device=dev, appearance=looks)
         overlay = painted = None
         if args.annotate:
             from ..models.workload.overlay import Overlay
@@ -430,6 +459,8 @@ def main(argv=None) -> int:
                             "ids_issued": int(tracker.state.next_id.item()) - 1,
                             "dropped": int(tracker.state.dropped.item()), "frames": len(lat),
                             "capacity": tracker.capacity, "motion": args.track_motion}
+            if tracker.appearance is not None:
+                out["track"]["described"] = int((tracker.state.has != 0).sum().item())
         if overlay is not None:
             out["annotate"] = {"changed_bytes": int((painted != buf).sum().item())}
         if chips is not None:

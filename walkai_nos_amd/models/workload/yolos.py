@@ -475,15 +475,21 @@ class YolosSmall(nn.Module):
         """:meth:`detect_image` and ``tracker.update`` (``tracker.Tracker``): the same dict with ``track_id`` and
         ``track_hits`` ``[1, nd]`` int32 beside ``labels`` — the id of each row's track and the frames it has been
         seen in, 0 behind ``count``. No host synchronisation either: captured as one graph, each replay detects on the
-        frame then in the buffers and advances the tracker by one frame."""
-        return tracker.update(self.detect_image(image_u8, threshold))
+        frame then in the buffers and advances the tracker by one frame. A tracker with an ``Appearance`` cuts its own
+        chips out of the frame before it associates (no ids exist yet, so no ``min_hits`` applies to that cut),
+        describes them and compares them with its tracks' descriptors: five launches more in the same graph."""
+        if getattr(tracker, "appearance", None) is not None:
+            image_u8 = self.processor.as_batch(image_u8, self.pos_embed.device)
+        return tracker.update(self.detect_image(image_u8, threshold), image_u8)
 
     def track_tiled(self, image_u8, tracker, tiles: Tuple[int, int] = (2, 2), overlap: float = 0.2,
                     threshold: float = 0.5, match: str = "ios", match_threshold: float = 0.5) -> Dict[str, object]:
         """:meth:`detect_tiled` and ``tracker.update``: the merged list with ``track_id`` and ``track_hits``
         ``[B * nd]`` int32 beside it, capturable as :meth:`track_image` is. (``match`` and ``match_threshold`` are the
-        cross-tile merge's; the tracker's own are set on the tracker.)"""
-        return tracker.update(self.detect_tiled(image_u8, tiles, overlap, threshold, match, match_threshold))
+        cross-tile merge's; the tracker's own are set on the tracker; its ``Appearance`` cuts from the whole frame.)"""
+        if getattr(tracker, "appearance", None) is not None:
+            image_u8 = self.processor.as_batch(image_u8, self.pos_embed.device)
+        return tracker.update(self.detect_tiled(image_u8, tiles, overlap, threshold, match, match_threshold), image_u8)
 
     def annotate_image(self, frame, overlay, threshold: float = 0.5, tracker=None, target=None) -> Dict[str, object]:
         """:meth:`detect_image` — :meth:`track_image` with a ``tracker`` — and ``overlay.draw`` (``overlay.Overlay``)

@@ -174,6 +174,12 @@ def _L() -> ctypes.CDLL:
             cut = [vp] * 6 + [i32, vp] + [i32] * 6 + [vp] * 5
             L.nos_chips_packed.argtypes = [vp, vp, vp, i64, ctypes.c_char_p, i32, i32] + cut
             L.nos_chips_yuv.argtypes = [src, hdr, i32, i32] + cut
+            # the appearance entries: descriptors, their intersection, the tracker variant, the tracks' descriptors
+            L.nos_chip_features.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
+            L.nos_feature_overlap.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+            L.nos_track_update_app_f32.argtypes = L.nos_track_update_f32.argtypes[:-1] + \
+                [vp, vp, i32, vp, vp, i32, i32, i32, vp]
+            L.nos_track_features.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp]
             L.nos_image_last_error.restype = ctypes.c_char_p
             if (L.nos_overlay_tile_rows(), L.nos_overlay_tile_columns()) != OVERLAY_TILE:
                 raise NativeUnavailable(f"{LIB} was built with another overlay tile than ops/image.py expects")
@@ -184,6 +190,8 @@ def _L() -> ctypes.CDLL:
             if (L.nos_chips_max_side(), L.nos_chips_max_capacity(), L.nos_chips_max_margin()) != \
                     (CHIP_MAX_SIDE, CHIP_MAX_CAPACITY, CHIP_MAX_MARGIN):
                 raise NativeUnavailable(f"{LIB} was built with other chip limits than ops/image.py expects")
+            if (L.nos_features_max_stripes(), L.nos_features_max_shift()) != (FEATURE_STRIPES[-1], FEATURE_MAX_SHIFT):
+                raise NativeUnavailable(f"{LIB} was built with other descriptor limits than ops/image.py expects")
             if (L.nos_image_taps(), L.nos_image_max_footprint(), L.nos_image_max_patch(),
                     L.nos_image_nv12_max_footprint(), L.nos_image_yuv420p_max_footprint(),
                     L.nos_image_packed_max_footprint(), L.nos_image_yuv_max_footprint()) != \
@@ -1518,7 +1526,10 @@ class TrackState:
     the detections come in), ``vel [T, 4]`` fp32 (per-frame displacement of the four corners), ``labels``, ``ids``
     (0: a free slot; ids start at 1), ``hits`` (frames matched, birth included), ``misses`` (consecutive frames
     unmatched) ``[T]`` int32, ``next_id [1]`` and ``dropped [1]`` int32 (births refused for lack of a slot). A free
-    slot holds zeros in every field."""
+    slot holds zeros in every field. With appearance (``track_state(..., features=D)``) three more: ``feat [T, D]``
+    int32 (the track's descriptor), ``has [T]`` int32 (non-zero once it holds one) — zeros in a free slot — and ``src
+    [T]`` int32, which every :func:`track_update` with features writes in full: the chip slot of the candidate that
+    matched or started the track in that frame, -1 for every other slot."""
     boxes: torch.Tensor
     vel: torch.Tensor
     labels: torch.Tensor
@@ -1527,6 +1538,9 @@ class TrackState:
     misses: torch.Tensor
     next_id: torch.Tensor
     dropped: torch.Tensor
+    feat: Optional[torch.Tensor] = None
+    has: Optional[torch.Tensor] = None
+    src: Optional[torch.Tensor] = None
 
     @property
     def capacity(self) -> int:
@@ -1541,18 +1555,24 @@ class TrackState:
 
     def reset(self) -> None:
         """No track, ``next_id`` 1, nothing dropped: fills on the current stream, in place (capturable)."""
-        for t in self.tensors():
-            t.zero_()
+        for t in self.tensors() + (self.feat, self.has, self.src):
+            if t is not None:
+                t.zero_()
         self.next_id.fill_(1)
 
 
-def track_state(capacity: int = 256, device=None) -> TrackState:
-    """An empty :class:`TrackState` of ``capacity`` slots on ``device``."""
+def track_state(capacity: int = 256, device=None, features: Optional[int] = None) -> TrackState:
+    """An empty :class:`TrackState` of ``capacity`` slots on ``device``; ``features``: the length ``D`` of the
+    descriptors its tracks keep (:func:`chip_features`), by default none."""
     T = int(capacity)
     if T < 1:
         raise ValueError(f"track_state: capacity {capacity!r} is not a positive number of slots")
+    if features is not None and int(features) < 1:
+        raise ValueError(f"track_state: features {features!r} is not a descriptor's length")
     z = lambda *shape, dtype=torch.int32: torch.zeros(*shape, dtype=dtype, device=device)      # noqa: E731
     state = TrackState(z(T, 4, dtype=torch.float32), z(T, 4, dtype=torch.float32), z(T), z(T), z(T), z(T), z(1), z(1))
+    if features is not None:
+        state.feat, state.has, state.src = z(T, int(features)), z(T), z(T)
     state.reset()
     return state
 
@@ -1590,16 +1610,23 @@ def _track_check(state: TrackState, count, scores, labels, boxes, match_threshol
 
 def track_update_reference(state: TrackState, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor,
                            boxes: torch.Tensor, match_threshold: float = 0.3, max_age: int = 30,
-                           birth_threshold: float = 0.0, motion: str = "constant", velocity_gain: float = 0.5) \
-        -> Tuple[torch.Tensor, torch.Tensor]:
+                           birth_threshold: float = 0.0, motion: str = "constant", velocity_gain: float = 0.5,
+                           features: Optional[torch.Tensor] = None, feature_rows: Optional[torch.Tensor] = None,
+                           appearance_gate: float = 0.0, reid_threshold: Optional[float] = None,
+                           feature_shift: int = 2,
+                           feature_total: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The torch composition of :func:`track_update`, with the same effect on ``state`` in place and without a host
     sync (the greedy pass is a loop of ``N`` steps on the device, each over one row of the candidate x track IoU
-    matrix). The lists are taken in the state's fp32."""
+    matrix). The lists are taken in the state's fp32; with ``features``, :func:`feature_overlap_reference`, the
+    appearance rule and :func:`track_features_reference` in int64."""
     count, scores, labels, boxes = _track_check(state, count, scores, labels, boxes, match_threshold, max_age, motion,
                                                 velocity_gain)
+    app = None if features is None else \
+        _appearance_check(state, features, feature_rows, appearance_gate, reid_threshold, feature_shift, feature_total)
     if scores.shape[0] == 0:        # no row: one that is no candidate, and nothing to return
         none = track_update_reference(state, count, scores.new_zeros(1), labels.new_zeros(1), boxes.new_zeros(1, 4),
-                                      match_threshold, max_age, birth_threshold, motion, velocity_gain)
+                                      match_threshold, max_age, birth_threshold, motion, velocity_gain, features,
+                                      feature_rows, appearance_gate, reid_threshold, feature_shift, feature_total)
         return none[0][:0], none[1][:0]
     N, T, dev = scores.shape[0], state.capacity, state.device
     scores, boxes, labels = scores.to(torch.float32), boxes.to(torch.float32), labels.to(torch.int32)
@@ -1613,19 +1640,42 @@ def track_update_reference(state: TrackState, count: torch.Tensor, scores: torch
     pred = state.boxes + state.vel if constant else state.boxes
     ov = pair_overlap(bx[:, None, :], pred[None, :, :], "iou")
     ok = (ov > match_threshold) & (lb[:, None] == state.labels[None, :]) & live[None, :] & cd[:, None]
+    if app is not None:
+        # the chip slot of a candidate by rank, the similarity of every (candidate, track) pair, and the two conditions
+        rows_k, gate_q, reid_q = app
+        K = rows_k.shape[0]
+        held = (rows_k >= 0) & (rows_k < N)
+        slot_of = torch.full((N + 1,), -1, dtype=torch.int64, device=dev)
+        slot_of.index_copy_(0, torch.where(held, rows_k, N).to(torch.int64), torch.arange(K, device=dev))
+        ck = torch.where(cd, slot_of[:N][order], -1)
+        sim = feature_overlap_reference(features, state.feat).to(torch.int64)[ck.clamp(min=0)]
+        comparable = (ck >= 0)[:, None] & (state.has != 0)[None, :]
+        same = (lb[:, None] == state.labels[None, :]) & live[None, :] & cd[:, None]
+        ok = ok & (~comparable | (sim >= gate_q))
+        reid = same & comparable & (state.misses >= 1)[None, :] & ~ok & (sim >= reid_q) if reid_q is not None \
+            else torch.zeros_like(ok)
+        sim = torch.where(reid, sim, -1)
     ov = torch.where(ok, ov, torch.full_like(ov, -1.0))
     taken = torch.zeros(T, dtype=torch.bool, device=dev)
     match = torch.full((N,), T, dtype=torch.int64, device=dev)          # T: no track
+    again = torch.zeros(T, dtype=torch.bool, device=dev)                # the tracks matched by re-identification
     for c in range(N):
         v = torch.where(taken, -1.0, ov[c])
         best = v.max()
         slot = torch.where((v == best) & (best >= 0), slots, T).min()   # the lowest slot of the largest overlap
+        if app is not None:
+            r = torch.where(taken, -1, sim[c])
+            top = r.max()
+            other = torch.where((r == top) & (top >= 0), slots, T).min()    # the lowest slot of the largest similarity
+            again = again | ((slots == other) & (slot == T))
+            slot = torch.where(slot == T, other, slot)
         match[c] = slot
         taken = taken | (slots == slot)
     hit = match[:, None] == slots[None, :]                              # [N, T], at most a one per row and column
     rank_of = hit.to(torch.int8).argmax(0)                              # the candidate a taken track took
     box_in = bx[rank_of]
     vel = state.vel + velocity_gain * ((box_in - state.boxes) - state.vel) if constant else state.vel
+    vel = torch.where(again[:, None], 0.0, vel)
     missed = live & ~taken
     misses = torch.where(missed, state.misses + 1, torch.zeros_like(state.misses))
     dead = missed & (misses > max_age)
@@ -1667,12 +1717,21 @@ def track_update_reference(state: TrackState, count: torch.Tensor, scores: torch
     state.dropped.add_((nb - started).to(torch.int32))
     for t, new in zip(state.tensors()[:6], (new_boxes, new_vel, new_labels, new_ids, hits, misses)):
         t.copy_(new)
+    if app is not None:
+        ext = torch.cat((torch.where(taken & keep, ck[rank_of], -1), ck.new_zeros(1)))
+        ext.index_copy_(0, dest, ck)
+        state.src.copy_(ext[:T])
+        state.has.mul_(keep)
+        track_features_reference(state, features, feature_shift)
     return track_id, track_hits
 
 
 def track_update(state: TrackState, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor,
                  boxes: torch.Tensor, match_threshold: float = 0.3, max_age: int = 30, birth_threshold: float = 0.0,
-                 motion: str = "constant", velocity_gain: float = 0.5) -> Tuple[torch.Tensor, torch.Tensor]:
+                 motion: str = "constant", velocity_gain: float = 0.5, features: Optional[torch.Tensor] = None,
+                 feature_rows: Optional[torch.Tensor] = None, appearance_gate: float = 0.0,
+                 reid_threshold: Optional[float] = None, feature_shift: int = 2,
+                 feature_total: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """One frame's detections — ``count [1]`` int32, ``scores [N]``, ``labels [N]`` int32, ``boxes [N, 4]`` (corners),
     what :func:`detections` (one image; its ``[1, M]`` views are accepted) and :func:`merge_detections` return —
     associated with the tracks of ``state``, which is updated in place, with no host synchronisation: captured in a
@@ -1693,11 +1752,36 @@ def track_update(state: TrackState, count: torch.Tensor, scores: torch.Tensor, l
        (those freed in step 4 included): ``ids = next_id++``, ``hits = 1``. When the slots run out, each remaining one
        adds 1 to ``dropped``.
 
-    One HIP launch (one workgroup) for fp32 lists up to 1024 rows and a state up to 1024 slots; past that, for other
-    dtypes, on the CPU and with the ``torch`` backend :func:`track_update_reference`."""
+    **Appearance.** With ``features [K, D]`` int32 and ``feature_rows [K]`` int32 — :func:`chip_features` of this
+    frame's chips and the chips' ``rows`` — on a state made with ``track_state(..., features=D)``, rule 2 compares
+    pictures too. ``feature_total`` is what every descriptor sums to, ``4096 S_h S_w`` (:func:`feature_total`; left
+    out, it is read from ``features`` on the host, which synchronises and cannot be captured); the thresholds are
+    ``gate_q = ceil(appearance_gate * total)`` and ``reid_q = ceil(reid_threshold * total)``. For candidate ``p`` in
+    score order and each live, untaken track ``t`` of its label:
+
+    * they are *comparable* when ``p``'s row holds chip slot ``k`` and ``has[t] != 0``; then ``sim = S[k][t]``
+      (:func:`feature_overlap` of ``features`` and ``state.feat``);
+    * ``t`` *overlaps* when ``IoU > match_threshold`` and it is not comparable or ``sim >= gate_q``;
+    * ``t`` *re-identifies* when ``reid_threshold`` is given, it is comparable, ``misses[t] >= 1`` before this frame,
+      it does not overlap and ``sim >= reid_q``;
+    * the winner is the overlapping track of largest IoU (ties: the lowest slot), and where none overlaps the
+      re-identifying track of largest ``sim`` (ties: the lowest slot). A track matched by overlap updates as in rule
+      3; one matched by re-identification takes the box bit for bit, ``vel = 0``, ``hits += 1``, ``misses = 0``.
+
+    ``state.src`` then holds, per slot, the chip slot of the candidate that matched or started its track in this frame
+    (-1 for any other slot and for a candidate without a chip), ``has`` of a slot that is free or was freed in this
+    frame is zeroed (what is born into it starts without a descriptor), and :func:`track_features` keeps the
+    descriptors: three launches, :func:`feature_overlap`, ``track_update_app_f32``, ``track_features_k``.
+
+    One HIP launch (one workgroup) for fp32 lists up to 1024 rows and a state up to 1024 slots — with features, up to
+    256 chip slots and descriptors of 64..512 — ; past that, for other dtypes, on the CPU and with the ``torch``
+    backend :func:`track_update_reference`."""
     lists = _track_check(state, count, scores, labels, boxes, match_threshold, max_age, motion, velocity_gain)
     count, scores, labels, boxes = lists
     N, T = scores.shape[0], state.capacity
+    if features is not None:
+        return _track_update_app(state, lists, match_threshold, max_age, birth_threshold, motion, velocity_gain,
+                                 features, feature_rows, appearance_gate, reid_threshold, feature_shift, feature_total)
     if not _use_hip(scores) or scores.dtype != torch.float32 or boxes.dtype != torch.float32 \
             or labels.dtype != torch.int32 or count.dtype != torch.int32 or N > MAX_ROWS or T > MAX_TRACKS or N < 1:
         return track_update_reference(state, *lists, match_threshold, max_age, birth_threshold, motion, velocity_gain)
@@ -2583,3 +2667,200 @@ def chips(frame, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor
         rc = _L().nos_chips_yuv(ctypes.byref(src), tables, h, w, *tail)
     _check(rc, "chips")
     return out
+
+
+# ---- what a chip looks like: descriptors for the tracker ---------------------------------------------------
+#: stripes a chip is split into, the length of a stripe's histogram, and the largest blend shift (``image_features.h``)
+FEATURE_STRIPES, FEATURE_BINS, FEATURE_MAX_SHIFT = (1, 2, 4, 8), 64, 8
+#: the kernels' limits on the overlap matrix: chips, tracks, descriptor length
+FEATURE_MAX_LENGTH = FEATURE_BINS * FEATURE_STRIPES[-1]
+
+#: the descriptors per (device, capacity, D) and the overlap matrix per (device, capacity, T), kept as the chip buffers
+_feature_buffers = GraphCache(16)
+
+
+def feature_total(size) -> int:
+    """What every descriptor of a chip of ``size = (S_h, S_w)`` sums to: ``4096 S_h S_w``."""
+    return 4096 * int(size[0]) * int(size[1])
+
+
+def _features_check(chips: torch.Tensor, rows: torch.Tensor, stripes: int) -> Tuple[int, int, int]:
+    if chips.dim() != 4 or chips.shape[-1] != 3 or chips.dtype != torch.uint8 or 0 in chips.shape:
+        raise ValueError("chip_features: chips is a uint8 [capacity, S_h, S_w, 3] tensor")
+    K, S_h, S_w = chips.shape[:3]
+    if rows.shape != (K,) or rows.device != chips.device:
+        raise ValueError(f"chip_features: rows is [{K}] on the chips' device")
+    if stripes not in FEATURE_STRIPES or stripes > S_h:
+        raise ValueError(f"chip_features: stripes {stripes!r} is none of {FEATURE_STRIPES} up to the chip's {S_h} rows")
+    return K, S_h, S_w
+
+
+def chip_features_reference(chips: torch.Tensor, rows: torch.Tensor, chip_count: Optional[torch.Tensor] = None,
+                            stripes: int = 4) -> torch.Tensor:
+    """The torch composition of :func:`chip_features` in int64, on any device and for any size, without a host sync."""
+    K, S_h, S_w = _features_check(chips, rows, stripes)
+    dev = chips.device
+    p = (chips.to(torch.int64) - 32).clamp(0, 192)                      # [K, S_h, S_w, 3]
+    k, f = p >> 6, (p & 63) >> 2
+    # row y lies in stripe s when s S_h // stripes <= y: s = ceil((y + 1) stripes / S_h) - 1
+    stripe = (((torch.arange(S_h, device=dev) + 1) * stripes - 1) // S_h)[:, None].expand(S_h, S_w)
+    out = torch.zeros((K, stripes * FEATURE_BINS), dtype=torch.int64, device=dev)
+    for c in range(8):
+        up = [(c >> 2) & 1, (c >> 1) & 1, c & 1]
+        w = torch.ones_like(p[..., 0])
+        b = torch.zeros_like(w)
+        for ch in range(3):
+            w = w * (f[..., ch] if up[ch] else 16 - f[..., ch])
+            b = b * 4 + (k[..., ch] + up[ch]).clamp(max=3)
+        out.scatter_add_(1, (stripe[None] * FEATURE_BINS + b).reshape(K, -1), w.reshape(K, -1))
+    return torch.where((rows >= 0)[:, None], out, 0).to(torch.int32)
+
+
+def chip_features(chips: torch.Tensor, rows: torch.Tensor, chip_count: Optional[torch.Tensor] = None,
+                  stripes: int = 4) -> torch.Tensor:
+    """One colour descriptor per chip of :func:`chips` — ``chips [capacity, S_h, S_w, 3]`` uint8, ``rows [capacity]``
+    int32, ``chip_count [1]`` (not read: ``rows`` says which slots are used) — as ``features [capacity, 64 stripes]``
+    int32, with no host synchronisation: horizontal stripes of a joint RGB histogram with soft bins, the classic
+    descriptor that :func:`feature_overlap` compares by histogram intersection. The rule, in exact integers:
+
+    * stripe ``s`` of ``stripes`` (1, 2, 4 or 8, at most ``S_h``) holds chip rows ``s S_h // stripes .. (s + 1) S_h //
+      stripes - 1``;
+    * a channel value ``v`` gives ``p = clamp(v - 32, 0, 192)``, ``k = p >> 6``, ``f = (p & 63) >> 2``: bin ``k`` of
+      4 gets weight ``16 - f`` and bin ``min(k + 1, 3)`` weight ``f`` (bin centres at 32, 96, 160 and 224);
+    * a pixel votes ``w_r w_g w_b`` into joint bin ``(k_r 4 + k_g) 4 + k_b`` of its stripe: up to 8 bins, 4096 in all;
+    * so every descriptor sums to ``4096 S_h S_w`` (:func:`feature_total`), at most 2^28; the row of a slot with
+      ``rows[k] < 0`` is zeros. Every element is written by every call.
+
+    One HIP launch (``chip_features_k``: a workgroup per stripe and slot, a histogram copy per lane in LDS,
+    ``csrc/image_features.h``) into a buffer cached per (device, capacity, length) for sides and capacities up to 256
+    on the GPU; past that, on the CPU and with the ``torch`` backend :func:`chip_features_reference`. Learned
+    embeddings are not offered."""
+    K, S_h, S_w = _features_check(chips, rows, stripes)
+    if not _use_hip(chips) or rows.dtype != torch.int32 or max(S_h, S_w) > CHIP_MAX_SIDE or K > CHIP_MAX_CAPACITY:
+        return chip_features_reference(chips, rows, chip_count, stripes)
+    D = FEATURE_BINS * stripes
+    out = _feature_buffers.get(("features", str(chips.device), K, D),
+                               lambda: torch.empty((K, D), dtype=torch.int32, device=chips.device))
+    chips, rows = chips.contiguous(), rows.contiguous()
+    rc = _L().nos_chip_features(chips.data_ptr(), rows.data_ptr(), K, S_h, S_w, stripes, out.data_ptr(),
+                                torch.cuda.current_stream().cuda_stream)
+    _check(rc, "chip_features")
+    return out
+
+
+def _overlap_check(features: torch.Tensor, t_feat: torch.Tensor) -> Tuple[int, int, int]:
+    if features.dim() != 2 or t_feat.dim() != 2 or features.shape[1] != t_feat.shape[1] or 0 in features.shape \
+            or 0 in t_feat.shape or features.device != t_feat.device:
+        raise ValueError(f"feature_overlap: features [K, D] and t_feat [T, D] on one device, not "
+                         f"{tuple(features.shape)} and {tuple(t_feat.shape)}")
+    return features.shape[0], t_feat.shape[0], features.shape[1]
+
+
+def feature_overlap_reference(features: torch.Tensor, t_feat: torch.Tensor) -> torch.Tensor:
+    """The torch composition of :func:`feature_overlap` in int64 (a block of tracks at a time)."""
+    K, T, D = _overlap_check(features, t_feat)
+    a, b = features.to(torch.int64), t_feat.to(torch.int64)
+    out = [torch.minimum(a[:, None, :], b[None, t:t + 64, :]).sum(-1) for t in range(0, T, 64)]
+    return torch.cat(out, dim=1).to(torch.int32)
+
+
+def feature_overlap(features: torch.Tensor, t_feat: torch.Tensor) -> torch.Tensor:
+    """Histogram intersection of every chip with every track: ``S[k][t] = sum_d min(features[k][d], t_feat[t][d])``,
+    int32 ``[K, T]``, every element written by every call, with no host synchronisation. A row of zeros on either side
+    gives zero, a descriptor with itself its total.
+
+    One HIP launch (``feature_overlap_k``, a tiled (min, +) product through LDS, ``csrc/image_features.h``) into a
+    buffer cached per (device, K, T) for int32 descriptors of 64, 128, ... 512, up to 256 chips and 1024 tracks on the
+    GPU; past that, on the CPU and with the ``torch`` backend :func:`feature_overlap_reference`."""
+    K, T, D = _overlap_check(features, t_feat)
+    if not _use_hip(features) or features.dtype != torch.int32 or t_feat.dtype != torch.int32 \
+            or K > CHIP_MAX_CAPACITY or T > MAX_TRACKS or D > FEATURE_MAX_LENGTH or D % FEATURE_BINS:
+        return feature_overlap_reference(features, t_feat)
+    features, t_feat = features.contiguous(), t_feat.contiguous()
+    if (features.data_ptr() | t_feat.data_ptr()) & 15:
+        return feature_overlap_reference(features, t_feat)
+    out = _feature_buffers.get(("overlap", str(features.device), K, T),
+                               lambda: torch.empty((K, T), dtype=torch.int32, device=features.device))
+    rc = _L().nos_feature_overlap(features.data_ptr(), t_feat.data_ptr(), K, T, D, out.data_ptr(),
+                                  torch.cuda.current_stream().cuda_stream)
+    _check(rc, "feature_overlap")
+    return out
+
+
+def track_features_reference(state: TrackState, features: torch.Tensor, shift: int = 2) -> None:
+    """The torch composition of :func:`track_features`."""
+    live, src = state.ids != 0, state.src.to(torch.int64)
+    new = features.to(torch.int64)[src.clamp(0, features.shape[0] - 1)]
+    old = state.feat.to(torch.int64)
+    blend = old + ((new - old + ((1 << shift) >> 1)) >> shift)
+    fed = live & (src >= 0)
+    out = torch.where((fed & (state.has != 0))[:, None], blend, torch.where(fed[:, None], new, old))
+    state.feat.copy_(torch.where(live[:, None], out, 0))
+    state.has.copy_(torch.where(live, state.has | fed.to(torch.int32), 0))
+
+
+def track_features(state: TrackState, features: torch.Tensor, shift: int = 2) -> None:
+    """The descriptors the tracks keep, after a :func:`track_update` with features has written ``state.src``, in place
+    and with no host synchronisation. A slot with ``ids == 0`` gets zeros in ``feat`` and ``has``; a slot with ``src >=
+    0`` and ``has == 0`` copies ``features[src]`` and sets ``has = 1``; one with ``src >= 0`` and ``has != 0`` takes,
+    per bin, ``old + floor((new - old + 2^(shift - 1)) / 2^shift)`` (a copy at ``shift = 0``); any other slot is left
+    alone. One HIP launch (``track_features_k``) where :func:`track_update` takes its HIP route. Galleries of more
+    than one descriptor a track are not offered."""
+    K, T, D = _overlap_check(features, state.feat)
+    if not 0 <= int(shift) <= FEATURE_MAX_SHIFT:
+        raise ValueError(f"track_features: shift {shift!r} is not in 0..{FEATURE_MAX_SHIFT}")
+    if not _use_hip(features) or features.dtype != torch.int32 or K > CHIP_MAX_CAPACITY or T > MAX_TRACKS \
+            or D > FEATURE_MAX_LENGTH:
+        return track_features_reference(state, features, int(shift))
+    features = features.contiguous()
+    rc = _L().nos_track_features(features.data_ptr(), K, D, state.ids.data_ptr(), state.src.data_ptr(), T,
+                                 state.feat.data_ptr(), state.has.data_ptr(), int(shift),
+                                 torch.cuda.current_stream().cuda_stream)
+    _check(rc, "track_features")
+
+
+def _appearance_check(state: TrackState, features, feature_rows, gate, reid, shift, total) -> tuple:
+    """The appearance arguments of :func:`track_update` checked: ``(rows [K], gate_q, reid_q or None)``."""
+    who = "track_update"
+    if state.feat is None:
+        raise ValueError(f"{who}: features take a state made with track_state(..., features=D)")
+    K, _, D = _overlap_check(features, state.feat)
+    if feature_rows is None or feature_rows.shape != (K,) or feature_rows.device != state.device \
+            or features.device != state.device:
+        raise ValueError(f"{who}: feature_rows is the chips' rows, [{K}] on the state's device")
+    if not 0.0 <= float(gate) <= 1.0 or (reid is not None and not 0.0 <= float(reid) <= 1.0):
+        raise ValueError(f"{who}: appearance_gate {gate!r} and reid_threshold {reid!r} are fractions of a descriptor")
+    if not 0 <= int(shift) <= FEATURE_MAX_SHIFT:
+        raise ValueError(f"{who}: feature_shift {shift!r} is not in 0..{FEATURE_MAX_SHIFT}")
+    if total is None:
+        total = int(features.sum(dim=1, dtype=torch.int64).max())      # a host read: pass feature_total to capture
+    q = lambda v: int(math.ceil(float(v) * int(total)))                 # noqa: E731
+    return feature_rows, q(gate), None if reid is None else q(reid)
+
+
+def _track_update_app(state: TrackState, lists, match_threshold, max_age, birth_threshold, motion, velocity_gain,
+                      features, feature_rows, gate, reid, shift, total) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`track_update` with features: the three launches, or the reference outside their limits."""
+    count, scores, labels, boxes = lists
+    rows, gate_q, reid_q = _appearance_check(state, features, feature_rows, gate, reid, shift, total)
+    N, T, (K, D) = scores.shape[0], state.capacity, features.shape
+    i32 = torch.int32
+    if not _use_hip(scores) or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or labels.dtype != i32 \
+            or count.dtype != i32 or features.dtype != i32 or rows.dtype != i32 or N > MAX_ROWS or N < 1 \
+            or T > MAX_TRACKS or K > CHIP_MAX_CAPACITY or D > FEATURE_MAX_LENGTH or D % FEATURE_BINS \
+            or max(gate_q, reid_q or 0) >= 1 << 31:
+        return track_update_reference(state, *lists, match_threshold, max_age, birth_threshold, motion, velocity_gain,
+                                      features, feature_rows, gate, reid, shift, total)
+    S = feature_overlap(features, state.feat)
+    scores, labels, boxes, rows = scores.contiguous(), labels.contiguous(), boxes.contiguous(), rows.contiguous()
+    track_id = torch.empty(N, dtype=i32, device=scores.device)
+    track_hits = torch.empty(N, dtype=i32, device=scores.device)
+    rc = _L().nos_track_update_app_f32(
+        count.data_ptr(), scores.data_ptr(), labels.data_ptr(), boxes.data_ptr(), N,
+        *(t.data_ptr() for t in state.tensors()), T, float(match_threshold), int(max_age), float(birth_threshold),
+        MOTIONS[motion], float(velocity_gain), track_id.data_ptr(), track_hits.data_ptr(), S.data_ptr(),
+        rows.data_ptr(), K, state.has.data_ptr(), state.src.data_ptr(), gate_q, reid_q or 0, int(reid_q is not None),
+        torch.cuda.current_stream().cuda_stream)
+    _check(rc, "track_update")
+    track_features(state, features, int(shift))
+    return track_id, track_hits
