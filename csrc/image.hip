@@ -23,6 +23,8 @@
 //    shadow copy of what a blur can read: two launches, no traffic between workgroups.
 //  * Cutting (image_chips.h): chips_k, the detections of selected labels cut out of any source the patch kernel reads and
 //    resampled to one size as RGB bytes — the one kernel here that reads a surface and writes a new tensor.
+//  * Resizing (image_scale.h): rescale_k, a frame resized into a second surface of the same layout by the chips' exact
+//    area average, plane by plane — the one kernel here that writes a frame it did not read.
 //  * Appearance (image_features.h): chip_features_k, feature_overlap_k and track_features_k — a colour descriptor per
 //    chip, its intersection with every track's, and the descriptor a track keeps — around track_update_app_f32
 //    (image_track.h), the tracker gated and re-identified by them.
@@ -42,6 +44,7 @@
 #include "image_overlay.h"
 #include "image_mosaic.h"
 #include "image_blur.h"
+#include "image_scale.h"
 #include "image_yuv.h"
 
 namespace {
@@ -728,6 +731,47 @@ int chips_launch_yuv(const NosYuvSrc& s, const ChipArgs& k, const YuvHdrArgs& n,
       yuv_dispatch<A>(s, [](auto y) -> ChipKernel<A> { return chips_k<Src::YUV, A, decltype(y)>; });
   return chips_launch(kernel, k, A(n), stream, "chips_yuv");
 }
+
+// One storage plane of a rescale whose slots share one lattice: P slots a period, `comps` of them components.
+ScalePlane scale_plane(const PlaneArg& s, const PlaneArg& d, int ph, int pw, int PH, int PW, int P, int comps) {
+  ScalePlane q{};
+  q.src = s.p, q.dst = const_cast<uint8_t*>(d.p), q.spitch = s.pitch, q.dpitch = d.pitch;
+  q.ph = ph, q.PH = PH, q.P = P, q.pw[0] = pw, q.PW[0] = PW;
+  for (int k = 0; k < comps; ++k) q.slots |= uint32_t(1 | k << 2) << (8 * k);
+  q.src_slots = pw * P, q.tiles_x = PW, q.unit = comps == 2 ? 1 : 0;
+  return q;
+}
+
+// The grid and the launch of both rescale entries: k.pl[0 .. np - 1] hold the planes, tiles_x their periods.
+int rescale_launch(ScaleArgs& k, int np, void* stream, const char* what) {
+  bool wide = false;
+  for (int i = 0; i < np; ++i) {
+    ScalePlane& q = k.pl[i];
+    for (int c = 0; c < 2; ++c) {
+      if (q.PW[c] == 0) continue;
+      q.area[c] = uint32_t(q.ph) * uint32_t(q.pw[c]), q.inv[c] = 1.0 / double(q.area[c]);
+      wide = wide || (uint64_t(q.area[c]) * (uint64_t(k.mask) + 1) > (1ull << 32));
+    }
+    const int TP = SCALE_T / q.P;
+    q.tiles_x = (q.tiles_x + TP - 1) / TP;
+  }
+  // a band of 8 rows, halved while the grid would hold fewer than 1024 workgroups
+  int grid = 0;
+  for (k.band = SCALE_BAND;; k.band /= 2) {
+    grid = 0;
+    for (int i = 0; i < np; ++i) {
+      k.pl[i].bands = (k.pl[i].PH + k.band - 1) / k.band, k.pl[i].first = grid;
+      grid += k.pl[i].tiles_x * k.pl[i].bands;
+    }
+    if (grid >= 1024 || k.band == 1) break;
+  }
+  for (int i = np; i < 3; ++i) k.pl[i].first = grid;
+  hipLaunchKernelGGL(wide ? rescale_k<true> : rescale_k<false>, dim3(grid), dim3(SCALE_T), 0,
+                     reinterpret_cast<hipStream_t>(stream), k);
+  return check(what);
+}
+
+bool ranges_meet(const PlaneArg& a, const PlaneArg& b) { return a.lo < b.hi && b.lo < a.hi; }
 }  // namespace
 
 extern "C" {
@@ -1213,6 +1257,75 @@ int nos_chips_yuv(const NosYuvSrc* src, const NosYuvHdr* hdr, int h, int w, cons
   if (hdr) return chips_launch_yuv<YuvHdrArgs>(*src, k, n, stream);
   if (src->chroma == 1) return chips_launch_yuv<YuvBilinearArgs>(*src, k, n, stream);
   return chips_launch_yuv<YuvArgs>(*src, k, n, stream);
+}
+
+int nos_rescale_row_chunk() { return SCALE_ROWS; }
+int nos_rescale_column_chunk() { return SCALE_SLOTS; }
+int nos_rescale_tile() { return SCALE_T; }
+int nos_rescale_max_side() { return SCALE_MAX_SIDE; }
+
+// The packed pixels src [h][w][C] resized into dst [H][W][C] of the same order (pitches and [lo, hi) as in
+// nos_overlay_packed; crop views are read and written in place): every colour byte of dst is the exact area average
+// of its component (image_scale.h), the fourth byte of a four-byte pixel is neither read into a result nor written.
+// Sides of 1..8192; the two storage ranges must not meet. Nothing is launched unless every check passes.
+int nos_rescale_packed(const void* src, const void* slo, const void* shi, long long spitch, int h, int w, void* dst,
+                       const void* dlo, const void* dhi, long long dpitch, int H, int W, const char* order,
+                       void* stream) {
+  if (!src || !dst || !order) return fail("rescale: null operand");
+  if (h < 1 || w < 1 || H < 1 || W < 1 || std::max(std::max(h, w), std::max(H, W)) > SCALE_MAX_SIDE)
+    return fail("rescale: sides of 1..8192 pixels");
+  PackedDst s{}, d{};
+  if (const int rc = packed_dst("rescale_packed", s, const_cast<void*>(src), slo, shi, spitch, order, h, w)) return rc;
+  if (const int rc = packed_dst("rescale_packed", d, dst, dlo, dhi, dpitch, order, H, W)) return rc;
+  if (ranges_meet(s.s, d.s)) return fail("rescale_packed: the source's and the target's storage meet");
+  ScaleArgs k{};
+  k.pl[0] = scale_plane(s.s, d.s, h, w, H, W, s.C, 3);
+  k.sb = 1, k.shift = 0, k.mask = 255;
+  return rescale_launch(k, 1, stream, "rescale_packed");
+}
+
+// The same between the one h x w frame src and the one H x W frame dst of a YUV surface (the checks of
+// nos_overlay_yuv on either side): both descriptors agree in layout, subsampling, sample format and order; every
+// sample plane is resized on its own lattice, a 16-bit sample stored whole as code << shift.
+int nos_rescale_yuv(const NosYuvSrc* src, int h, int w, const NosYuvSrc* dst, int H, int W, void* stream) {
+  if (!src || !dst) return fail("rescale: null operand");
+  if (src->size != int(sizeof(NosYuvSrc)) || dst->size != int(sizeof(NosYuvSrc)))
+    return fail("rescale_yuv: descriptor size mismatch (NosYuvSrc of another build)");
+  if (h < 1 || w < 1 || H < 1 || W < 1 || std::max(std::max(h, w), std::max(H, W)) > SCALE_MAX_SIDE)
+    return fail("rescale: sides of 1..8192 pixels");
+  YuvDst s{}, d{};
+  if (const int rc = yuv_dst("rescale_yuv", s, *src, h, w)) return rc;
+  if (const int rc = yuv_dst("rescale_yuv", d, *dst, H, W)) return rc;
+  if (s.layout != d.layout || s.hsub != d.hsub || s.vsub != d.vsub || s.sb != d.sb || src->depth != dst->depth ||
+      s.shift != d.shift || s.order != d.order)
+    return fail("rescale_yuv: the source and the target differ in layout, subsampling, sample format or order");
+  const int np = s.layout == YUV_PACKED ? 1 : s.layout == YUV_SEMI ? 2 : 3;
+  for (int i = 0; i < np; ++i)
+    for (int j = 0; j < np; ++j)
+      if (ranges_meet(s.pl[i], d.pl[j])) return fail("rescale_yuv: the source's and the target's storage meet");
+  const int ch = (h + (1 << s.vsub) - 1) >> s.vsub, cw = (w + (1 << s.hsub) - 1) >> s.hsub;
+  const int CH = (H + (1 << s.vsub) - 1) >> s.vsub, CW = (W + (1 << s.hsub) - 1) >> s.hsub;
+  ScaleArgs k{};
+  k.sb = s.sb, k.shift = s.shift, k.mask = (1 << src->depth) - 1;
+  if (s.layout == YUV_PACKED) {
+    // a macropixel: luma (class 0, two columns) at slots yo and yo + 2, the chroma components (class 1) at the others
+    ScalePlane& q = k.pl[0];
+    q = scale_plane(s.pl[0], d.pl[0], h, w, H, W, 4, 0);
+    q.pw[1] = cw, q.PW[1] = CW, q.ns[0] = 1, q.src_slots = 4 * cw, q.tiles_x = CW, q.unit = 2;
+    const int yo = s.order == 1 ? 1 : 0;
+    for (int slot = 0; slot < 4; ++slot) {
+      const bool luma = (slot & 1) == yo;
+      q.slots |= uint32_t(luma ? (1 | yo << 2 | (slot >> 1) << 4) : (2 | slot << 2)) << (8 * slot);
+    }
+  } else {
+    k.pl[0] = scale_plane(s.pl[0], d.pl[0], h, w, H, W, 1, 1);
+    if (s.layout == YUV_SEMI) {
+      k.pl[1] = scale_plane(s.pl[1], d.pl[1], ch, cw, CH, CW, 2, 2);
+    } else {
+      for (int i = 1; i < 3; ++i) k.pl[i] = scale_plane(s.pl[i], d.pl[i], ch, cw, CH, CW, 1, 1);
+    }
+  }
+  return rescale_launch(k, np, stream, "rescale_yuv");
 }
 
 int nos_features_max_stripes() { return FEAT_MAX_STRIPES; }

@@ -71,6 +71,12 @@ captured, so it is timed eagerly, wall time per call with the stream drained, al
 of the HIP call: on the converted frame (``*_torch_wall_us``), from the frame itself, conversion included
 (``*_rgb_torch_wall_us``: what a pod does today), and ``*_hip_wall_us``.
 
+Seven rows time the scaler (``--rows scale`` runs them alone): ``scale_2160p_nv12_to_1080p_*`` and ``_to_720p_*``, the
+same from ``rgb`` and ``p010``, and ``scale_1080p_nv12_to_720p_*``: ``ops.image.rescale`` (``*_hip_us``) against
+``rescale_reference`` (``*_torch_us``), a device copy of the source's bytes (``*_copy_us``, the floor) and, for NV12,
+``rgb()`` then ``F.interpolate(mode="area")`` (``*_rgb_area_us``: what a pod pays today, with no conversion back — not
+the same output, a cost comparison only), all by graph replays, medians of three alternating rounds.
+
 The appearance rows (``--rows appearance`` runs them alone) time the launches behind ``track_update(...,
 features=...)`` against their torch references, all by graph replays: ``appearance_<scene>_features_*``
 (``chip_features``), ``_overlap_*`` (``feature_overlap``), ``_track_*`` (the three launches of ``track_update`` with
@@ -126,10 +132,10 @@ def main() -> int:
     ap.add_argument("--out", default="gpurun_out/kbench.json")
     ap.add_argument("--only", choices=("all", "attn", "gemm", "model", "modes", "image"), default="all")
     ap.add_argument("--slices", default="spx,dpx,qpx,cpx")
-    ap.add_argument("--rows", choices=("all", "tiles", "track", "overlay", "mosaic", "blur", "chips", "appearance"),
+    ap.add_argument("--rows", choices=("all", "tiles", "track", "overlay", "mosaic", "blur", "chips", "appearance", "scale"),
                     default="all",
                     help="image: every row, or the tiled-detection rows alone, or the tracker's, the overlay's, the "
-                         "mosaic's, the blur's, the chips' or the appearance rows")
+                         "mosaic's, the blur's, the chips', the appearance or the scaler's rows")
     ap.add_argument("--partitions", type=int, default=0, help="modes: run only this many partitions of each mode")
     ap.add_argument("--free-s", type=float, default=0.0,
                     help="modes: serve free-running (one thread per pod, as the bench) for this many seconds "
@@ -414,6 +420,8 @@ def image_bench(a) -> int:
                 chips_rows(r, s, a.iters, rounds)
             if a.rows in ("all", "appearance"):
                 appearance_rows(r, s, a.iters, rounds)
+            if a.rows in ("all", "scale"):
+                scale_rows(r, s, a.iters, rounds)
             if not full:
                 print(json.dumps(r), flush=True)
                 results.append(r)
@@ -910,6 +918,59 @@ def chips_rows(r, s, iters, rounds):
         rects = want[2][:int(want[3])].cpu()
         r[f"chips_{name}_scene"] = {"rows": n, "chips": int(want[3]), "frame": [h, w], "size": [128, 64],
                                     "box_pixels": int(((rects[:, 2] - rects[:, 0]) * (rects[:, 3] - rects[:, 1])).sum()),
+                                    "hip_equals_torch": bool(same)}
+
+
+def scale_rows(r, s, iters, rounds):
+    """The scaler (see the module docstring): ``scale_*_hip_us`` against ``*_torch_us`` (``rescale_reference``),
+    ``*_copy_us`` (a device copy of the source's bytes: the floor) and, for NV12, ``*_rgb_area_us`` (``rgb()`` then
+    ``F.interpolate(mode="area")``, what a pod does today: another output, a cost comparison only), all by graph
+    replays; ``*_scene`` says whether the kernel's target equalled the reference's."""
+    import statistics
+
+    import torch.nn.functional as F
+
+    from walkai_nos_amd.models.workload import surfaces
+    from walkai_nos_amd.models.workload.processor import Nv12
+    from walkai_nos_amd.models.workload.scaler import Scaler
+    from walkai_nos_amd.ops import image as I
+    g = torch.Generator().manual_seed(11)
+    cases = [(fmt, 2160, 3840, out) for fmt in ("nv12", "rgb", "p010") for out in ((1080, 1920), (720, 1280))] \
+        + [("nv12", 1080, 1920, (720, 1280))]
+    for fmt, h, w, (H, W) in cases:
+        name = f"{h}p_{fmt}_to_{H}p"
+        if fmt == "rgb":
+            buf = torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8).cuda()
+            frame = buf
+        else:
+            pitch = -(-w * (2 if fmt == "p010" else 1) // 256) * 256
+            buf = torch.randint(0, 256, (pitch * h * 3 // 2,), generator=g, dtype=torch.uint8).cuda()
+            frame = Nv12.from_buffer(buf, h, w, pitch) if fmt == "nv12" else surfaces.from_buffer(fmt, buf, h, w, pitch)
+        scaler, spare = Scaler((H, W)), torch.empty_like(buf)
+        target = scaler.target(frame)
+        planes = (target,) if fmt == "rgb" else tuple(getattr(target, k) for k in target.PLANES)
+        with torch.cuda.stream(s):
+            scaler.scale(frame)
+            got = [t.clone() for t in planes]
+            for t in planes:
+                t.zero_()
+            I.rescale_reference(frame, target)
+            same = all(torch.equal(a, b) for a, b in zip(got, planes))
+            s.synchronize()
+        fns = {"hip": lambda: I.rescale(frame, target), "torch": lambda: I.rescale_reference(frame, target),
+               "copy": lambda: spare.copy_(buf)}
+        if fmt == "nv12":
+            fns["rgb_area"] = lambda: F.interpolate(frame.rgb().permute(0, 3, 1, 2).float(), size=(H, W), mode="area")
+        t = {k: [] for k in fns}
+        for _ in range(rounds):
+            for k, fn in fns.items():
+                t[k].append(timeit(fn, s, iters if k != "torch" else max(2, iters // 5)))
+        for k, vs in t.items():
+            r[f"scale_{name}_{k}_us"] = round(statistics.median(vs), 1)
+        r[f"scale_{name}_rounds_us"] = {k: [round(v, 1) for v in vs] for k, vs in t.items()}
+        print(f"[kbench] scale_{name}: {r[f'scale_{name}_rounds_us']}", file=sys.stderr, flush=True)
+        r[f"scale_{name}_scene"] = {"frame": [h, w], "size": [H, W], "source_bytes": buf.numel(),
+                                    "target_bytes": sum(t.numel() * t.element_size() for t in planes),
                                     "hip_equals_torch": bool(same)}
 
 

@@ -54,6 +54,9 @@ more launch inside the captured graph) as RGB chips of ``--chip-size H,W`` (defa
 (default 64) a frame, each box grown by ``--chip-margin`` pixels first; it goes with ``--tiles``, ``--track``, every
 ``--pixel-format`` and ``--transfer``. With ``--annotate`` the chips are cut before the frame is painted. The JSON line
 then carries ``"chips": {"count": ..., "nonzero_bytes": ...}`` of the last inference.
+``--scale-out H,W`` resizes the frame — with ``--annotate`` the painted one — to that size in its own layout
+(``scaler.Scaler``, ``ops.image.rescale``: one more launch inside the captured graph, no RGB frame) on every SDR
+``--pixel-format``; the JSON line then carries ``"scaled": {"hw": [H, W], "nonzero_bytes": ...}``.
 """
 from __future__ import annotations
 
@@ -170,7 +173,20 @@ def main(argv=None) -> int:
     ap.add_argument("--chip-size", default=None, help="--chips: H,W of every chip, 1..256 each (default 128,64)")
     ap.add_argument("--chip-capacity", type=int, default=None, help="--chips: the chips of one frame, 1..256 (default 64)")
     ap.add_argument("--chip-margin", type=int, default=None, help="--chips: pixels added around a box, 0..64 (default 0)")
+    ap.add_argument("--scale-out", default="", help="--end-to-end: H,W: the (annotated) frame resized to that size in its own layout")
     args = ap.parse_args(argv)
+    scale_out = None
+    if args.scale_out:
+        if not args.end_to_end:
+            ap.error("--scale-out takes --end-to-end")
+        if args.transfer != "sdr":
+            ap.error(f"--scale-out resizes SDR surfaces: it is not offered with --transfer {args.transfer}")
+        try:
+            scale_out = tuple(int(v) for v in args.scale_out.split(","))
+        except ValueError:
+            scale_out = ()
+        if len(scale_out) != 2 or any(not 1 <= v <= 8192 for v in scale_out):
+            ap.error(f"--scale-out {args.scale_out!r} is not H,W with sides in 1..8192")
     chip_labels = chip_size = None
     if args.chips:
         if not args.end_to_end:
@@ -353,7 +369,18 @@ def main(argv=None) -> int:
             chips = Chips(chip_size, chip_labels, 64 if args.chip_capacity is None else args.chip_capacity,
                           args.chip_margin or 0, args.track_min_hits if args.track else 1, model.c.num_labels)
 
+        scaler = None
+        if scale_out is not None:
+            from ..models.workload.scaler import Scaler
+            scaler = Scaler(scale_out)
+
         def infer():
+            det = detect()
+            if scaler is not None and "scaled" not in det:      # (annotate_image and annotate_tiled scale what they painted)
+                det = {**det, "scaled": scaler.scale(det.get("frame", img))}
+            return det
+
+        def detect():
             if chips is not None:
                 if tiles is not None:
                     det = model.chip_tiled(img, chips, tiles, args.tile_overlap, args.threshold, args.match,
@@ -368,8 +395,8 @@ def main(argv=None) -> int:
                 painted.copy_(buf)
                 if tiles is not None:
                     return model.annotate_tiled(img, overlay, tiles, args.tile_overlap, args.threshold, args.match,
-                                                args.match_threshold, tracker, target)
-                return model.annotate_image(img, overlay, args.threshold, tracker, target)
+                                                args.match_threshold, tracker, target, scaler)
+                return model.annotate_image(img, overlay, args.threshold, tracker, target, scaler)
             if tracker is not None:
                 if tiles is not None:
                     return model.track_tiled(img, tracker, tiles, args.tile_overlap, args.threshold, args.match,
@@ -465,6 +492,10 @@ def main(argv=None) -> int:
             out["annotate"] = {"changed_bytes": int((painted != buf).sum().item())}
         if chips is not None:
             out["chips"] = {"count": int(res["chip_count"].item()), "nonzero_bytes": int((res["chips"] != 0).sum().item())}
+        if scale_out is not None:
+            scaled = res["scaled"]
+            planes = (scaled,) if isinstance(scaled, torch.Tensor) else tuple(getattr(scaled, k) for k in scaled.PLANES)
+            out["scaled"] = {"hw": list(scale_out), "nonzero_bytes": sum(int((t != 0).sum().item()) for t in planes)}
     if census is not None:
         out["census"] = census
     out["hbm"] = _shim()

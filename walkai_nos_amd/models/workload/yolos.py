@@ -491,29 +491,40 @@ class YolosSmall(nn.Module):
             image_u8 = self.processor.as_batch(image_u8, self.pos_embed.device)
         return tracker.update(self.detect_tiled(image_u8, tiles, overlap, threshold, match, match_threshold), image_u8)
 
-    def annotate_image(self, frame, overlay, threshold: float = 0.5, tracker=None, target=None) -> Dict[str, object]:
+    def annotate_image(self, frame, overlay, threshold: float = 0.5, tracker=None, target=None,
+                       scaler=None) -> Dict[str, object]:
         """:meth:`detect_image` — :meth:`track_image` with a ``tracker`` — and ``overlay.draw`` (``overlay.Overlay``)
         into ``target``: the same dict with ``"frame"``, the painted target, added. One more launch (more where the
         overlay pixelates or blurs labels: the mosaic, the blur's two, then the drawing) and no host synchronisation:
         frame in, annotated (redacted, pixelated, blurred) frame out is still one capturable graph. ``target`` is a
         surface of the frame's size (the boxes are in the frame's pixels) and defaults to ``frame`` itself, painted in
         place: a decoder writes the next frame over it before the next replay. With ``target=None`` a replay on an
-        unchanged buffer therefore detects on the annotated frame, not on the one that was put there."""
+        unchanged buffer therefore detects on the annotated frame, not on the one that was put there. With a ``scaler``
+        (``scaler.Scaler``) the painted surface is resized after the drawing, one more launch inside the same graph, and
+        the dict gains ``"scaled"``: a frame of the surface's class and layout at the scaler's size."""
         det = self.detect_image(frame, threshold) if tracker is None else self.track_image(frame, tracker, threshold)
-        return {**det, "frame": overlay.draw(det, frame if target is None else target)}
+        return self._painted(det, overlay.draw(det, frame if target is None else target), scaler)
+
+    @staticmethod
+    def _painted(det: Dict[str, object], painted, scaler) -> Dict[str, object]:
+        """The dict of :meth:`annotate_image` and :meth:`annotate_tiled`: ``"frame"``, and ``"scaled"`` with a scaler."""
+        out = {**det, "frame": painted}
+        if scaler is not None:
+            out["scaled"] = scaler.scale(painted)
+        return out
 
     def annotate_tiled(self, frame, overlay, tiles: Tuple[int, int] = (2, 2), overlap: float = 0.2,
                        threshold: float = 0.5, match: str = "ios", match_threshold: float = 0.5, tracker=None,
-                       target=None) -> Dict[str, object]:
+                       target=None, scaler=None) -> Dict[str, object]:
         """:meth:`detect_tiled` — :meth:`track_tiled` with a ``tracker`` — and ``overlay.draw`` of the merged list into
         ``target``, as :meth:`annotate_image` (the mosaic and the blur of an overlay that pixelates or blurs labels included): with
         ``target=None`` the frame itself is painted, and a replay on an unchanged buffer detects on the annotated
-        frame."""
+        frame; with a ``scaler`` the painted surface is resized as there."""
         if tracker is None:
             det = self.detect_tiled(frame, tiles, overlap, threshold, match, match_threshold)
         else:
             det = self.track_tiled(frame, tracker, tiles, overlap, threshold, match, match_threshold)
-        return {**det, "frame": overlay.draw(det, frame if target is None else target)}
+        return self._painted(det, overlay.draw(det, frame if target is None else target), scaler)
 
     def chip_image(self, frame, chips, threshold: float = 0.5, tracker=None) -> Dict[str, object]:
         """:meth:`detect_image` — :meth:`track_image` with a ``tracker`` — and ``chips.cut`` (``chips.Chips``): the same

@@ -88,6 +88,11 @@ which is also what runs on the CPU, with the ``torch`` backend and past a layout
   launch on every layout, chroma mode and transfer the front end reads, PQ / HLG included (``csrc/image_chips.h``).
   :func:`chips_reference` is the torch composition. Aspect-preserving or letterboxed chips, bilinear or bicubic
   enlargement, float or normalised output, rotated boxes, batches and more than 256 chips are not offered.
+* :func:`rescale` — the write side's second surface: a frame resized into a target of the same layout, depth,
+  subsampling and byte order at any other size by one launch, plane by plane, with the exact area average
+  :func:`chip_weights` defines per axis (``csrc/image_scale.h``); :func:`rescale_reference` is the torch composition.
+  Bilinear, bicubic and Lanczos resizing, changing layout, depth or subsampling while resizing, PQ / HLG surfaces,
+  batches, sides above 8192 on the GPU route and resizing in place are not offered.
 """
 from __future__ import annotations
 
@@ -180,7 +185,12 @@ def _L() -> ctypes.CDLL:
             L.nos_track_update_app_f32.argtypes = L.nos_track_update_f32.argtypes[:-1] + \
                 [vp, vp, i32, vp, vp, i32, i32, i32, vp]
             L.nos_track_features.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp]
+            # a surface and its size on either side of both rescale entries
+            L.nos_rescale_packed.argtypes = [vp, vp, vp, i64, i32, i32] * 2 + [ctypes.c_char_p, vp]
+            L.nos_rescale_yuv.argtypes = [src, i32, i32] * 2 + [vp]
             L.nos_image_last_error.restype = ctypes.c_char_p
+            if L.nos_rescale_max_side() != RESCALE_MAX_SIDE:
+                raise NativeUnavailable(f"{LIB} was built with another largest rescale side than ops/image.py expects")
             if (L.nos_overlay_tile_rows(), L.nos_overlay_tile_columns()) != OVERLAY_TILE:
                 raise NativeUnavailable(f"{LIB} was built with another overlay tile than ops/image.py expects")
             if (L.nos_mosaic_tile_rows(), L.nos_mosaic_tile_columns()) != MOSAIC_TILE:
@@ -298,12 +308,13 @@ _tables = GraphCache(16)
 
 
 def invalidate_cache() -> None:
-    """Drop every cached tap table, tile-origin table, HDR table, overlay table and chip buffer, also those a captured graph holds: capture such
-    graphs again."""
+    """Drop every cached tap table, tile-origin table, HDR table, overlay table, chip buffer and scaled frame, also those a captured graph
+    holds: capture such graphs again."""
     _tables.clear()
     _hdr_tables.clear()
     _overlay_tables.clear()
     _chip_buffers.clear()
+    _scale_buffers.clear()
 
 
 def _make_tables(h: int, w: int, H: int, W: int, p: int, device: torch.device) -> Optional[tuple]:
@@ -2667,6 +2678,118 @@ def chips(frame, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor
         rc = _L().nos_chips_yuv(ctypes.byref(src), tables, h, w, *tail)
     _check(rc, "chips")
     return out
+
+
+# ---- a frame resized into a second surface of its own layout ---------------------------------------------
+#: the largest side of either frame on the HIP route of :func:`rescale` (``csrc/image_scale.h``)
+RESCALE_MAX_SIDE = 8192
+
+#: the planes of ``models/workload/scaler.py``'s targets per (device, layout, size), kept as :data:`_chip_buffers` are
+_scale_buffers = GraphCache(16)
+
+
+def _rescale_check(frame, target) -> Tuple[OverlaySurface, OverlaySurface]:
+    """Both surfaces of :func:`rescale` described and checked, ``ValueError`` before any launch: SDR, one frame each
+    (:func:`overlay_surface`), one device, the same kind, storage that does not meet."""
+    who = "rescale"
+    s, d = overlay_surface(frame), overlay_surface(target)
+    if s.device != d.device:
+        raise ValueError(f"{who}: the frame is on {s.device}, the target on {d.device}")
+    if (s.packed is None) != (d.packed is None):
+        raise ValueError(f"{who}: a packed frame and a YUV frame are not of one kind (no colour conversion here)")
+    if s.packed is not None:
+        if s.packed[1] != d.packed[1]:
+            raise ValueError(f"{who}: the frame is {s.packed[1]}, the target {d.packed[1]}")
+        held = ((s.packed[0],), (d.packed[0],))
+    else:
+        kind = lambda v: (v[0], v[2], v[3], v[4], v[5])       # noqa: E731  (layout, subsampling, depth, msb, order)
+        if kind(s.yuv) != kind(d.yuv):
+            raise ValueError(f"{who}: the frame is (layout, subsampling, depth, msb, order) = {kind(s.yuv)}, the "
+                             f"target {kind(d.yuv)}")
+        if s.yuv[0] == YUV_PLANAR:
+            # which of U and V lies first, where both lie in one allocation on either side (I420 against YV12)
+            first = [v[1][1].data_ptr() < v[1][2].data_ptr() for v in (s.yuv, d.yuv)
+                     if _storage_bounds(v[1][1]) == _storage_bounds(v[1][2])]
+            if len(first) == 2 and first[0] != first[1]:
+                raise ValueError(f"{who}: U lies first in one surface and V in the other")
+        held = (s.yuv[1], d.yuv[1])
+    for a in held[0]:
+        for b in held[1]:
+            (alo, ahi), (blo, bhi) = _storage_bounds(a), _storage_bounds(b)
+            if alo < bhi and blo < ahi:
+                raise ValueError(f"{who}: the frame's and the target's storage meet (resizing in place is not offered)")
+    return s, d
+
+
+def _plane_codes(view: torch.Tensor, shift: int, depth: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(bits, codes)`` of a sample plane: the view a result is stored through (16-bit words as int16) and what
+    :func:`yuv_codes` reads of it, int32."""
+    if view.dtype == torch.uint8:
+        return view, view.to(torch.int32)
+    bits = view if view.dtype == torch.int16 else view.view(torch.int16)
+    return bits, ((bits.to(torch.int32) & 0xffff) >> shift) & ((1 << depth) - 1)
+
+
+def rescale_reference(frame, target):
+    """The torch composition of :func:`rescale`, with the same effect on ``target`` on any device and for any size,
+    without a host sync: per sample plane ``Wy @ codes @ Wx^T`` in float64 with :func:`chip_weights` — exact, every
+    term is an integer below 2^53 — then ``(sum + A // 2) // A`` in int64, stored through the plane's strided view (a
+    16-bit word whole, as ``code << shift``)."""
+    s, d = _rescale_check(frame, target)
+    depth = 8 if s.yuv is None else s.yuv[3]
+    for (sv, _, _, _), (dv, _, _, _) in zip(s.samples, d.samples):
+        _, codes = _plane_codes(sv, s.shift, depth)
+        bits, _ = _plane_codes(dv, d.shift, depth)
+        (ph, pw), (PH, PW) = codes.shape, bits.shape
+        A = ph * pw
+        total = chip_weights(ph, PH, s.device) @ codes.to(torch.float64) @ chip_weights(pw, PW, s.device).t()
+        out = torch.div(total.to(torch.int64) + A // 2, A, rounding_mode="floor") << d.shift
+        bits.copy_(out.to(torch.uint8) if bits.dtype == torch.uint8 else ((out + 32768) % 65536 - 32768).to(torch.int16))
+    return target
+
+
+def rescale(frame, target):
+    """``frame`` resized into ``target``, a second surface of the same kind and any other size, with no host
+    synchronisation, no RGB frame and no colour conversion; returns ``target``. Both are what :func:`overlay_surface`
+    takes (a uint8 ``[h, w, 3]`` tensor or a ``Packed``, ``Nv12``, ``Yuv420p``, ``YuvPlanar``, ``YuvSemiPlanar`` or
+    ``Yuyv`` frame; pitched rows and crop views are read and written through their strides), SDR, one frame each. They
+    agree in kind — the same packed order, or the same YUV layout, subsampling, depth, ``msb`` and component order
+    (``vu``, the YUYV order, which of U and V lies first) — and their storage does not meet; a frame or a pair that breaks
+    any of this is a ``ValueError`` before any launch. The size is no such condition: any two sizes are served (a side
+    above :data:`RESCALE_MAX_SIDE` by the reference, below). The rule, in exact integers:
+
+    1. Each sample plane of the target (``OverlaySurface.samples``: the three colour bytes of a packed pixel, or Y, U
+       and V) is computed from the plane of the same component of the source, ``ph x pw`` to ``PH x PW`` samples — the
+       chroma planes of a subsampled surface ``ceil(h / 2^vsub) x ceil(w / 2^hsub)`` — each on its own lattice. A
+       uniform resize keeps chroma where the stream's siting says it lies relative to luma, so no siting is taken.
+    2. A sample's code is what :func:`yuv_codes` reads (the byte, or ``(word >> shift) & mask``). With ``Wy =
+       chip_weights(ph, PH)``, ``Wx = chip_weights(pw, PW)`` and ``A = ph pw``: ``out[J][I] = (sum_y sum_x Wy[J][y]
+       Wx[I][x] code[y][x] + A // 2) // A`` — the box filter when shrinking, replication with blended seams when
+       enlarging, a copy at equal sizes, :func:`mosaic`'s rounded mean at an integer ratio.
+    3. The result is stored as the byte, or as the whole 16-bit word ``out << shift`` (a P010 word's low bits become 0).
+    4. Every sample of every plane of the target is written by every call, and nothing else: not the pitch padding, not
+       the parent of a crop, not the fourth byte of RGBA / BGRA (which reaches no result either), no byte of the source.
+
+    One HIP launch (``rescale_k``: a workgroup per tile of whole storage units of the target and band of rows,
+    ``csrc/image_scale.h``) on the GPU for sides of 1..:data:`RESCALE_MAX_SIDE`; past that, on the CPU and with the
+    ``torch`` backend :func:`rescale_reference`. Bilinear, bicubic and Lanczos resizing, changing layout, depth or
+    subsampling on the way, PQ / HLG surfaces, batches, and resizing in place are not offered."""
+    s, d = _rescale_check(frame, target)
+    if not _use_hip(d.samples[0][0]) or max(s.h, s.w, d.h, d.w) > RESCALE_MAX_SIDE:
+        return rescale_reference(frame, target)
+    stream = torch.cuda.current_stream().cuda_stream
+    if s.packed is not None:
+        ends = []
+        for data, _ in (s.packed, d.packed):
+            lo, hi = _storage_bounds(data)
+            ends.append((data.data_ptr(), lo, hi, data.stride(1) if data.shape[1] > 1 else data.shape[2] * data.shape[3],
+                         data.shape[1], data.shape[2]))
+        rc = _L().nos_rescale_packed(*ends[0], *ends[1], s.packed[1].encode(), stream)
+    else:
+        src, dst = yuv_src(*s.yuv, (0,) * 12), yuv_src(*d.yuv, (0,) * 12)
+        rc = _L().nos_rescale_yuv(ctypes.byref(src), s.h, s.w, ctypes.byref(dst), d.h, d.w, stream)
+    _check(rc, "rescale")
+    return target
 
 
 # ---- what a chip looks like: descriptors for the tracker ---------------------------------------------------
