@@ -467,25 +467,36 @@ int yuv_format(const NosYuvSrc& s) {
   return 0;
 }
 
-// The planes of a descriptor whose format is known, holding sB frames of sh x sw, as pl[0..2]: every plane's first
-// and last sample inside its storage [lo, hi). cw x ch: the size of a chroma plane in samples.
-int yuv_planes(const NosYuvSrc& s, int sB, int sh, int sw, PlaneArg* pl, long long& cw, long long& ch) {
-  const bool packed = s.layout == YUV_PACKED;
-  // rows and row bytes of every plane
+// The storage planes of one frame: how many there are, the rows and the row bytes of each, and for a YUV surface
+// cw x ch, the size of a chroma plane in samples.
+struct PlaneSizes {
+  int np;
+  long long rows[3], rowbytes[3], cw, ch;
+};
+
+// Those of a YUV surface of h x w whose format is known.
+PlaneSizes yuv_sizes(const NosYuvSrc& s, int h, int w) {
+  const bool packed = s.layout == YUV_PACKED, semi = s.layout == YUV_SEMI;
   const long long SB = s.sample_bytes;
-  cw = (sw + (1LL << s.hsub) - 1) >> s.hsub, ch = (sh + (1LL << s.vsub) - 1) >> s.vsub;
-  const int np = packed ? 1 : s.layout == YUV_SEMI ? 2 : 3;
-  const long long rows[3] = {sh, ch, ch};
-  const long long rowbytes[3] = {packed ? 4 * ((sw + 1LL) / 2) : sw * SB, s.layout == YUV_SEMI ? 2 * cw * SB : cw * SB,
-                                 cw * SB};
-  for (int i = 0; i < np; ++i) {
+  PlaneSizes z{packed ? 1 : semi ? 2 : 3};
+  z.cw = (w + (1LL << s.hsub) - 1) >> s.hsub, z.ch = (h + (1LL << s.vsub) - 1) >> s.vsub;
+  z.rows[0] = h, z.rows[1] = z.rows[2] = z.ch;
+  z.rowbytes[0] = packed ? 4 * ((w + 1LL) / 2) : w * SB;       // a macropixel of two pixels is four bytes
+  z.rowbytes[1] = semi ? 2 * z.cw * SB : z.cw * SB, z.rowbytes[2] = z.cw * SB;
+  return z;
+}
+
+// The planes of a descriptor whose format is known, holding sB frames of sh x sw, as pl[0..2]: every plane's first
+// and last sample inside its storage [lo, hi). z: yuv_sizes of sh x sw.
+int yuv_planes(const NosYuvSrc& s, int sB, const PlaneSizes& z, PlaneArg* pl) {
+  for (int i = 0; i < z.np; ++i) {
     const PlaneArg q = plane_arg(s.plane[i].p, s.plane[i].lo, s.plane[i].hi, s.plane[i].pitch, s.plane[i].bstride);
     if (!q.p) return fail("image_patch_planes: null operand");
-    if (q.pitch < rowbytes[i]) return fail("image_patch_planes_yuv: a plane's pitch is smaller than its row's bytes");
+    if (q.pitch < z.rowbytes[i]) return fail("image_patch_planes_yuv: a plane's pitch is smaller than its row's bytes");
     if (!stride_range(q)) return fail("image_patch_planes_yuv: pitch or batch stride out of range");
-    if (SB == 2 && ((reinterpret_cast<uintptr_t>(q.p) | uintptr_t(q.pitch) | uintptr_t(q.bs)) & 1))
+    if (s.sample_bytes == 2 && ((reinterpret_cast<uintptr_t>(q.p) | uintptr_t(q.pitch) | uintptr_t(q.bs)) & 1))
       return fail("image_patch_planes_yuv: 16-bit planes lie at an even address with an even pitch and batch stride");
-    if (!inside(sB, q, rows[i], rowbytes[i]))
+    if (!inside(sB, q, z.rows[i], z.rowbytes[i]))
       return fail("image_patch_planes_yuv: a plane does not lie inside its storage bounds");
     pl[i] = q;
   }
@@ -502,15 +513,15 @@ int yuv_source(const NosYuvSrc& s, YuvBilinearArgs& n, int sB, int sh, int sw) {
     return fail("image_patch_planes_yuv: unknown chroma siting (bit 0 horizontally, bit 1 vertically co-sited)");
   if (s.chroma == 1 && s.hsub == 0)
     return fail("image_patch_planes_yuv: bilinear chroma takes a subsampled source (4:4:4 is launched as nearest)");
-  long long cw = 0, ch = 0;
-  if (const int rc = yuv_planes(s, sB, sh, sw, n.pl, cw, ch)) return rc;
+  const PlaneSizes z = yuv_sizes(s, sh, sw);
+  if (const int rc = yuv_planes(s, sB, z, n.pl)) return rc;
   if (!table_ok(s.tab, s.depth))
     return fail("image_patch_planes_yuv: colour table: coefficients below 2^23 in size, offsets below 2^depth");
   for (int i = 0; i < 12; ++i) n.tab[i] = s.tab[i];
   n.vsub = s.vsub, n.depth = s.depth, n.shift = s.shift, n.mask = (1 << s.depth) - 1, n.order = s.order;
   // co-sited: (4, 0) of C[i], C[i] at an even position, held as (0, 4) of C[i - 1], C[i], and (2, 2) at an odd one;
   // centred: (1, 3) and (3, 1)
-  n.cw = int(cw), n.ch = int(ch);
+  n.cw = int(z.cw), n.ch = int(z.ch);
   static const int cosited[4] = {0, 4, 2, 2}, centred[4] = {1, 3, 3, 1};
   for (int i = 0; i < 4; ++i)
     n.wx[i] = (s.siting & 1 ? cosited : centred)[i], n.wy[i] = (s.siting & 2 ? cosited : centred)[i];
@@ -561,43 +572,56 @@ int yuv_launch(const NosYuvSrc& s, bool hdr, const ImgArgs& k, const YuvHdrArgs&
   if (s.chroma == 1) return yuv_launch_as<YuvBilinearArgs>(s, k, n, f, grid, stream, what);
   return yuv_launch_as<YuvArgs>(s, k, n, f, grid, stream, what);
 }
-// What the overlay and mosaic entries check of one frame's lists, of the [L] table of labels and of the frame's size.
-int list_args(const char* who, int h, int w, const int* count, const float* scores, const int* labels,
-              const float* boxes, const int* track_id, const int* track_hits, int N, const void* table, int L,
-              int min_hits) {
+// One frame's lists as the effect entries take them: N rows, track_id and track_hits both null or both given, the [L]
+// table of labels (modes or select, uint8), and min_hits.
+struct Lists {
+  const int* count;
+  const float* scores;
+  const int* labels;
+  const float* boxes;
+  const int *track_id, *track_hits;
+  const void* table;
+  int N, L, min_hits;
+};
+
+// What every effect entry checks of one frame's lists and of the frame's size.
+int list_args(const char* who, int h, int w, const Lists& l) {
   const char* msg = nullptr;
-  if (!count || !scores || !labels || !boxes || !table) msg = ": null operand";
-  else if ((track_id == nullptr) != (track_hits == nullptr)) msg = ": track_id and track_hits go together";
+  if (!l.count || !l.scores || !l.labels || !l.boxes || !l.table) msg = ": null operand";
+  else if ((l.track_id == nullptr) != (l.track_hits == nullptr)) msg = ": track_id and track_hits go together";
   else if (h <= 0 || w <= 0 || h > (1 << 15) || w > (1 << 15)) msg = ": a frame of 1..32768 rows and columns";
-  else if (N <= 0 || N > OMAX) msg = ": 0 < rows <= 1024";
-  else if (L <= 0 || min_hits < 1) msg = ": labels > 0, min_hits >= 1";
+  else if (l.N <= 0 || l.N > OMAX) msg = ": 0 < rows <= 1024";
+  else if (l.L <= 0 || l.min_hits < 1) msg = ": labels > 0, min_hits >= 1";
   return msg ? fail(who, msg) : 0;
 }
 
 // What both overlay entries check of the lists, the tables and the parameters, and fill of k.
-int overlay_args(OverlayArgs& k, int h, int w, const int* count, const float* scores, const int* labels,
-                 const float* boxes, const int* track_id, const int* track_hits, int N, const void* modes, int L,
-                 const int* codes, int K, const int* font, int thickness, int scale, int min_hits) {
+int overlay_args(OverlayArgs& k, int h, int w, const Lists& l, const int* codes, int K, const int* font, int thickness,
+                 int scale) {
   if (!codes || !font) return fail("overlay: null operand");
-  if (const int rc = list_args("overlay", h, w, count, scores, labels, boxes, track_id, track_hits, N, modes, L, min_hits))
-    return rc;
+  if (const int rc = list_args("overlay", h, w, l)) return rc;
   if (K <= 0 || K > OVERLAY_MAX_K) return fail("overlay: 0 < colours <= 1024");
   if (thickness < 1 || thickness > OVERLAY_MAX_T || scale < 0 || scale > OVERLAY_MAX_S)
     return fail("overlay: 1 <= thickness <= 2^20, 0 <= scale <= 1024");
-  k = OverlayArgs{count, scores, labels, boxes, track_id, track_hits, static_cast<const uint8_t*>(modes), codes, font,
-                  N, L, K, thickness, scale, min_hits, h, w};
+  k = OverlayArgs{l.count, l.scores, l.labels, l.boxes, l.track_id, l.track_hits, static_cast<const uint8_t*>(l.table),
+                  codes, font, l.N, l.L, K, thickness, scale, l.min_hits, h, w};
   return 0;
 }
 
-// What both mosaic entries check and fill of k (mask is the surface's, filled by the entry).
-int mosaic_args(MosaicArgs& k, int h, int w, const int* count, const float* scores, const int* labels,
-                const float* boxes, const int* track_id, const int* track_hits, int N, const void* select, int L,
-                int min_hits, int cell) {
-  if (const int rc = list_args("mosaic", h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits))
-    return rc;
+// What the selecting effects (who: mosaic, blur, chips) check of the lists, and the MosaicArgs they share: no cell, the
+// mask of a byte (a YUV entry fills in the surface's).
+int select_args(const char* who, MosaicArgs& m, int h, int w, const Lists& l) {
+  if (const int rc = list_args(who, h, w, l)) return rc;
+  m = MosaicArgs{l.count, l.scores, l.labels, l.boxes, l.track_id, l.track_hits, static_cast<const uint8_t*>(l.table),
+                 l.N, l.L, l.min_hits, h, w, 0, 255};
+  return 0;
+}
+
+// What both mosaic entries check and fill of k.
+int mosaic_args(MosaicArgs& k, int h, int w, const Lists& l, int cell) {
+  if (const int rc = select_args("mosaic", k, h, w, l)) return rc;
   if (cell < MOSAIC_MIN_CELL || cell > MTILE || (cell & (cell - 1))) return fail("mosaic: a cell of 4, 8, 16, 32 or 64 pixels");
-  k = MosaicArgs{count, scores, labels, boxes, track_id, track_hits, static_cast<const uint8_t*>(select), N, L, min_hits,
-                 h, w, cell, 255};
+  k.cell = cell;
   return 0;
 }
 
@@ -630,35 +654,31 @@ int packed_dst(const char* who, PackedDst& dst, void* img, const void* lo, const
   return 0;
 }
 
-// The checks both YUV entries (who: overlay_yuv, mosaic_yuv) make of the descriptor's format and planes; fills d.
+// What the YUV effect entries open with: the descriptor is there ("<effect>: ...") and of this build ("<entry>: ...").
+int yuv_open(const char* effect, const char* entry, const NosYuvSrc* s) {
+  if (!s) return fail(effect, ": null operand");
+  if (s->size != int(sizeof(NosYuvSrc))) return fail(entry, ": descriptor size mismatch (NosYuvSrc of another build)");
+  return 0;
+}
+
+// The checks the YUV effect entries (who: overlay_yuv, ...) make of the descriptor's format and planes; fills d.
 int yuv_dst(const char* who, YuvDst& d, const NosYuvSrc& s, int h, int w) {
-  long long cw = 0, ch = 0;
-  if (yuv_format(s) || yuv_planes(s, 1, h, w, d.pl, cw, ch)) return fail(who, ": the surface: " + g_err);
+  if (yuv_format(s) || yuv_planes(s, 1, yuv_sizes(s, h, w), d.pl)) return fail(who, ": the surface: " + g_err);
   d.layout = s.layout, d.hsub = s.hsub, d.vsub = s.vsub, d.sb = s.sample_bytes, d.shift = s.shift, d.order = s.order;
   return 0;
 }
-// The rows and the row bytes of the np planes of a YUV surface of h x w whose format is known (yuv_planes' own).
-int yuv_plane_sizes(const NosYuvSrc& s, int h, int w, long long* rows, long long* rowbytes) {
-  const long long SB = s.sample_bytes, cw = (w + (1LL << s.hsub) - 1) >> s.hsub, ch = (h + (1LL << s.vsub) - 1) >> s.vsub;
-  const bool packed = s.layout == YUV_PACKED;
-  rows[0] = h, rows[1] = rows[2] = ch;
-  rowbytes[0] = packed ? 4 * ((w + 1LL) / 2) : w * SB, rowbytes[1] = s.layout == YUV_SEMI ? 2 * cw * SB : cw * SB;
-  rowbytes[2] = cw * SB;
-  return packed ? 1 : s.layout == YUV_SEMI ? 2 : 3;
-}
 
-// The shadow of np planes (image_blur.h): plane i lies behind plane i - 1 at its own pitch, at its own address modulo
+// The shadow of z.np planes (image_blur.h): plane i lies behind plane i - 1 at its own pitch, at its own address modulo
 // 4. Returns the bytes a shadow needs at most; with a shadow, fills out[i].p (the rest of out[i] is pl[i]'s).
-long long blur_shadow(const PlaneArg* pl, const long long* rows, const long long* rowbytes, int np, void* shadow,
-                      PlaneArg* out) {
+long long blur_shadow(const PlaneArg* pl, const PlaneSizes& z, void* shadow, PlaneArg* out) {
   long long at = 0;
-  for (int i = 0; i < np; ++i) {
+  for (int i = 0; i < z.np; ++i) {
     if (shadow) {
       uint8_t* q = static_cast<uint8_t*>(shadow) + at;
       q += (reinterpret_cast<uintptr_t>(pl[i].p) - reinterpret_cast<uintptr_t>(q)) & 3;
       out[i] = pl[i], out[i].p = q;
     }
-    at += (rows[i] - 1) * pl[i].pitch + rowbytes[i] + 4;
+    at += (z.rows[i] - 1) * pl[i].pitch + z.rowbytes[i] + 4;
   }
   return at;
 }
@@ -669,15 +689,10 @@ constexpr int BLUR_BAND_LDS = 48 << 10;
 int blur_band(int radius, int pb) { return blur_lds(BTILE, radius, radius, pb) <= BLUR_BAND_LDS ? BTILE : BTILE / 2; }
 
 // What both blur entries check and fill of k (mask and band are filled by the entry).
-int blur_args(BlurArgs& k, int h, int w, const int* count, const float* scores, const int* labels, const float* boxes,
-              const int* track_id, const int* track_hits, int N, const void* select, int L, int min_hits, int radius,
-              const void* taps, const void* shadow) {
+int blur_args(BlurArgs& k, int h, int w, const Lists& l, int radius, const void* taps, const void* shadow) {
   if (radius < 1 || radius > BLUR_MAX_RADIUS) return fail("blur: a radius of 1..32 pixels");
-  if (const int rc = list_args("blur", h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits))
-    return rc;
+  if (const int rc = select_args("blur", k.m, h, w, l)) return rc;
   if (!taps || !shadow) return fail("blur: null operand");
-  k.m = MosaicArgs{count, scores, labels, boxes, track_id, track_hits, static_cast<const uint8_t*>(select), N, L, min_hits,
-                   h, w, 0, 255};
   k.taps = static_cast<const int16_t*>(taps), k.radius = radius, k.band = blur_band(radius, 2);
   return 0;
 }
@@ -694,18 +709,14 @@ int blur_launch(const BlurArgs& k, const Dst& dst, const Dst& shadow, int pb, vo
 }
 
 // What both chips entries check of the lists, the sizes and the outputs, and fill of k.
-int chips_args(ChipArgs& k, int h, int w, const int* count, const float* scores, const int* labels, const float* boxes,
-               const int* track_id, const int* track_hits, int N, const void* select, int L, int min_hits, int margin,
-               int capacity, int sh, int sw, void* chips, int* rows, int* rects, int* chip_count) {
-  if (const int rc = list_args("chips", h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits))
-    return rc;
+int chips_args(ChipArgs& k, int h, int w, const Lists& l, int margin, int capacity, int sh, int sw, void* chips,
+               int* rows, int* rects, int* chip_count) {
+  if (const int rc = select_args("chips", k.m, h, w, l)) return rc;
   if (!chips || !rows || !rects || !chip_count) return fail("chips: null operand");
   if (sh < 1 || sh > CHIP_MAX_SIDE || sw < 1 || sw > CHIP_MAX_SIDE) return fail("chips: chip sides of 1..256 pixels");
   if (capacity < 1 || capacity > CHIP_MAX_CAPACITY) return fail("chips: a capacity of 1..256 chips");
   if (margin < 0 || margin > CHIP_MAX_MARGIN) return fail("chips: a margin of 0..64 pixels");
   if ((long long)h * w > CHIP_MAX_AREA) return fail("chips: a frame of at most 2^24 pixels (the sums are 32 bits)");
-  k.m = MosaicArgs{count, scores, labels, boxes, track_id, track_hits, static_cast<const uint8_t*>(select), N, L, min_hits,
-                   h, w, 0, 255};
   k.chips = static_cast<uint8_t*>(chips), k.rows = rows, k.rects = rects, k.chip_count = chip_count;
   k.capacity = capacity, k.sh = sh, k.sw = sw, k.margin = margin;
   k.band = std::max(1, std::min(sh, CHIP_NACC * CT / 3 / sw));
@@ -769,6 +780,12 @@ int rescale_launch(ScaleArgs& k, int np, void* stream, const char* what) {
   hipLaunchKernelGGL(wide ? rescale_k<true> : rescale_k<false>, dim3(grid), dim3(SCALE_T), 0,
                      reinterpret_cast<hipStream_t>(stream), k);
   return check(what);
+}
+
+// The sides both rescale entries take, of the source and of the target.
+int rescale_sides(int h, int w, int H, int W) {
+  const bool ok = h >= 1 && w >= 1 && H >= 1 && W >= 1 && std::max(std::max(h, w), std::max(H, W)) <= SCALE_MAX_SIDE;
+  return ok ? 0 : fail("rescale: sides of 1..8192 pixels");
 }
 
 bool ranges_meet(const PlaneArg& a, const PlaneArg& b) { return a.lo < b.hi && b.lo < a.hi; }
@@ -1073,9 +1090,8 @@ int nos_overlay_packed(void* img, const void* lo, const void* hi, long long pitc
                        int K, const int* font, int thickness, int scale, int min_hits, void* stream) {
   if (!img || !order) return fail("overlay: null operand");
   OverlayArgs k{};
-  if (const int rc = overlay_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, modes, L, codes, K,
-                                  font, thickness, scale, min_hits))
-    return rc;
+  const Lists l{count, scores, labels, boxes, track_id, track_hits, modes, N, L, min_hits};
+  if (const int rc = overlay_args(k, h, w, l, codes, K, font, thickness, scale)) return rc;
   PackedDst dst{};
   if (const int rc = packed_dst("overlay_packed", dst, img, lo, hi, pitch, order, h, w)) return rc;
   return overlay_launch(k, dst, stream, "overlay_packed");
@@ -1088,12 +1104,10 @@ int nos_overlay_packed(void* img, const void* lo, const void* hi, long long pitc
 int nos_overlay_yuv(const NosYuvSrc* dst, int h, int w, const int* count, const float* scores, const int* labels,
                     const float* boxes, const int* track_id, const int* track_hits, int N, const void* modes, int L,
                     const int* codes, int K, const int* font, int thickness, int scale, int min_hits, void* stream) {
-  if (!dst) return fail("overlay: null operand");
-  if (dst->size != int(sizeof(NosYuvSrc))) return fail("overlay_yuv: descriptor size mismatch (NosYuvSrc of another build)");
+  if (const int rc = yuv_open("overlay", "overlay_yuv", dst)) return rc;
   OverlayArgs k{};
-  if (const int rc = overlay_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, modes, L, codes, K,
-                                  font, thickness, scale, min_hits))
-    return rc;
+  const Lists l{count, scores, labels, boxes, track_id, track_hits, modes, N, L, min_hits};
+  if (const int rc = overlay_args(k, h, w, l, codes, K, font, thickness, scale)) return rc;
   YuvDst d{};
   if (const int rc = yuv_dst("overlay_yuv", d, *dst, h, w)) return rc;
   return overlay_launch(k, d, stream, "overlay_yuv");
@@ -1113,8 +1127,8 @@ int nos_mosaic_packed(void* img, const void* lo, const void* hi, long long pitch
                       int cell, void* stream) {
   if (!img || !order) return fail("mosaic: null operand");
   MosaicArgs k{};
-  if (const int rc = mosaic_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits, cell))
-    return rc;
+  const Lists l{count, scores, labels, boxes, track_id, track_hits, select, N, L, min_hits};
+  if (const int rc = mosaic_args(k, h, w, l, cell)) return rc;
   PackedDst dst{};
   if (const int rc = packed_dst("mosaic_packed", dst, img, lo, hi, pitch, order, h, w)) return rc;
   return mosaic_launch(k, dst, stream, "mosaic_packed");
@@ -1126,11 +1140,10 @@ int nos_mosaic_packed(void* img, const void* lo, const void* hi, long long pitch
 int nos_mosaic_yuv(const NosYuvSrc* dst, int h, int w, const int* count, const float* scores, const int* labels,
                    const float* boxes, const int* track_id, const int* track_hits, int N, const void* select, int L,
                    int min_hits, int cell, void* stream) {
-  if (!dst) return fail("mosaic: null operand");
-  if (dst->size != int(sizeof(NosYuvSrc))) return fail("mosaic_yuv: descriptor size mismatch (NosYuvSrc of another build)");
+  if (const int rc = yuv_open("mosaic", "mosaic_yuv", dst)) return rc;
   MosaicArgs k{};
-  if (const int rc = mosaic_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits, cell))
-    return rc;
+  const Lists l{count, scores, labels, boxes, track_id, track_hits, select, N, L, min_hits};
+  if (const int rc = mosaic_args(k, h, w, l, cell)) return rc;
   YuvDst d{};
   if (const int rc = yuv_dst("mosaic_yuv", d, *dst, h, w)) return rc;
   k.mask = (1 << dst->depth) - 1;
@@ -1146,8 +1159,7 @@ long long nos_blur_shadow_packed(long long pitch, const char* order, int h, int 
   const int C = order ? packed_order(order, o) : 0;
   if (!C || h <= 0 || w <= 0 || pitch < (long long)w * C) return fail("blur_packed: the shadow of an unknown image");
   const PlaneArg pl = plane_arg(nullptr, nullptr, nullptr, pitch, 0);
-  const long long rows = h, rowbytes = (long long)w * C;
-  return blur_shadow(&pl, &rows, &rowbytes, 1, nullptr, nullptr);
+  return blur_shadow(&pl, PlaneSizes{1, {h}, {(long long)w * C}}, nullptr, nullptr);
 }
 
 // The same for the surface nos_blur_yuv takes.
@@ -1155,9 +1167,7 @@ long long nos_blur_shadow_yuv(const NosYuvSrc* dst, int h, int w) {
   if (!dst || dst->size != int(sizeof(NosYuvSrc))) return fail("blur_yuv: descriptor size mismatch (NosYuvSrc of another build)");
   YuvDst d{};
   if (const int rc = yuv_dst("blur_yuv", d, *dst, h, w)) return rc;
-  long long rows[3], rowbytes[3];
-  const int np = yuv_plane_sizes(*dst, h, w, rows, rowbytes);
-  return blur_shadow(d.pl, rows, rowbytes, np, nullptr, nullptr);
+  return blur_shadow(d.pl, yuv_sizes(*dst, h, w), nullptr, nullptr);
 }
 
 // The detections of the labels select [L] (uint8, non-zero: blur) marks, blurred in packed pixels img: every pixel of a
@@ -1172,14 +1182,12 @@ int nos_blur_packed(void* img, const void* lo, const void* hi, long long pitch, 
                     void* shadow, long long shadow_bytes, void* stream) {
   if (!img || !order) return fail("blur: null operand");
   BlurArgs k{};
-  if (const int rc = blur_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits,
-                               radius, taps, shadow))
-    return rc;
+  const Lists l{count, scores, labels, boxes, track_id, track_hits, select, N, L, min_hits};
+  if (const int rc = blur_args(k, h, w, l, radius, taps, shadow)) return rc;
   PackedDst dst{};
   if (const int rc = packed_dst("blur_packed", dst, img, lo, hi, pitch, order, h, w)) return rc;
-  const long long rows = h, rowbytes = (long long)w * dst.C;
   PackedDst sh = dst;
-  if (blur_shadow(&dst.s, &rows, &rowbytes, 1, shadow, &sh.s) > shadow_bytes)
+  if (blur_shadow(&dst.s, PlaneSizes{1, {h}, {(long long)w * dst.C}}, shadow, &sh.s) > shadow_bytes)
     return fail("blur_packed: the shadow is smaller than nos_blur_shadow_packed asks");
   return blur_launch(k, dst, sh, 2, stream, "blur_packed");
 }
@@ -1190,18 +1198,14 @@ int nos_blur_packed(void* img, const void* lo, const void* hi, long long pitch, 
 int nos_blur_yuv(const NosYuvSrc* dst, int h, int w, const int* count, const float* scores, const int* labels,
                  const float* boxes, const int* track_id, const int* track_hits, int N, const void* select, int L,
                  int min_hits, int radius, const void* taps, void* shadow, long long shadow_bytes, void* stream) {
-  if (!dst) return fail("blur: null operand");
-  if (dst->size != int(sizeof(NosYuvSrc))) return fail("blur_yuv: descriptor size mismatch (NosYuvSrc of another build)");
+  if (const int rc = yuv_open("blur", "blur_yuv", dst)) return rc;
   BlurArgs k{};
-  if (const int rc = blur_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits,
-                               radius, taps, shadow))
-    return rc;
+  const Lists l{count, scores, labels, boxes, track_id, track_hits, select, N, L, min_hits};
+  if (const int rc = blur_args(k, h, w, l, radius, taps, shadow)) return rc;
   YuvDst d{};
   if (const int rc = yuv_dst("blur_yuv", d, *dst, h, w)) return rc;
-  long long rows[3], rowbytes[3];
-  const int np = yuv_plane_sizes(*dst, h, w, rows, rowbytes);
   YuvDst sh = d;
-  if (blur_shadow(d.pl, rows, rowbytes, np, shadow, sh.pl) > shadow_bytes)
+  if (blur_shadow(d.pl, yuv_sizes(*dst, h, w), shadow, sh.pl) > shadow_bytes)
     return fail("blur_yuv: the shadow is smaller than nos_blur_shadow_yuv asks");
   const int pb = dst->sample_bytes == 2 ? 4 : 2;
   k.m.mask = (1 << dst->depth) - 1, k.band = blur_band(radius, pb);
@@ -1227,9 +1231,8 @@ int nos_chips_packed(const void* img, const void* lo, const void* hi, long long 
                      int sh, int sw, void* chips, int* rows, int* rects, int* chip_count, void* stream) {
   if (!img || !order) return fail("chips: null operand");
   ChipArgs k{};
-  if (const int rc = chips_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits,
-                                margin, capacity, sh, sw, chips, rows, rects, chip_count))
-    return rc;
+  const Lists l{count, scores, labels, boxes, track_id, track_hits, select, N, L, min_hits};
+  if (const int rc = chips_args(k, h, w, l, margin, capacity, sh, sw, chips, rows, rects, chip_count)) return rc;
   PackedDst d{};
   if (const int rc = packed_dst("chips_packed", d, const_cast<void*>(img), lo, hi, pitch, order, h, w)) return rc;
   const PackedArgs n{d.s, d.r, 1, 2 - d.r};
@@ -1244,14 +1247,12 @@ int nos_chips_yuv(const NosYuvSrc* src, const NosYuvHdr* hdr, int h, int w, cons
                   const int* labels, const float* boxes, const int* track_id, const int* track_hits, int N,
                   const void* select, int L, int min_hits, int margin, int capacity, int sh, int sw, void* chips,
                   int* rows, int* rects, int* chip_count, void* stream) {
-  if (!src) return fail("chips: null operand");
-  if (src->size != int(sizeof(NosYuvSrc))) return fail("chips_yuv: descriptor size mismatch (NosYuvSrc of another build)");
+  if (const int rc = yuv_open("chips", "chips_yuv", src)) return rc;
   if (hdr && hdr->size != int(sizeof(NosYuvHdr)))
     return fail("chips_yuv: table descriptor size mismatch (NosYuvHdr of another build)");
   ChipArgs k{};
-  if (const int rc = chips_args(k, h, w, count, scores, labels, boxes, track_id, track_hits, N, select, L, min_hits,
-                                margin, capacity, sh, sw, chips, rows, rects, chip_count))
-    return rc;
+  const Lists l{count, scores, labels, boxes, track_id, track_hits, select, N, L, min_hits};
+  if (const int rc = chips_args(k, h, w, l, margin, capacity, sh, sw, chips, rows, rects, chip_count)) return rc;
   YuvHdrArgs n{};
   if (yuv_source(*src, n, 1, h, w) || (hdr && hdr_args(*src, *hdr, n))) return fail("chips_yuv", ": the source: " + g_err);
   if (hdr) return chips_launch_yuv<YuvHdrArgs>(*src, k, n, stream);
@@ -1272,8 +1273,7 @@ int nos_rescale_packed(const void* src, const void* slo, const void* shi, long l
                        const void* dlo, const void* dhi, long long dpitch, int H, int W, const char* order,
                        void* stream) {
   if (!src || !dst || !order) return fail("rescale: null operand");
-  if (h < 1 || w < 1 || H < 1 || W < 1 || std::max(std::max(h, w), std::max(H, W)) > SCALE_MAX_SIDE)
-    return fail("rescale: sides of 1..8192 pixels");
+  if (const int rc = rescale_sides(h, w, H, W)) return rc;
   PackedDst s{}, d{};
   if (const int rc = packed_dst("rescale_packed", s, const_cast<void*>(src), slo, shi, spitch, order, h, w)) return rc;
   if (const int rc = packed_dst("rescale_packed", d, dst, dlo, dhi, dpitch, order, H, W)) return rc;
@@ -1291,20 +1291,18 @@ int nos_rescale_yuv(const NosYuvSrc* src, int h, int w, const NosYuvSrc* dst, in
   if (!src || !dst) return fail("rescale: null operand");
   if (src->size != int(sizeof(NosYuvSrc)) || dst->size != int(sizeof(NosYuvSrc)))
     return fail("rescale_yuv: descriptor size mismatch (NosYuvSrc of another build)");
-  if (h < 1 || w < 1 || H < 1 || W < 1 || std::max(std::max(h, w), std::max(H, W)) > SCALE_MAX_SIDE)
-    return fail("rescale: sides of 1..8192 pixels");
+  if (const int rc = rescale_sides(h, w, H, W)) return rc;
   YuvDst s{}, d{};
   if (const int rc = yuv_dst("rescale_yuv", s, *src, h, w)) return rc;
   if (const int rc = yuv_dst("rescale_yuv", d, *dst, H, W)) return rc;
   if (s.layout != d.layout || s.hsub != d.hsub || s.vsub != d.vsub || s.sb != d.sb || src->depth != dst->depth ||
       s.shift != d.shift || s.order != d.order)
     return fail("rescale_yuv: the source and the target differ in layout, subsampling, sample format or order");
-  const int np = s.layout == YUV_PACKED ? 1 : s.layout == YUV_SEMI ? 2 : 3;
+  const PlaneSizes zs = yuv_sizes(*src, h, w), zd = yuv_sizes(*dst, H, W);
+  const int np = zs.np, ch = int(zs.ch), cw = int(zs.cw), CH = int(zd.ch), CW = int(zd.cw);
   for (int i = 0; i < np; ++i)
     for (int j = 0; j < np; ++j)
       if (ranges_meet(s.pl[i], d.pl[j])) return fail("rescale_yuv: the source's and the target's storage meet");
-  const int ch = (h + (1 << s.vsub) - 1) >> s.vsub, cw = (w + (1 << s.hsub) - 1) >> s.hsub;
-  const int CH = (H + (1 << s.vsub) - 1) >> s.vsub, CW = (W + (1 << s.hsub) - 1) >> s.hsub;
   ScaleArgs k{};
   k.sb = s.sb, k.shift = s.shift, k.mask = (1 << src->depth) - 1;
   if (s.layout == YUV_PACKED) {

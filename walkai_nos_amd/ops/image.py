@@ -1793,8 +1793,7 @@ def track_update(state: TrackState, count: torch.Tensor, scores: torch.Tensor, l
     if features is not None:
         return _track_update_app(state, lists, match_threshold, max_age, birth_threshold, motion, velocity_gain,
                                  features, feature_rows, appearance_gate, reid_threshold, feature_shift, feature_total)
-    if not _use_hip(scores) or scores.dtype != torch.float32 or boxes.dtype != torch.float32 \
-            or labels.dtype != torch.int32 or count.dtype != torch.int32 or N > MAX_ROWS or T > MAX_TRACKS or N < 1:
+    if not _hip_lists(lists + (None, None)) or T > MAX_TRACKS:      # (the lists of a tracker have no ids yet)
         return track_update_reference(state, *lists, match_threshold, max_age, birth_threshold, motion, velocity_gain)
     scores, labels, boxes = scores.contiguous(), labels.contiguous(), boxes.contiguous()
     track_id = torch.empty(N, dtype=torch.int32, device=scores.device)
@@ -1870,6 +1869,57 @@ def _writable(views, who: str) -> None:
             raise ValueError(f"{who}: the target is an expanded view, not memory a frame can be written into")
 
 
+def _frame_kind(frame, who: str, what: str, one: bool) -> tuple:
+    """What a frame is, told by its fields: ``("packed", data [B, h, w, C], order)`` for a uint8 tensor or a ``Packed``
+    frame, its memory checked (``one``: a batch above one is refused), or ``("yuyv" | "semiplanar" | "planar", None,
+    None)``, whose planes the caller checks; ``ValueError`` for anything else, ``what`` ("target", "frame") it is."""
+    if isinstance(frame, torch.Tensor) or (hasattr(frame, "data") and hasattr(frame, "order")
+                                           and not hasattr(frame, "width")):
+        data, order = (frame, "rgb") if isinstance(frame, torch.Tensor) else (frame.data, frame.order)
+        if order not in PACKED_ORDERS:
+            raise ValueError(f"{who}: channel order {order!r} is none of {sorted(PACKED_ORDERS)}")
+        C = PACKED_ORDERS[order][0]
+        if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() not in (3, 4) \
+                or data.shape[-1] != C or 0 in data.shape:
+            raise ValueError(f"{who}: {order} takes a uint8 [h, w, {C}] tensor")
+        data = data if data.dim() == 4 else data[None]
+        if one and data.shape[0] != 1:
+            raise ValueError(f"{who}: one frame, not a batch of {data.shape[0]}")
+        if not _packed_strides(data):
+            raise ValueError(f"{who}: rows may be pitched, but the bytes of a row are contiguous")
+        return "packed", data, order
+    if hasattr(frame, "data") and hasattr(frame, "width"):
+        return "yuyv", None, None
+    if hasattr(frame, "y") and hasattr(frame, "uv"):
+        return "semiplanar", None, None
+    if hasattr(frame, "y") and hasattr(frame, "u") and hasattr(frame, "v"):
+        return "planar", None, None
+    raise ValueError(f"{who}: the {what} is a uint8 [h, w, 3] tensor or a Packed, Nv12, Yuv420p, YuvPlanar, "
+                     f"YuvSemiPlanar or Yuyv frame, not {type(frame).__name__}")
+
+
+def _plane_codes(view: torch.Tensor, shift: int, depth: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(bits, codes)`` of a sample plane: the view a result is stored through (16-bit words as int16) and what
+    :func:`yuv_codes` reads of it, int32."""
+    if view.dtype == torch.uint8:
+        return view, view.to(torch.int32)
+    bits = view if view.dtype == torch.int16 else view.view(torch.int16)
+    return bits, ((bits.to(torch.int32) & 0xffff) >> shift) & ((1 << depth) - 1)
+
+
+def _plane_store(view: torch.Tensor, codes: torch.Tensor, shift: int, on: Optional[torch.Tensor] = None) -> None:
+    """The counterpart of :func:`_plane_codes`: integer ``codes`` stored through a sample plane's view (or its
+    ``bits``) where ``on`` is set, or everywhere — the byte, or the whole 16-bit word ``code << shift``, whose bits
+    are written as int16."""
+    val = codes << shift
+    if view.dtype == torch.uint8:
+        bits, val = view, val.to(torch.uint8)
+    else:
+        bits = view if view.dtype == torch.int16 else view.view(torch.int16)
+        val = ((val + 32768) % 65536 - 32768).to(torch.int16)
+    bits.copy_(val if on is None else torch.where(on, val, bits))
+
+
 def overlay_surface(target) -> OverlaySurface:
     """A target described, without a copy. ``target``: a uint8 ``[h, w, 3]`` (or ``[1, h, w, 3]``) RGB tensor whose
     rows may be pitched, or a frame of ``models/workload``: ``Packed`` (``data``, ``order``), ``Nv12`` / ``YuvSemiPlanar``
@@ -1880,32 +1930,21 @@ def overlay_surface(target) -> OverlaySurface:
     if getattr(target, "transfer", "sdr") != "sdr":
         raise ValueError(f"{who}: an SDR colour has no code on a {target.transfer!r} surface (no inverse tone map)")
     g = lambda name, default: getattr(target, name, default)    # noqa: E731
-    if isinstance(target, torch.Tensor) or (hasattr(target, "data") and hasattr(target, "order")
-                                            and not hasattr(target, "width")):
-        data, order = (target, "rgb") if isinstance(target, torch.Tensor) else (target.data, target.order)
-        if order not in PACKED_ORDERS:
-            raise ValueError(f"{who}: channel order {order!r} is none of {sorted(PACKED_ORDERS)}")
-        C, (r, _, b) = PACKED_ORDERS[order]
-        if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() not in (3, 4) \
-                or data.shape[-1] != C or 0 in data.shape:
-            raise ValueError(f"{who}: {order} takes a uint8 [h, w, {C}] tensor")
-        data = data if data.dim() == 4 else data[None]
-        if data.shape[0] != 1:
-            raise ValueError(f"{who}: one frame, not a batch of {data.shape[0]}")
-        if not _packed_strides(data):
-            raise ValueError(f"{who}: rows may be pitched, but the bytes of a row are contiguous")
+    kind, data, order = _frame_kind(target, who, "target", True)
+    if kind == "packed":
+        r, _, b = PACKED_ORDERS[order][1]
         _writable((data,), who)
         return OverlaySurface(data.shape[1], data.shape[2], data.device, (data, order), None, None,
                               [(data[0, :, :, c], k, 0, 0) for k, c in enumerate((r, 1, b))])
     matrix, full = g("matrix", "bt601"), bool(g("full_range", False))
-    if hasattr(target, "data") and hasattr(target, "width"):
+    if kind == "yuyv":
         order = g("order", "yuyv")
         yv, uv, vv = yuyv_planes(target.data, target.width, order)
         data = target.data if target.data.dim() == 3 else target.data[None]
         planes, sub, depth, msb = (data,), "422", 8, False
         yuv = (YUV_PACKED, planes, sub, depth, msb, tuple(YUYV_ORDERS).index(order))
         views = (yv, uv, vv)
-    elif hasattr(target, "y") and hasattr(target, "uv"):
+    elif kind == "semiplanar":
         sub, depth, msb = g("subsampling", "420"), g("depth", 8), bool(g("msb", False))
         y, uv = yuv_semiplanar_planes(target.y, target.uv, sub, depth)
         B, ch, cw = uv.shape[:3]
@@ -1913,13 +1952,10 @@ def overlay_surface(target) -> OverlaySurface:
         vu = int(bool(g("vu", False)))
         yuv = (YUV_SEMIPLANAR, (y, pairs), sub, depth, msb, vu)
         views = (y, uv[..., vu], uv[..., 1 - vu])
-    elif hasattr(target, "y") and hasattr(target, "u") and hasattr(target, "v"):
+    else:
         sub, depth, msb = g("subsampling", "420"), g("depth", 8), bool(g("msb", False))
         views = yuv_planes(target.y, target.u, target.v, sub, depth)
         yuv = (YUV_PLANAR, tuple(views), sub, depth, msb, 0)
-    else:
-        raise ValueError(f"{who}: the target is a uint8 [h, w, 3] tensor or a Packed, Nv12, Yuv420p, YuvPlanar, "
-                         f"YuvSemiPlanar or Yuyv frame, not {type(target).__name__}")
     _yuv_check(matrix, yuv[3])
     if views[0].shape[0] != 1:
         raise ValueError(f"{who}: one frame, not a batch of {views[0].shape[0]}")
@@ -1999,28 +2035,106 @@ def _overlay_lists(who: str, count, scores, labels, boxes, track_id, track_hits,
     return count, scores, labels, boxes, track_id, track_hits
 
 
-def _overlay_check(surface: OverlaySurface, count, scores, labels, boxes, track_id, track_hits, thickness, scale, modes,
-                   min_hits, codes) -> tuple:
-    """The arguments of :func:`overlay` checked, ``ValueError`` before any launch; the lists as ``count [1]``,
-    ``scores [N]``, ``labels [N]``, ``boxes [N, 4]``, ids and hits ``[N]`` or None (``[1, N]`` views are flattened)."""
+_LIST_NAMES = ("count", "scores", "labels", "boxes", "track_id", "track_hits")
+
+
+def _lists_on(who: str, device, where: str, lists: tuple, names: tuple, tables: tuple) -> tuple:
+    """:func:`_overlay_lists`' lists and the ``tables`` of those ``names`` held to ``device``, where the ``where``
+    ("target", "frame") lies; the lists as ``count [1]``, ``scores [N]``, ``labels [N]``, ``boxes [N, 4]``, ids and
+    hits ``[N]`` or None."""
+    for name, t in zip(_LIST_NAMES + names, lists + tables):
+        if t is not None and t.device != device:
+            raise ValueError(f"{who}: the {where} is on {device}, {name} on {t.device}")
+    return lists if lists[0].dim() == 1 else (lists[0].reshape(1),) + lists[1:]      # (count holds one element)
+
+
+def _effect_lists(who: str, device, where: str, lists: tuple, min_hits, select, verb: str) -> tuple:
+    """What :func:`mosaic`, :func:`blur` and :func:`chips` check of one frame's lists, of ``min_hits`` and of the
+    ``[L]`` table of the labels that are ``verb`` ("pixelated", ...), ``ValueError`` before any launch; the lists as
+    :func:`_lists_on` returns them (``[1, N]`` views are flattened)."""
+    lists = _overlay_lists(who, *lists, min_hits)
+    if not isinstance(select, torch.Tensor) or select.dtype != torch.uint8 or select.dim() != 1 or select.numel() < 1:
+        raise ValueError(f"{who}: select is a uint8 [L] tensor, non-zero where a label is {verb}")
+    return _lists_on(who, device, where, lists, ("select",), (select,))
+
+
+def _overlay_check(surface: OverlaySurface, lists, thickness, scale, modes, min_hits, codes) -> tuple:
+    """The arguments of :func:`overlay` checked, ``ValueError`` before any launch; the lists as :func:`_lists_on`
+    returns them (``[1, N]`` views are flattened)."""
     who = "overlay"
     if not 1 <= int(thickness) <= OVERLAY_MAX_THICKNESS:
         raise ValueError(f"{who}: thickness {thickness!r} is not in 1..{OVERLAY_MAX_THICKNESS}")
     if not 0 <= int(scale) <= OVERLAY_MAX_SCALE:
         raise ValueError(f"{who}: scale {scale!r} is not in 0..{OVERLAY_MAX_SCALE} (0: no tags)")
-    count, scores, labels, boxes, track_id, track_hits = _overlay_lists(who, count, scores, labels, boxes, track_id,
-                                                                        track_hits, min_hits)
+    lists = _overlay_lists(who, *lists, min_hits)
     if not isinstance(modes, torch.Tensor) or modes.dtype != torch.uint8 or modes.dim() != 1 or modes.numel() < 1:
         raise ValueError(f"{who}: modes is a uint8 [L] tensor of 0 (not drawn), 1 (outline and tag), 2 (redacted)")
     if not isinstance(codes, torch.Tensor) or codes.dtype != torch.int32 or codes.dim() != 2 or codes.shape[1] != 3 \
             or codes.shape[0] < 3 or codes.shape[0] % 2 != 1 or codes.shape[0] > 2 * OVERLAY_MAX_COLOURS + 1 \
             or not codes.is_contiguous():
         raise ValueError(f"{who}: codes is overlay_codes' contiguous int32 [2 K + 1, 3] table")
-    for name, t in (("count", count), ("scores", scores), ("labels", labels), ("boxes", boxes), ("track_id", track_id),
-                    ("track_hits", track_hits), ("modes", modes), ("codes", codes)):
-        if t is not None and t.device != surface.device:
-            raise ValueError(f"{who}: the target is on {surface.device}, {name} on {t.device}")
-    return count.reshape(1), scores, labels, boxes, track_id, track_hits
+    return _lists_on(who, surface.device, "target", lists, ("modes", "codes"), (modes, codes))
+
+
+def _hip_lists(lists: tuple) -> bool:
+    """Whether checked lists take the HIP route: on the GPU with the HIP backend, fp32 scores and boxes, int32 count,
+    labels, ids and hits, ``1..MAX_ROWS`` rows. Anything else is the reference's."""
+    count, scores, labels, boxes, track_id, track_hits = lists
+    i32 = torch.int32
+    return _use_hip(scores) and scores.dtype == torch.float32 and boxes.dtype == torch.float32 and labels.dtype == i32 \
+        and count.dtype == i32 and (track_id is None or (track_id.dtype == i32 and track_hits.dtype == i32)) \
+        and 1 <= scores.shape[0] <= MAX_ROWS
+
+
+def _list_args(lists: tuple, table: torch.Tensor) -> Tuple[tuple, tuple]:
+    """The launch arguments every effect entry takes behind its surface — the pointers of the four lists, of the ids
+    and hits (None without them), ``N``, the ``[L]`` table's pointer and ``L`` — and the contiguous tensors they point
+    into, which the caller holds across the call."""
+    count, scores, labels, boxes, track_id, track_hits = lists
+    scores, labels, boxes, table = scores.contiguous(), labels.contiguous(), boxes.contiguous(), table.contiguous()
+    if track_id is not None:
+        track_id, track_hits = track_id.contiguous(), track_hits.contiguous()
+    return (count.data_ptr(), scores.data_ptr(), labels.data_ptr(), boxes.data_ptr(),
+            None if track_id is None else track_id.data_ptr(), None if track_id is None else track_hits.data_ptr(),
+            scores.shape[0], table.data_ptr(), table.shape[0]), (scores, labels, boxes, table, track_id, track_hits)
+
+
+def _surface_args(packed: Optional[tuple], yuv: Optional[tuple]) -> Tuple[tuple, tuple, tuple]:
+    """``(place, pitch, order)``: what an entry takes of the one-frame surface it reads or writes, each a tuple to be
+    spliced in that order before the surface's size. For ``packed = (data [1, h, w, C], order)`` the first byte and the
+    storage bounds, the row pitch, the order; for ``yuv`` (as :class:`OverlaySurface` holds it) the descriptor by
+    reference and two empty tuples."""
+    if packed is None:
+        # no colour table: ctypes leaves ``tab`` at the zeros the effects' entries never read
+        return (ctypes.byref(yuv_src(*yuv, ())),), (), ()
+    data, order = packed
+    pitch = data.stride(1) if data.shape[1] > 1 else data.shape[2] * data.shape[3]
+    return (data.data_ptr(), *_storage_bounds(data)), (pitch,), (order.encode(),)
+
+
+def _label_values(labels: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """int32 ``[N]``: ``table[label]`` of every row whose label lies in ``0 .. L - 1``, else 0."""
+    L, lb = table.shape[0], labels.to(torch.int64)
+    return torch.where((lb >= 0) & (lb < L), table[lb.clamp(0, L - 1)].to(torch.int32), 0)
+
+
+def _effect_rows(count, scores, boxes, track_id, track_hits, min_hits, chosen: torch.Tensor) -> tuple:
+    """Rules 1 and 2 of :func:`overlay` on the lists' device, without a host sync: ``(ok [N] bool, x0, y0, x1, y1 [N]
+    int32)`` — whether a row is drawn, given the rows ``chosen`` by their label, and its rectangle before clipping,
+    columns ``x0 .. x1 - 1`` and rows ``y0 .. y1 - 1`` (``floor``, ``floor``, ``ceil``, ``ceil`` of the clamped
+    corners; zeros for a row with a coordinate that is not finite)."""
+    N, i32 = scores.shape[0], torch.int32
+    bx = boxes.to(torch.float32)
+    finite = torch.isfinite(bx).all(dim=1)
+    c = torch.where(finite[:, None], bx, 0.0).clamp(-OVERLAY_CLAMP, OVERLAY_CLAMP)
+    x0, y0 = torch.floor(c[:, 0]).to(i32), torch.floor(c[:, 1]).to(i32)
+    x1, y1 = torch.ceil(c[:, 2]).to(i32), torch.ceil(c[:, 3]).to(i32)
+    n = count.reshape(1)[0].clamp(0, N)
+    ok = (torch.arange(N, device=scores.device) < n) & (scores.to(torch.float32) > 0) & chosen & finite \
+        & (x1 > x0) & (y1 > y0)
+    if track_id is not None:
+        ok = ok & (track_id > 0) & (track_hits >= int(min_hits))
+    return ok, x0, y0, x1, y1
 
 
 def overlay_slots(h: int, w: int, count, scores, labels, boxes, track_id, track_hits, thickness: int, scale: int,
@@ -2033,22 +2147,10 @@ def overlay_slots(h: int, w: int, count, scores, labels, boxes, track_id, track_
     Y = torch.arange(h, device=dev, dtype=i32)[:, None]
     X = torch.arange(w, device=dev, dtype=i32)[None, :]
     font, tens = _overlay_font(dev), _overlay_table("tens", (1, 10, 100, 1000, 10000, 100000), dev)
-    L = modes.shape[0]
-    lb = labels.to(torch.int64)
-    inside = (lb >= 0) & (lb < L)
-    mode = torch.where(inside, modes[lb.clamp(0, L - 1)].to(i32), 0)
-    bx = boxes.to(torch.float32)
-    finite = torch.isfinite(bx).all(dim=1)
-    c = torch.where(finite[:, None], bx, 0.0).clamp(-OVERLAY_CLAMP, OVERLAY_CLAMP)
-    x0, y0 = torch.floor(c[:, 0]).to(i32), torch.floor(c[:, 1]).to(i32)
-    x1, y1 = torch.ceil(c[:, 2]).to(i32) - 1, torch.ceil(c[:, 3]).to(i32) - 1
-    n = count.reshape(1)[0].clamp(0, N)
-    ok = (torch.arange(N, device=dev) < n) & (scores.to(torch.float32) > 0) & ((mode == 1) | (mode == 2)) & finite \
-        & (x1 >= x0) & (y1 >= y0)
-    key = lb
-    if track_id is not None:
-        ok = ok & (track_id > 0) & (track_hits >= int(min_hits))
-        key = track_id.to(torch.int64)
+    mode = _label_values(labels, modes)
+    ok, x0, y0, x1, y1 = _effect_rows(count, scores, boxes, track_id, track_hits, min_hits, (mode == 1) | (mode == 2))
+    x1, y1 = x1 - 1, y1 - 1
+    key = (labels if track_id is None else track_id).to(torch.int64)
     key = torch.where(ok, key, 0)          # (a row that is not drawn may hold anything)
     v = (key % 1000000).to(i32)
     nd = 1 + sum((v >= p).to(i32) for p in (10, 100, 1000, 10000, 100000))
@@ -2083,19 +2185,14 @@ def overlay_reference(target, count: torch.Tensor, scores: torch.Tensor, labels:
     ``(cy, cx)`` takes the colour of luma pixel ``(cy << vsub, cx << hsub)`` where that pixel is painted and keeps its
     value elsewhere."""
     surface = overlay_surface(target)
-    lists = _overlay_check(surface, count, scores, labels, boxes, track_id, track_hits, thickness, scale, modes,
+    lists = _overlay_check(surface, (count, scores, labels, boxes, track_id, track_hits), thickness, scale, modes,
                            min_hits, codes)
     if lists[1].shape[0] == 0:
         return target
     slot = overlay_slots(surface.h, surface.w, *lists, thickness, scale, modes, min_hits, (codes.shape[0] - 1) // 2)
     for view, comp, hs, vs in surface.samples:
         sub = slot[::1 << vs, ::1 << hs]
-        val = codes[sub.clamp(min=0).long(), comp] << surface.shift
-        if view.dtype == torch.uint8:
-            view.copy_(torch.where(sub >= 0, val.to(torch.uint8), view))
-        else:       # 16-bit words, written whole: the same bits as int16
-            bits = view if view.dtype == torch.int16 else view.view(torch.int16)
-            bits.copy_(torch.where(sub >= 0, ((val + 32768) % 65536 - 32768).to(torch.int16), bits))
+        _plane_store(view, codes[sub.clamp(min=0).long(), comp], surface.shift, sub >= 0)
     return target
 
 
@@ -2131,31 +2228,17 @@ def overlay(target, count: torch.Tensor, scores: torch.Tensor, labels: torch.Ten
     blending, antialiased lines, class names or any glyph but digits, PQ / HLG surfaces, batches above one and more
     than 1024 rows are not offered."""
     surface = overlay_surface(target)
-    lists = _overlay_check(surface, count, scores, labels, boxes, track_id, track_hits, thickness, scale, modes,
+    lists = _overlay_check(surface, (count, scores, labels, boxes, track_id, track_hits), thickness, scale, modes,
                            min_hits, codes)
-    count, scores, labels, boxes, track_id, track_hits = lists
-    N = scores.shape[0]
-    i32 = torch.int32
-    if not _use_hip(scores) or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or labels.dtype != i32 \
-            or count.dtype != i32 or (track_id is not None and (track_id.dtype != i32 or track_hits.dtype != i32)) \
-            or N > MAX_ROWS or N < 1:
+    if not _hip_lists(lists):
         return overlay_reference(target, *lists, thickness=thickness, scale=scale, modes=modes, min_hits=min_hits,
                                  codes=codes)
-    scores, labels, boxes, modes = scores.contiguous(), labels.contiguous(), boxes.contiguous(), modes.contiguous()
-    ids = (None, None) if track_id is None else (track_id.contiguous(), track_hits.contiguous())
-    tail = (count.data_ptr(), scores.data_ptr(), labels.data_ptr(), boxes.data_ptr(),
-            None if ids[0] is None else ids[0].data_ptr(), None if ids[1] is None else ids[1].data_ptr(), N,
-            modes.data_ptr(), modes.shape[0], codes.data_ptr(), (codes.shape[0] - 1) // 2,
-            _overlay_font(surface.device).data_ptr(), int(thickness), int(scale), int(min_hits),
-            torch.cuda.current_stream().cuda_stream)
-    if surface.packed is not None:
-        data, order = surface.packed
-        lo, hi = _storage_bounds(data)
-        pitch = data.stride(1) if data.shape[1] > 1 else data.shape[2] * data.shape[3]
-        rc = _L().nos_overlay_packed(data.data_ptr(), lo, hi, pitch, order.encode(), surface.h, surface.w, *tail)
-    else:
-        src = yuv_src(*surface.yuv, (0,) * 12)
-        rc = _L().nos_overlay_yuv(ctypes.byref(src), surface.h, surface.w, *tail)
+    args, held = _list_args(lists, modes)
+    entry = _L().nos_overlay_yuv if surface.packed is None else _L().nos_overlay_packed
+    place, pitch, order = _surface_args(surface.packed, surface.yuv)
+    rc = entry(*place, *pitch, *order, surface.h, surface.w, *args, codes.data_ptr(), (codes.shape[0] - 1) // 2,
+               _overlay_font(surface.device).data_ptr(), int(thickness), int(scale), int(min_hits),
+               torch.cuda.current_stream().cuda_stream)
     _check(rc, "overlay")
     return target
 
@@ -2166,20 +2249,12 @@ MOSAIC_CELLS = (4, 8, 16, 32, 64)
 MOSAIC_TILE = (64, 64)
 
 
-def _mosaic_check(surface: OverlaySurface, count, scores, labels, boxes, track_id, track_hits, min_hits, select,
-                  cell) -> tuple:
-    """The arguments of :func:`mosaic` checked, ``ValueError`` before any launch; the lists as :func:`_overlay_check`
+def _mosaic_check(surface: OverlaySurface, lists, min_hits, select, cell) -> tuple:
+    """The arguments of :func:`mosaic` checked, ``ValueError`` before any launch; the lists as :func:`_effect_lists`
     returns them."""
-    who = "mosaic"
     if cell not in MOSAIC_CELLS:
-        raise ValueError(f"{who}: cell {cell!r} is none of {MOSAIC_CELLS}")
-    lists = _overlay_lists(who, count, scores, labels, boxes, track_id, track_hits, min_hits)
-    if not isinstance(select, torch.Tensor) or select.dtype != torch.uint8 or select.dim() != 1 or select.numel() < 1:
-        raise ValueError(f"{who}: select is a uint8 [L] tensor, non-zero where a label is pixelated")
-    for name, t in zip(("count", "scores", "labels", "boxes", "track_id", "track_hits", "select"), lists + (select,)):
-        if t is not None and t.device != surface.device:
-            raise ValueError(f"{who}: the target is on {surface.device}, {name} on {t.device}")
-    return (lists[0].reshape(1),) + lists[1:]
+        raise ValueError(f"mosaic: cell {cell!r} is none of {MOSAIC_CELLS}")
+    return _effect_lists("mosaic", surface.device, "target", lists, min_hits, select, "pixelated")
 
 
 def mosaic_cells(h: int, w: int, count, scores, labels, boxes, track_id, track_hits, min_hits: int,
@@ -2187,20 +2262,10 @@ def mosaic_cells(h: int, w: int, count, scores, labels, boxes, track_id, track_h
     """Rules 1 and 2 of :func:`mosaic` on the lists' device, without a host sync and without a loop over the rows: bool
     ``[ceil(h / cell), ceil(w / cell)]``, the marked cells. A selected row's rectangle, clipped to the frame, spans a
     range of cell rows and one of cell columns; the mask is where the sum over rows of their outer product is not 0."""
-    dev, N, cell = scores.device, scores.shape[0], int(cell)
-    L = select.shape[0]
-    lb = labels.to(torch.int64)
-    chosen = (lb >= 0) & (lb < L) & (select[lb.clamp(0, L - 1)] != 0)
-    bx = boxes.to(torch.float32)
-    finite = torch.isfinite(bx).all(dim=1)
-    c = torch.where(finite[:, None], bx, 0.0).clamp(-OVERLAY_CLAMP, OVERLAY_CLAMP)
-    x0, y0 = torch.floor(c[:, 0]).to(torch.int32), torch.floor(c[:, 1]).to(torch.int32)
-    x1, y1 = torch.ceil(c[:, 2]).to(torch.int32) - 1, torch.ceil(c[:, 3]).to(torch.int32) - 1
-    n = count.reshape(1)[0].clamp(0, N)
-    ok = (torch.arange(N, device=dev) < n) & (scores.to(torch.float32) > 0) & chosen & finite & (x1 >= x0) & (y1 >= y0)
-    if track_id is not None:
-        ok = ok & (track_id > 0) & (track_hits >= int(min_hits))
-    x0, y0, x1, y1 = x0.clamp(min=0), y0.clamp(min=0), x1.clamp(max=w - 1), y1.clamp(max=h - 1)
+    dev, cell = scores.device, int(cell)
+    ok, x0, y0, x1, y1 = _effect_rows(count, scores, boxes, track_id, track_hits, min_hits,
+                                      _label_values(labels, select) != 0)
+    x0, y0, x1, y1 = x0.clamp(min=0), y0.clamp(min=0), (x1 - 1).clamp(max=w - 1), (y1 - 1).clamp(max=h - 1)
     ok = ok & (x1 >= x0) & (y1 >= y0)
     ci = torch.arange(-(-h // cell), device=dev, dtype=torch.int32)[None, :]
     cj = torch.arange(-(-w // cell), device=dev, dtype=torch.int32)[None, :]
@@ -2219,31 +2284,23 @@ def mosaic_reference(target, count: torch.Tensor, scores: torch.Tensor, labels: 
     reshape, ``m = (sum + n // 2) // n`` spread back over the cell and stored through the plane's strided view where the
     cell is marked."""
     surface = overlay_surface(target)
-    lists = _mosaic_check(surface, count, scores, labels, boxes, track_id, track_hits, min_hits, select, cell)
+    lists = _mosaic_check(surface, (count, scores, labels, boxes, track_id, track_hits), min_hits, select, cell)
     if lists[1].shape[0] == 0:
         return target
     cell = int(cell)
     marked = mosaic_cells(surface.h, surface.w, *lists, min_hits, select, cell)
     depth = 8 if surface.yuv is None else surface.yuv[3]
     for view, _, hs, vs in surface.samples:
-        if view.dtype == torch.uint8:
-            bits, codes = view, view.to(torch.int32)
-        else:       # 16-bit words: the same bits as int16, read as yuv_codes does
-            bits = view if view.dtype == torch.int16 else view.view(torch.int16)
-            codes = ((bits.to(torch.int32) & 0xffff) >> surface.shift) & ((1 << depth) - 1)
+        bits, codes = _plane_codes(view, surface.shift, depth)
         ph, pw = codes.shape
         cv, cw = cell >> vs, cell >> hs
         gi, gj = marked.shape
         pad = (0, gj * cw - pw, 0, gi * cv - ph)
         total = F.pad(codes, pad).reshape(gi, cv, gj, cw).sum(dim=(1, 3))
         n = F.pad(torch.ones_like(codes), pad).reshape(gi, cv, gj, cw).sum(dim=(1, 3))
-        m = torch.div(total + torch.div(n, 2, rounding_mode="floor"), n, rounding_mode="floor") << surface.shift
+        m = torch.div(total + torch.div(n, 2, rounding_mode="floor"), n, rounding_mode="floor")
         spread = lambda t: t.repeat_interleave(cv, dim=0).repeat_interleave(cw, dim=1)[:ph, :pw]     # noqa: E731
-        m, on = spread(m), spread(marked)
-        if view.dtype == torch.uint8:
-            bits.copy_(torch.where(on, m.to(torch.uint8), bits))
-        else:
-            bits.copy_(torch.where(on, ((m + 32768) % 65536 - 32768).to(torch.int16), bits))
+        _plane_store(bits, spread(m), surface.shift, spread(marked))
     return target
 
 
@@ -2281,27 +2338,14 @@ def mosaic(target, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tens
     Cells of other sizes, PQ / HLG surfaces, batches above one and cells anchored to the box instead of the frame are
     not offered; :func:`blur` is the redaction that follows the box."""
     surface = overlay_surface(target)
-    lists = _mosaic_check(surface, count, scores, labels, boxes, track_id, track_hits, min_hits, select, cell)
-    count, scores, labels, boxes, track_id, track_hits = lists
-    N = scores.shape[0]
-    i32 = torch.int32
-    if not _use_hip(scores) or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or labels.dtype != i32 \
-            or count.dtype != i32 or (track_id is not None and (track_id.dtype != i32 or track_hits.dtype != i32)) \
-            or N > MAX_ROWS or N < 1:
+    lists = _mosaic_check(surface, (count, scores, labels, boxes, track_id, track_hits), min_hits, select, cell)
+    if not _hip_lists(lists):
         return mosaic_reference(target, *lists, min_hits=min_hits, select=select, cell=cell)
-    scores, labels, boxes, select = scores.contiguous(), labels.contiguous(), boxes.contiguous(), select.contiguous()
-    ids = (None, None) if track_id is None else (track_id.contiguous(), track_hits.contiguous())
-    tail = (count.data_ptr(), scores.data_ptr(), labels.data_ptr(), boxes.data_ptr(),
-            None if ids[0] is None else ids[0].data_ptr(), None if ids[1] is None else ids[1].data_ptr(), N,
-            select.data_ptr(), select.shape[0], int(min_hits), int(cell), torch.cuda.current_stream().cuda_stream)
-    if surface.packed is not None:
-        data, order = surface.packed
-        lo, hi = _storage_bounds(data)
-        pitch = data.stride(1) if data.shape[1] > 1 else data.shape[2] * data.shape[3]
-        rc = _L().nos_mosaic_packed(data.data_ptr(), lo, hi, pitch, order.encode(), surface.h, surface.w, *tail)
-    else:
-        src = yuv_src(*surface.yuv, (0,) * 12)
-        rc = _L().nos_mosaic_yuv(ctypes.byref(src), surface.h, surface.w, *tail)
+    args, held = _list_args(lists, select)
+    entry = _L().nos_mosaic_yuv if surface.packed is None else _L().nos_mosaic_packed
+    place, pitch, order = _surface_args(surface.packed, surface.yuv)
+    rc = entry(*place, *pitch, *order, surface.h, surface.w, *args, int(min_hits), int(cell),
+               torch.cuda.current_stream().cuda_stream)
     _check(rc, "mosaic")
     return target
 
@@ -2341,20 +2385,12 @@ def _blur_table(radius: int, device: torch.device) -> torch.Tensor:
     return _overlay_tables.get(("blur", int(radius), str(device)), make)
 
 
-def _blur_check(surface: OverlaySurface, count, scores, labels, boxes, track_id, track_hits, min_hits, select,
-                radius) -> tuple:
-    """The arguments of :func:`blur` checked, ``ValueError`` before any launch; the lists as :func:`_mosaic_check`
+def _blur_check(surface: OverlaySurface, lists, min_hits, select, radius) -> tuple:
+    """The arguments of :func:`blur` checked, ``ValueError`` before any launch; the lists as :func:`_effect_lists`
     returns them."""
-    who = "blur"
     if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= BLUR_MAX_RADIUS:
-        raise ValueError(f"{who}: radius {radius!r} is not an integer in 1..{BLUR_MAX_RADIUS}")
-    lists = _overlay_lists(who, count, scores, labels, boxes, track_id, track_hits, min_hits)
-    if not isinstance(select, torch.Tensor) or select.dtype != torch.uint8 or select.dim() != 1 or select.numel() < 1:
-        raise ValueError(f"{who}: select is a uint8 [L] tensor, non-zero where a label is blurred")
-    for name, t in zip(("count", "scores", "labels", "boxes", "track_id", "track_hits", "select"), lists + (select,)):
-        if t is not None and t.device != surface.device:
-            raise ValueError(f"{who}: the target is on {surface.device}, {name} on {t.device}")
-    return (lists[0].reshape(1),) + lists[1:]
+        raise ValueError(f"blur: radius {radius!r} is not an integer in 1..{BLUR_MAX_RADIUS}")
+    return _effect_lists("blur", surface.device, "target", lists, min_hits, select, "blurred")
 
 
 def blur_reference(target, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor,
@@ -2366,30 +2402,22 @@ def blur_reference(target, count: torch.Tensor, scores: torch.Tensor, labels: to
     the axis radii (exact: every partial sum is an integer below 2^28), ``(sum + 2^15) // 2^16`` is stored through the
     plane's strided view where the owner pixel is painted. Every plane is read before it is written."""
     surface = overlay_surface(target)
-    lists = _blur_check(surface, count, scores, labels, boxes, track_id, track_hits, min_hits, select, radius)
+    lists = _blur_check(surface, (count, scores, labels, boxes, track_id, track_hits), min_hits, select, radius)
     if lists[1].shape[0] == 0:
         return target
     painted = mosaic_cells(surface.h, surface.w, *lists, min_hits, select, 1)
     depth = 8 if surface.yuv is None else surface.yuv[3]
     f64 = torch.float64
     for view, _, hs, vs in surface.samples:
-        if view.dtype == torch.uint8:
-            bits, codes = view, view.to(torch.int32)
-        else:       # 16-bit words: the same bits as int16, read as yuv_codes does
-            bits = view if view.dtype == torch.int16 else view.view(torch.int16)
-            codes = ((bits.to(torch.int32) & 0xffff) >> surface.shift) & ((1 << depth) - 1)
+        bits, codes = _plane_codes(view, surface.shift, depth)
         rh, rv = radius >> hs, radius >> vs
         th, tv = (_overlay_tables.get(("blur64", rho, str(view.device)),
                                       lambda: torch.from_numpy(blur_taps(rho)).to(device=view.device, dtype=f64))
                   for rho in (rh, rv))      # cached as the kernel's table is: nothing is copied from the host in a capture
         x = F.pad(codes.to(f64)[None, None], (rh, rh, rv, rv), mode="replicate")
         x = F.conv2d(F.conv2d(x, th.reshape(1, 1, 1, -1)), tv.reshape(1, 1, -1, 1))[0, 0]
-        m = torch.div(x + 32768.0, 65536.0, rounding_mode="floor").to(torch.int32) << surface.shift
-        on = painted[::1 << vs, ::1 << hs]
-        if view.dtype == torch.uint8:
-            bits.copy_(torch.where(on, m.to(torch.uint8), bits))
-        else:
-            bits.copy_(torch.where(on, ((m + 32768) % 65536 - 32768).to(torch.int16), bits))
+        m = torch.div(x + 32768.0, 65536.0, rounding_mode="floor").to(torch.int32)
+        _plane_store(bits, m, surface.shift, painted[::1 << vs, ::1 << hs])
     return target
 
 
@@ -2423,36 +2451,22 @@ def blur(target, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor
     1024 rows on the GPU; past that, for other dtypes, on the CPU and with the ``torch`` backend :func:`blur_reference`.
     Radii above 32, box or other kernels, PQ / HLG surfaces, batches above one and feathered edges are not offered."""
     surface = overlay_surface(target)
-    lists = _blur_check(surface, count, scores, labels, boxes, track_id, track_hits, min_hits, select, radius)
-    count, scores, labels, boxes, track_id, track_hits = lists
-    N = scores.shape[0]
-    i32 = torch.int32
-    if not _use_hip(scores) or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or labels.dtype != i32 \
-            or count.dtype != i32 or (track_id is not None and (track_id.dtype != i32 or track_hits.dtype != i32)) \
-            or N > MAX_ROWS or N < 1:
+    lists = _blur_check(surface, (count, scores, labels, boxes, track_id, track_hits), min_hits, select, radius)
+    if not _hip_lists(lists):
         return blur_reference(target, *lists, min_hits=min_hits, select=select, radius=radius)
-    scores, labels, boxes, select = scores.contiguous(), labels.contiguous(), boxes.contiguous(), select.contiguous()
-    ids = (None, None) if track_id is None else (track_id.contiguous(), track_hits.contiguous())
+    args, held = _list_args(lists, select)
     taps = _blur_table(radius, surface.device)
     L = _L()
-    if surface.packed is not None:
-        data, order = surface.packed
-        pitch = data.stride(1) if data.shape[1] > 1 else data.shape[2] * data.shape[3]
-        need = L.nos_blur_shadow_packed(pitch, order.encode(), surface.h, surface.w)
+    h, w = surface.h, surface.w
+    place, pitch, order = _surface_args(surface.packed, surface.yuv)
+    if surface.packed is not None:      # (the shadow of packed pixels needs no address)
+        need, entry = L.nos_blur_shadow_packed(*pitch, *order, h, w), L.nos_blur_packed
     else:
-        src = yuv_src(*surface.yuv, (0,) * 12)
-        need = L.nos_blur_shadow_yuv(ctypes.byref(src), surface.h, surface.w)
+        need, entry = L.nos_blur_shadow_yuv(*place, h, w), L.nos_blur_yuv
     _check(min(need, 0), "blur")
     shadow = torch.empty(need, dtype=torch.uint8, device=surface.device)
-    tail = (count.data_ptr(), scores.data_ptr(), labels.data_ptr(), boxes.data_ptr(),
-            None if ids[0] is None else ids[0].data_ptr(), None if ids[1] is None else ids[1].data_ptr(), N,
-            select.data_ptr(), select.shape[0], int(min_hits), int(radius), taps.data_ptr(), shadow.data_ptr(), need,
-            torch.cuda.current_stream().cuda_stream)
-    if surface.packed is not None:
-        lo, hi = _storage_bounds(data)
-        rc = L.nos_blur_packed(data.data_ptr(), lo, hi, pitch, order.encode(), surface.h, surface.w, *tail)
-    else:
-        rc = L.nos_blur_yuv(ctypes.byref(src), surface.h, surface.w, *tail)
+    rc = entry(*place, *pitch, *order, h, w, *args, int(min_hits), int(radius), taps.data_ptr(), shadow.data_ptr(), need,
+               torch.cuda.current_stream().cuda_stream)
     _check(rc, "blur")
     return target
 
@@ -2472,36 +2486,22 @@ def _chip_source(frame) -> tuple:
     gives the converted ``[B, h, w, 3]`` frame. ``frame``: a uint8 ``[h, w, 3]`` (or ``[B, h, w, 3]``) RGB tensor or any
     frame of ``models/workload``, told apart by its fields as :func:`overlay_surface` does; every chroma mode and
     transfer is read."""
-    who = "chips"
     g = lambda name, default: getattr(frame, name, default)    # noqa: E731
-    if isinstance(frame, torch.Tensor) or (hasattr(frame, "data") and hasattr(frame, "order")
-                                           and not hasattr(frame, "width")):
-        data, order = (frame, "rgb") if isinstance(frame, torch.Tensor) else (frame.data, frame.order)
-        if order not in PACKED_ORDERS:
-            raise ValueError(f"{who}: channel order {order!r} is none of {sorted(PACKED_ORDERS)}")
-        C = PACKED_ORDERS[order][0]
-        if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() not in (3, 4) \
-                or data.shape[-1] != C or 0 in data.shape:
-            raise ValueError(f"{who}: {order} takes a uint8 [h, w, {C}] tensor")
-        data = data if data.dim() == 4 else data[None]
-        if not _packed_strides(data):
-            raise ValueError(f"{who}: rows may be pitched, but the bytes of a row are contiguous")
+    kind, data, order = _frame_kind(frame, "chips", "frame", False)
+    if kind == "packed":
         return data.shape[0], data.shape[1], data.shape[2], data.device, (data, order), None, \
             lambda: packed_to_rgb(data, order)
     matrix, full = g("matrix", "bt601"), bool(g("full_range", False))
     chroma, siting = g("chroma", "nearest"), g("siting", "left")
     transfer, peak = g("transfer", "sdr"), g("peak_nits", 1000.0)
-    if hasattr(frame, "data") and hasattr(frame, "width"):
+    if kind == "yuyv":
         source = _yuyv_source(frame.data, frame.width, g("order", "yuyv"), matrix, full, chroma, siting)
-    elif hasattr(frame, "y") and hasattr(frame, "uv"):
+    elif kind == "semiplanar":
         source = _semiplanar_source(frame.y, frame.uv, g("subsampling", "420"), g("depth", 8), bool(g("msb", False)),
                                     matrix, full, bool(g("vu", False)), chroma, siting, transfer, peak)
-    elif hasattr(frame, "y") and hasattr(frame, "u") and hasattr(frame, "v"):
+    else:
         source = _planar_source(frame.y, frame.u, frame.v, g("subsampling", "420"), g("depth", 8),
                                 bool(g("msb", False)), matrix, full, chroma, siting, transfer, peak)
-    else:
-        raise ValueError(f"{who}: the frame is a uint8 [h, w, 3] tensor or a Packed, Nv12, Yuv420p, YuvPlanar, "
-                         f"YuvSemiPlanar or Yuyv frame, not {type(frame).__name__}")
     first, (h, w), src, rgb, hdr = source
     return first.shape[0], h, w, first.device, None, (src, hdr), rgb
 
@@ -2522,16 +2522,9 @@ def _chips_params(size, capacity, margin) -> tuple:
     return S_h, S_w, int(capacity), int(margin)
 
 
-def _chips_check(device, count, scores, labels, boxes, track_id, track_hits, min_hits, select) -> tuple:
-    """One frame's lists of :func:`chips` checked, as :func:`_mosaic_check` returns them."""
-    who = "chips"
-    lists = _overlay_lists(who, count, scores, labels, boxes, track_id, track_hits, min_hits)
-    if not isinstance(select, torch.Tensor) or select.dtype != torch.uint8 or select.dim() != 1 or select.numel() < 1:
-        raise ValueError(f"{who}: select is a uint8 [L] tensor, non-zero where a label is cut out")
-    for name, t in zip(("count", "scores", "labels", "boxes", "track_id", "track_hits", "select"), lists + (select,)):
-        if t is not None and t.device != device:
-            raise ValueError(f"{who}: the frame is on {device}, {name} on {t.device}")
-    return (lists[0].reshape(1),) + lists[1:]
+def _chips_check(device, lists, min_hits, select) -> tuple:
+    """One frame's lists of :func:`chips` checked, as :func:`_effect_lists` returns them."""
+    return _effect_lists("chips", device, "frame", lists, min_hits, select, "cut out")
 
 
 def chip_rects(h: int, w: int, count, scores, labels, boxes, track_id, track_hits, min_hits: int, select: torch.Tensor,
@@ -2539,19 +2532,8 @@ def chip_rects(h: int, w: int, count, scores, labels, boxes, track_id, track_hit
     """The selection of :func:`chips` on the lists' device, without a host sync: ``(selected [N] bool, rects [N, 4]
     int32)`` — :func:`mosaic`'s rule 1, then the rectangle as ``(X0, Y0, X1, Y1)``, exclusive, grown by ``margin`` and
     clipped to the frame; a row of which nothing is left is not selected."""
-    N, L = scores.shape[0], select.shape[0]
-    lb = labels.to(torch.int64)
-    chosen = (lb >= 0) & (lb < L) & (select[lb.clamp(0, L - 1)] != 0)
-    bx = boxes.to(torch.float32)
-    finite = torch.isfinite(bx).all(dim=1)
-    c = torch.where(finite[:, None], bx, 0.0).clamp(-OVERLAY_CLAMP, OVERLAY_CLAMP)
-    x0, y0 = torch.floor(c[:, 0]).to(torch.int32), torch.floor(c[:, 1]).to(torch.int32)
-    x1, y1 = torch.ceil(c[:, 2]).to(torch.int32), torch.ceil(c[:, 3]).to(torch.int32)
-    n = count.reshape(1)[0].clamp(0, N)
-    ok = (torch.arange(N, device=scores.device) < n) & (scores.to(torch.float32) > 0) & chosen & finite \
-        & (x1 > x0) & (y1 > y0)
-    if track_id is not None:
-        ok = ok & (track_id > 0) & (track_hits >= int(min_hits))
+    ok, x0, y0, x1, y1 = _effect_rows(count, scores, boxes, track_id, track_hits, min_hits,
+                                      _label_values(labels, select) != 0)
     m = int(margin)
     rect = torch.stack(((x0 - m).clamp(min=0), (y0 - m).clamp(min=0), (x1 + m).clamp(max=w), (y1 + m).clamp(max=h)), 1)
     return ok & (rect[:, 2] > rect[:, 0]) & (rect[:, 3] > rect[:, 1]), rect
@@ -2608,7 +2590,7 @@ def chips_reference(frame, count: torch.Tensor, scores: torch.Tensor, labels: to
                 raise ValueError(f"chips: a batch of {B} frames takes count [{B}] and lists [{B}, N]")
             one = tuple(None if t is None else t.reshape(B, *t.shape[1:])[b] for t in one)
             one = (one[0].reshape(1),) + one[1:]
-        lists = _chips_check(device, *one, min_hits, select)
+        lists = _chips_check(device, one, min_hits, select)
         out.append(_chips_one(img[b], lists, S_h, S_w, select, capacity, margin, min_hits))
     return out[0] if B == 1 else tuple(torch.stack(t) for t in zip(*out))
 
@@ -2648,30 +2630,20 @@ def chips(frame, count: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor
     kw = dict(size=(S_h, S_w), select=select, capacity=capacity, margin=margin, min_hits=min_hits)
     if B != 1:
         return chips_reference(frame, count, scores, labels, boxes, track_id, track_hits, **kw)
-    lists = _chips_check(device, count, scores, labels, boxes, track_id, track_hits, min_hits, select)
-    count, scores, labels, boxes, track_id, track_hits = lists
-    N = scores.shape[0]
-    i32 = torch.int32
-    if not _use_hip(scores) or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or labels.dtype != i32 \
-            or count.dtype != i32 or (track_id is not None and (track_id.dtype != i32 or track_hits.dtype != i32)) \
-            or N > MAX_ROWS or N < 1 or max(S_h, S_w) > CHIP_MAX_SIDE or capacity > CHIP_MAX_CAPACITY \
-            or h * w > CHIP_MAX_AREA:
+    lists = _chips_check(device, (count, scores, labels, boxes, track_id, track_hits), min_hits, select)
+    if not _hip_lists(lists) or max(S_h, S_w) > CHIP_MAX_SIDE or capacity > CHIP_MAX_CAPACITY or h * w > CHIP_MAX_AREA:
         return chips_reference(frame, *lists, **kw)
+    i32 = torch.int32
     out = _chip_buffers.get((str(device), capacity, S_h, S_w), lambda: (
         torch.empty((capacity, S_h, S_w, 3), dtype=torch.uint8, device=device),
         torch.empty((capacity,), dtype=i32, device=device), torch.empty((capacity, 4), dtype=i32, device=device),
         torch.empty((1,), dtype=i32, device=device)))
-    scores, labels, boxes, select = scores.contiguous(), labels.contiguous(), boxes.contiguous(), select.contiguous()
-    ids = (None, None) if track_id is None else (track_id.contiguous(), track_hits.contiguous())
-    tail = (count.data_ptr(), scores.data_ptr(), labels.data_ptr(), boxes.data_ptr(),
-            None if ids[0] is None else ids[0].data_ptr(), None if ids[1] is None else ids[1].data_ptr(), N,
-            select.data_ptr(), select.shape[0], int(min_hits), margin, capacity, S_h, S_w,
-            *(t.data_ptr() for t in out), torch.cuda.current_stream().cuda_stream)
+    args, held = _list_args(lists, select)
+    tail = (*args, int(min_hits), margin, capacity, S_h, S_w, *(t.data_ptr() for t in out),
+            torch.cuda.current_stream().cuda_stream)
     if packed is not None:
-        data, order = packed
-        lo, hi = _storage_bounds(data)
-        pitch = data.stride(1) if data.shape[1] > 1 else data.shape[2] * data.shape[3]
-        rc = _L().nos_chips_packed(data.data_ptr(), lo, hi, pitch, order.encode(), h, w, *tail)
+        place, pitch, order = _surface_args(packed, None)
+        rc = _L().nos_chips_packed(*place, *pitch, *order, h, w, *tail)
     else:
         src, hdr = yuv
         tables = None if hdr is None else ctypes.byref(yuv_hdr(*_hdr_device_tables(*hdr, device)))
@@ -2721,15 +2693,6 @@ def _rescale_check(frame, target) -> Tuple[OverlaySurface, OverlaySurface]:
     return s, d
 
 
-def _plane_codes(view: torch.Tensor, shift: int, depth: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """``(bits, codes)`` of a sample plane: the view a result is stored through (16-bit words as int16) and what
-    :func:`yuv_codes` reads of it, int32."""
-    if view.dtype == torch.uint8:
-        return view, view.to(torch.int32)
-    bits = view if view.dtype == torch.int16 else view.view(torch.int16)
-    return bits, ((bits.to(torch.int32) & 0xffff) >> shift) & ((1 << depth) - 1)
-
-
 def rescale_reference(frame, target):
     """The torch composition of :func:`rescale`, with the same effect on ``target`` on any device and for any size,
     without a host sync: per sample plane ``Wy @ codes @ Wx^T`` in float64 with :func:`chip_weights` — exact, every
@@ -2739,12 +2702,10 @@ def rescale_reference(frame, target):
     depth = 8 if s.yuv is None else s.yuv[3]
     for (sv, _, _, _), (dv, _, _, _) in zip(s.samples, d.samples):
         _, codes = _plane_codes(sv, s.shift, depth)
-        bits, _ = _plane_codes(dv, d.shift, depth)
-        (ph, pw), (PH, PW) = codes.shape, bits.shape
+        (ph, pw), (PH, PW) = codes.shape, dv.shape
         A = ph * pw
         total = chip_weights(ph, PH, s.device) @ codes.to(torch.float64) @ chip_weights(pw, PW, s.device).t()
-        out = torch.div(total.to(torch.int64) + A // 2, A, rounding_mode="floor") << d.shift
-        bits.copy_(out.to(torch.uint8) if bits.dtype == torch.uint8 else ((out + 32768) % 65536 - 32768).to(torch.int16))
+        _plane_store(dv, torch.div(total.to(torch.int64) + A // 2, A, rounding_mode="floor"), d.shift)
     return target
 
 
@@ -2778,16 +2739,10 @@ def rescale(frame, target):
     if not _use_hip(d.samples[0][0]) or max(s.h, s.w, d.h, d.w) > RESCALE_MAX_SIDE:
         return rescale_reference(frame, target)
     stream = torch.cuda.current_stream().cuda_stream
-    if s.packed is not None:
-        ends = []
-        for data, _ in (s.packed, d.packed):
-            lo, hi = _storage_bounds(data)
-            ends.append((data.data_ptr(), lo, hi, data.stride(1) if data.shape[1] > 1 else data.shape[2] * data.shape[3],
-                         data.shape[1], data.shape[2]))
-        rc = _L().nos_rescale_packed(*ends[0], *ends[1], s.packed[1].encode(), stream)
-    else:
-        src, dst = yuv_src(*s.yuv, (0,) * 12), yuv_src(*d.yuv, (0,) * 12)
-        rc = _L().nos_rescale_yuv(ctypes.byref(src), s.h, s.w, ctypes.byref(dst), d.h, d.w, stream)
+    (place, pitch, order), (to_place, to_pitch, _) = _surface_args(s.packed, s.yuv), _surface_args(d.packed, d.yuv)
+    entry = _L().nos_rescale_yuv if s.packed is None else _L().nos_rescale_packed
+    # either end with its size; the order (packed pixels only) once, behind both
+    rc = entry(*place, *pitch, s.h, s.w, *to_place, *to_pitch, d.h, d.w, *order, stream)
     _check(rc, "rescale")
     return target
 
