@@ -25,6 +25,9 @@
 //    resampled to one size as RGB bytes — the one kernel here that reads a surface and writes a new tensor.
 //  * Resizing (image_scale.h): rescale_k, a frame resized into a second surface of the same layout by the chips' exact
 //    area average, plane by plane — the one kernel here that writes a frame it did not read.
+//  * Converting (image_convert.h): convert_k, a frame of any source the chips read written into a second surface of any
+//    SDR layout, depth, subsampling and order at any size — the chips' read side, the forward colour rule, rescale_k's
+//    whole storage units.
 //  * Appearance (image_features.h): chip_features_k, feature_overlap_k and track_features_k — a colour descriptor per
 //    chip, its intersection with every track's, and the descriptor a track keeps — around track_update_app_f32
 //    (image_track.h), the tracker gated and re-identified by them.
@@ -82,6 +85,7 @@ constexpr int NG = RS / 12, GROUP_FMAX_W = NG * 4 - 3;
 }  // namespace
 
 #include "image_chips.h"  // behind the source tags: chips_k is instantiated by them
+#include "image_convert.h"
 #include "image_features.h"
 
 namespace {
@@ -789,6 +793,96 @@ int rescale_sides(int h, int w, int H, int W) {
 }
 
 bool ranges_meet(const PlaneArg& a, const PlaneArg& b) { return a.lo < b.hi && b.lo < a.hi; }
+
+template <class A>
+using ConvKernel = void (*)(ConvArgs, A);
+
+// The target of both convert entries, checked and described: packed pixels (dst, its bounds, pitch and order) or, with
+// dyuv, a YUV surface and the 12 integers of its colour rule. pl: its planes, for the test against the source's.
+int convert_target(ConvArgs& k, PlaneArg* pl, void* dst, const void* dlo, const void* dhi, long long dpitch,
+                   const char* dorder, const NosYuvSrc* dyuv, int H, int W, const int* table) {
+  auto plane = [](const PlaneArg& s, int P, int cs, int vs, int unit, uint32_t slots) {
+    return ConvPlane{const_cast<uint8_t*>(s.p), s.pitch, slots, P, cs, vs, unit};
+  };
+  if ((dst == nullptr) == (dyuv == nullptr)) return fail("convert: a packed target or a YUV target");
+  if (!dyuv) {
+    if (!dorder) return fail("convert: null operand");
+    PackedDst d{};
+    if (const int rc = packed_dst("convert", d, dst, dlo, dhi, dpitch, dorder, H, W)) return rc;
+    const uint32_t slots = uint32_t(CV_BYTE) << (8 * d.r) | uint32_t(CV_BYTE | 1 << 3) << 8 |
+                           uint32_t(CV_BYTE | 2 << 3) << (8 * (2 - d.r));
+    k.pl[0] = plane(d.s, d.C, 0, 0, 1, slots), pl[0] = d.s;
+    k.np = 1, k.sb = 1, k.shift = 0, k.maxcode = 255;
+    return 0;
+  }
+  if (dyuv->size != int(sizeof(NosYuvSrc))) return fail("convert: descriptor size mismatch (NosYuvSrc of another build)");
+  if (!table) return fail("convert: a YUV target takes the 12 integers of its colour rule");
+  YuvDst d{};
+  if (const int rc = yuv_dst("convert", d, *dyuv, H, W)) return rc;
+  // 2^-14 fixed point: coefficients below 2^18 in size and offsets of the depth keep every sum in int32
+  for (int i = 0; i < 12; ++i) {
+    if (i < 9 ? std::abs(table[i]) >= (1 << 18) : (table[i] < 0 || table[i] >= (1 << dyuv->depth)))
+      return fail("convert: colour rule: coefficients below 2^18 in size, offsets below 2^depth");
+    k.tab[i] = table[i];
+  }
+  k.sb = d.sb, k.shift = d.shift, k.maxcode = (1 << dyuv->depth) - 1;
+  const uint32_t y0 = CV_LUMA, y1 = CV_LUMA | 1 << 3, u = CV_U, v = CV_V;
+  if (d.layout == YUV_PACKED) {
+    // a macropixel: Y0 U Y1 V, U Y0 V Y1 or Y0 V Y1 U
+    const uint32_t slots = d.order == 0 ? (y0 | u << 8 | y1 << 16 | v << 24)
+                           : d.order == 1 ? (u | y0 << 8 | v << 16 | y1 << 24) : (y0 | v << 8 | y1 << 16 | u << 24);
+    k.pl[0] = plane(d.pl[0], 4, 1, 0, 4, slots), k.np = 1;
+  } else {
+    const int one = d.sb == 1 ? 4 : 1;  // 8-bit samples of a plane go four to a dword
+    k.pl[0] = plane(d.pl[0], 1, 0, 0, one, y0);
+    if (d.layout == YUV_SEMI) {
+      k.pl[1] = plane(d.pl[1], 2, d.hsub, d.vsub, 2, d.order ? (v | u << 8) : (u | v << 8)), k.np = 2;
+    } else {
+      k.pl[1] = plane(d.pl[1], 1, d.hsub, d.vsub, one, u), k.pl[2] = plane(d.pl[2], 1, d.hsub, d.vsub, one, v), k.np = 3;
+    }
+  }
+  for (int i = 0; i < k.np; ++i) pl[i] = d.pl[i];
+  return 0;
+}
+
+// What both convert entries check behind their source (sp: its ns planes) and their target, then the grid and the
+// launch of the source's two kernels: SAME at equal sizes, else the resampling one on at most 2^24 source pixels.
+template <class A>
+int convert_launch(ConvKernel<A> same, ConvKernel<A> resample, ConvArgs& k, const A& n, const PlaneArg* sp, int ns,
+                   const PlaneArg* dp, int h, int w, int H, int W, void* stream, const char* what) {
+  for (int i = 0; i < ns; ++i)
+    for (int j = 0; j < k.np; ++j)
+      if (ranges_meet(sp[i], dp[j])) return fail(what, ": the source's and the target's storage meet");
+  const bool eq = h == H && w == W;
+  if (!eq && (long long)h * w > CV_MAX_AREA)
+    return fail(what, ": resizing takes a frame of at most 2^24 pixels (the sums are 32 bits)");
+  k.h = h, k.w = w, k.H = H, k.W = W, k.tiles_x = (W + CV_TW - 1) / CV_TW;
+  // a band of 8 rows, halved while the grid would hold fewer than 1024 workgroups; origins stay even
+  int grid = 0;
+  for (k.band = CV_BAND;; k.band /= 2) {
+    grid = k.tiles_x * ((H + k.band - 1) / k.band);
+    if (grid >= 1024 || k.band == 2) break;
+  }
+  hipLaunchKernelGGL(eq ? same : resample, dim3(grid), dim3(CV_T), 0, reinterpret_cast<hipStream_t>(stream), k, n);
+  return check(what);
+}
+
+// The two kernels of a checked YUV source, from the table the patch kernel and the chips are taken from.
+template <class A>
+int convert_launch_yuv(const NosYuvSrc& s, ConvArgs& k, const YuvHdrArgs& n, int ns, const PlaneArg* dp, int h, int w,
+                       int H, int W, void* stream) {
+  const ConvKernel<A> same =
+      yuv_dispatch<A>(s, [](auto y) -> ConvKernel<A> { return convert_k<Src::YUV, A, decltype(y), true>; });
+  const ConvKernel<A> resample =
+      yuv_dispatch<A>(s, [](auto y) -> ConvKernel<A> { return convert_k<Src::YUV, A, decltype(y), false>; });
+  return convert_launch<A>(same, resample, k, A(n), n.pl, ns, dp, h, w, H, W, stream, "convert_yuv");
+}
+
+// The sides both convert entries take.
+int convert_sides(int h, int w, int H, int W) {
+  const bool ok = h >= 1 && w >= 1 && H >= 1 && W >= 1 && std::max(std::max(h, w), std::max(H, W)) <= CV_MAX_SIDE;
+  return ok ? 0 : fail("convert: sides of 1..8192 pixels");
+}
 }  // namespace
 
 extern "C" {
@@ -1324,6 +1418,59 @@ int nos_rescale_yuv(const NosYuvSrc* src, int h, int w, const NosYuvSrc* dst, in
     }
   }
   return rescale_launch(k, np, stream, "rescale_yuv");
+}
+
+int nos_convert_max_side() { return CV_MAX_SIDE; }
+int nos_convert_tile() { return CV_TW; }
+int nos_convert_row_chunk() { return CV_ROWS; }
+int nos_convert_column_chunk() { return 4 * CV_GROUPS; }
+
+// The packed pixels img [h][w][C] (as nos_chips_packed takes them) converted into a second surface of any SDR layout
+// at H x W (convert_k, image_convert.h): R, the exact area average of the frame stretched to H x W (the frame itself at
+// equal sizes), stored as packed pixels dst [H][W][C'] in dorder (as nos_rescale_packed takes its target; the fourth
+// byte is not written) or, with dyuv, as the YUV surface it describes (as nos_rescale_yuv takes its target) by the 12
+// integers of table (ops/image.py's convert_table: luma per pixel, chroma from the mean of its block). Exactly one of
+// dst and dyuv is given. Sides of 1..8192, a source of at most 2^24 pixels unless the sizes are equal; the two storage
+// ranges must not meet. Every sample of the target is written, nothing else. Nothing is launched unless every check
+// passes.
+int nos_convert_packed(const void* img, const void* lo, const void* hi, long long pitch, const char* order, int h, int w,
+                       void* dst, const void* dlo, const void* dhi, long long dpitch, const char* dorder,
+                       const NosYuvSrc* dyuv, int H, int W, const int* table, void* stream) {
+  if (!img || !order) return fail("convert: null operand");
+  if (const int rc = convert_sides(h, w, H, W)) return rc;
+  PackedDst s{};
+  if (const int rc = packed_dst("convert_packed", s, const_cast<void*>(img), lo, hi, pitch, order, h, w)) return rc;
+  ConvArgs k{};
+  PlaneArg dp[3];
+  if (const int rc = convert_target(k, dp, dst, dlo, dhi, dpitch, dorder, dyuv, H, W, table)) return rc;
+  const PackedArgs n{s.s, s.r, 1, 2 - s.r};
+  if (s.C == 4)
+    return convert_launch<PackedArgs>(convert_k<Src::PACKED4, PackedArgs, NoYuv, true>,
+                                      convert_k<Src::PACKED4, PackedArgs, NoYuv, false>, k, n, &s.s, 1, dp, h, w, H, W,
+                                      stream, "convert_packed");
+  return convert_launch<PackedArgs>(convert_k<Src::PACKED3, PackedArgs, NoYuv, true>,
+                                    convert_k<Src::PACKED3, PackedArgs, NoYuv, false>, k, n, &s.s, 1, dp, h, w, H, W,
+                                    stream, "convert_packed");
+}
+
+// The same from the one h x w frame of any YUV source NosYuvSrc describes, read as nos_chips_yuv reads it (nearest or
+// bilinear chroma at its siting; with hdr not null, PQ / HLG through the tables).
+int nos_convert_yuv(const NosYuvSrc* src, const NosYuvHdr* hdr, int h, int w, void* dst, const void* dlo, const void* dhi,
+                    long long dpitch, const char* dorder, const NosYuvSrc* dyuv, int H, int W, const int* table,
+                    void* stream) {
+  if (const int rc = yuv_open("convert", "convert_yuv", src)) return rc;
+  if (hdr && hdr->size != int(sizeof(NosYuvHdr)))
+    return fail("convert_yuv: table descriptor size mismatch (NosYuvHdr of another build)");
+  if (const int rc = convert_sides(h, w, H, W)) return rc;
+  YuvHdrArgs n{};
+  if (yuv_source(*src, n, 1, h, w) || (hdr && hdr_args(*src, *hdr, n))) return fail("convert_yuv", ": the source: " + g_err);
+  ConvArgs k{};
+  PlaneArg dp[3];
+  if (const int rc = convert_target(k, dp, dst, dlo, dhi, dpitch, dorder, dyuv, H, W, table)) return rc;
+  const int ns = yuv_sizes(*src, h, w).np;
+  if (hdr) return convert_launch_yuv<YuvHdrArgs>(*src, k, n, ns, dp, h, w, H, W, stream);
+  if (src->chroma == 1) return convert_launch_yuv<YuvBilinearArgs>(*src, k, n, ns, dp, h, w, H, W, stream);
+  return convert_launch_yuv<YuvArgs>(*src, k, n, ns, dp, h, w, H, W, stream);
 }
 
 int nos_features_max_stripes() { return FEAT_MAX_STRIPES; }

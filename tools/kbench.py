@@ -77,6 +77,13 @@ same from ``rgb`` and ``p010``, and ``scale_1080p_nv12_to_720p_*``: ``ops.image.
 ``rgb()`` then ``F.interpolate(mode="area")`` (``*_rgb_area_us``: what a pod pays today, with no conversion back — not
 the same output, a cost comparison only), all by graph replays, medians of three alternating rounds.
 
+Five rows time the converter (``--rows convert`` runs them alone) on a 2160x3840 source: ``convert_bgra_to_nv12_*``,
+``convert_nv12_to_bgra_*`` and ``convert_yuy2_to_nv12_*`` at the same size, ``convert_p010pq_to_nv12_1080p_*`` and
+``convert_nv12_to_nv12_1080p_*``: ``ops.image.convert`` (``*_hip_us``) against ``convert_reference`` (``*_torch_us``), the
+source's ``rgb()`` alone (``*_rgb_us``: the first step of what a pod does today), a device copy of the source's bytes
+(``*_copy_us``, the floor) and, for the last, ``ops.image.rescale`` of the same pair (``*_rescale_us``).
+``profiles/image_convert_kbench.json``.
+
 The appearance rows (``--rows appearance`` runs them alone) time the launches behind ``track_update(...,
 features=...)`` against their torch references, all by graph replays: ``appearance_<scene>_features_*``
 (``chip_features``), ``_overlap_*`` (``feature_overlap``), ``_track_*`` (the three launches of ``track_update`` with
@@ -132,10 +139,11 @@ def main() -> int:
     ap.add_argument("--out", default="gpurun_out/kbench.json")
     ap.add_argument("--only", choices=("all", "attn", "gemm", "model", "modes", "image"), default="all")
     ap.add_argument("--slices", default="spx,dpx,qpx,cpx")
-    ap.add_argument("--rows", choices=("all", "tiles", "track", "overlay", "mosaic", "blur", "chips", "appearance", "scale"),
+    ap.add_argument("--rows", choices=("all", "tiles", "track", "overlay", "mosaic", "blur", "chips", "appearance", "scale",
+                                       "convert"),
                     default="all",
                     help="image: every row, or the tiled-detection rows alone, or the tracker's, the overlay's, the "
-                         "mosaic's, the blur's, the chips', the appearance or the scaler's rows")
+                         "mosaic's, the blur's, the chips', the appearance, the scaler's or the converter's rows")
     ap.add_argument("--partitions", type=int, default=0, help="modes: run only this many partitions of each mode")
     ap.add_argument("--free-s", type=float, default=0.0,
                     help="modes: serve free-running (one thread per pod, as the bench) for this many seconds "
@@ -422,6 +430,8 @@ def image_bench(a) -> int:
                 appearance_rows(r, s, a.iters, rounds)
             if a.rows in ("all", "scale"):
                 scale_rows(r, s, a.iters, rounds)
+            if a.rows in ("all", "convert"):
+                convert_rows(r, s, a.iters, rounds)
             if not full:
                 print(json.dumps(r), flush=True)
                 results.append(r)
@@ -972,6 +982,59 @@ def scale_rows(r, s, iters, rounds):
         r[f"scale_{name}_scene"] = {"frame": [h, w], "size": [H, W], "source_bytes": buf.numel(),
                                     "target_bytes": sum(t.numel() * t.element_size() for t in planes),
                                     "hip_equals_torch": bool(same)}
+
+
+def convert_rows(r, s, iters, rounds):
+    """The converter (see the module docstring): ``convert_*_hip_us`` against ``*_torch_us`` (``convert_reference``),
+    ``*_rgb_us`` (the source's ``rgb()`` alone), ``*_copy_us`` (a device copy of the source's bytes: the floor) and, for
+    NV12 to NV12, ``*_rescale_us``, all by graph replays; ``*_scene`` says whether the kernel's target equalled the
+    reference's."""
+    import statistics
+
+    from walkai_nos_amd.models.workload import surfaces
+    from walkai_nos_amd.models.workload.processor import Nv12, Packed
+    from walkai_nos_amd.models.workload.scaler import Scaler
+    from walkai_nos_amd.ops import image as I
+    g = torch.Generator().manual_seed(12)
+    h, w = 2160, 3840
+    cases = (("bgra", "nv12", (h, w), {}), ("nv12", "bgra", (h, w), {}), ("yuy2", "nv12", (h, w), {}),
+             ("p010", "nv12", (1080, 1920), dict(matrix="bt2020", transfer="pq")), ("nv12", "nv12", (1080, 1920), {}))
+    for fmt, out, (H, W), kw in cases:
+        name = f"{fmt}{kw.get('transfer', '')}_to_{out}" + ("" if (H, W) == (h, w) else f"_{H}p")
+        if fmt == "bgra":
+            buf = torch.randint(0, 256, (h, w, 4), generator=g, dtype=torch.uint8).cuda()
+            frame = Packed(buf, fmt)
+        else:
+            pitch = -(-w * (1 if fmt == "nv12" else 2) // 256) * 256
+            buf = torch.randint(0, 256, (pitch * h * (2 if fmt == "yuy2" else 3) // 2,), generator=g, dtype=torch.uint8).cuda()
+            frame = Nv12.from_buffer(buf, h, w, pitch) if fmt == "nv12" else surfaces.from_buffer(fmt, buf, h, w, pitch, **kw)
+        target, spare = Scaler((H, W), format=out).target(frame), torch.empty_like(buf)
+        planes = tuple(getattr(target, k) for k in target.PLANES)
+        samples = [view for view, *_ in I.overlay_surface(target).samples]     # (not the fourth byte of BGRA)
+        with torch.cuda.stream(s):
+            I.convert(frame, target)
+            got = [t.clone() for t in samples]
+            for t in samples:
+                t.zero_()
+            I.convert_reference(frame, target)
+            same = all(torch.equal(a, b) for a, b in zip(got, samples))
+            s.synchronize()
+        fns = {"hip": lambda: I.convert(frame, target), "torch": lambda: I.convert_reference(frame, target),
+               "rgb": lambda: frame.rgb(), "copy": lambda: spare.copy_(buf)}
+        if fmt == out:
+            own = Scaler((H, W)).target(frame)
+            fns["rescale"] = lambda: I.rescale(frame, own)
+        t = {k: [] for k in fns}
+        for _ in range(rounds):
+            for k, fn in fns.items():
+                t[k].append(timeit(fn, s, iters if k != "torch" else max(2, iters // 5)))
+        for k, vs in t.items():
+            r[f"convert_{name}_{k}_us"] = round(statistics.median(vs), 1)
+        r[f"convert_{name}_rounds_us"] = {k: [round(v, 1) for v in vs] for k, vs in t.items()}
+        print(f"[kbench] convert_{name}: {r[f'convert_{name}_rounds_us']}", file=sys.stderr, flush=True)
+        r[f"convert_{name}_scene"] = {"frame": [h, w], "size": [H, W], "source_bytes": buf.numel(),
+                                      "target_bytes": sum(t.numel() * t.element_size() for t in planes),
+                                      "hip_equals_torch": bool(same)}
 
 
 def appearance_rows(r, s, iters, rounds):

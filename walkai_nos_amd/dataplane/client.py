@@ -56,7 +56,10 @@ more launch inside the captured graph) as RGB chips of ``--chip-size H,W`` (defa
 then carries ``"chips": {"count": ..., "nonzero_bytes": ...}`` of the last inference.
 ``--scale-out H,W`` resizes the frame — with ``--annotate`` the painted one — to that size in its own layout
 (``scaler.Scaler``, ``ops.image.rescale``: one more launch inside the captured graph, no RGB frame) on every SDR
-``--pixel-format``; the JSON line then carries ``"scaled": {"hw": [H, W], "nonzero_bytes": ...}``.
+``--pixel-format``; the JSON line then carries ``"scaled": {"hw": [H, W], "format": ..., "nonzero_bytes": ...}``.
+``--scale-out-format NAME`` (any ``--pixel-format`` name) writes the resized frame in that layout instead
+(``ops.image.convert``, still one launch), with ``--scale-out-matrix`` and ``--scale-out-full-range`` for a YUV format;
+with it ``--scale-out`` also goes with ``--transfer pq|hlg``, whose frames are read as the model reads them.
 """
 from __future__ import annotations
 
@@ -174,13 +177,25 @@ def main(argv=None) -> int:
     ap.add_argument("--chip-capacity", type=int, default=None, help="--chips: the chips of one frame, 1..256 (default 64)")
     ap.add_argument("--chip-margin", type=int, default=None, help="--chips: pixels added around a box, 0..64 (default 0)")
     ap.add_argument("--scale-out", default="", help="--end-to-end: H,W: the (annotated) frame resized to that size in its own layout")
+    ap.add_argument("--scale-out-format", choices=("rgb", "bgr", "rgba", "bgra", "nv12", "nv21", "i420", "yv12")
+                    + tuple(SURFACES), default=None,
+                    help="--scale-out: the layout the resized frame is written in (default: the frame's own)")
+    ap.add_argument("--scale-out-matrix", choices=("bt601", "bt709", "bt2020"), default=None,
+                    help="--scale-out-format: a YUV format's colour matrix (default: an SDR YUV frame's own, else bt709)")
+    ap.add_argument("--scale-out-full-range", action="store_true", default=None,
+                    help="--scale-out-format: full-range YUV codes (default: an SDR YUV frame's own, else limited)")
     args = ap.parse_args(argv)
     scale_out = None
+    if not args.scale_out and (args.scale_out_format or args.scale_out_matrix or args.scale_out_full_range):
+        ap.error("--scale-out-format, --scale-out-matrix and --scale-out-full-range take --scale-out")
+    if not args.scale_out_format and (args.scale_out_matrix or args.scale_out_full_range):
+        ap.error("--scale-out-matrix and --scale-out-full-range take --scale-out-format")
     if args.scale_out:
         if not args.end_to_end:
             ap.error("--scale-out takes --end-to-end")
-        if args.transfer != "sdr":
-            ap.error(f"--scale-out resizes SDR surfaces: it is not offered with --transfer {args.transfer}")
+        if args.transfer != "sdr" and not args.scale_out_format:
+            ap.error(f"--scale-out resizes SDR surfaces: it is not offered with --transfer {args.transfer} "
+                     f"(--scale-out-format converts them)")
         try:
             scale_out = tuple(int(v) for v in args.scale_out.split(","))
         except ValueError:
@@ -372,7 +387,7 @@ def main(argv=None) -> int:
         scaler = None
         if scale_out is not None:
             from ..models.workload.scaler import Scaler
-            scaler = Scaler(scale_out)
+            scaler = Scaler(scale_out, args.scale_out_format, args.scale_out_matrix, args.scale_out_full_range)
 
         def infer():
             det = detect()
@@ -495,7 +510,8 @@ def main(argv=None) -> int:
         if scale_out is not None:
             scaled = res["scaled"]
             planes = (scaled,) if isinstance(scaled, torch.Tensor) else tuple(getattr(scaled, k) for k in scaled.PLANES)
-            out["scaled"] = {"hw": list(scale_out), "nonzero_bytes": sum(int((t != 0).sum().item()) for t in planes)}
+            out["scaled"] = {"hw": list(scale_out), "format": args.scale_out_format or args.pixel_format,
+                             "nonzero_bytes": sum(int((t != 0).sum().item()) for t in planes)}
     if census is not None:
         out["census"] = census
     out["hbm"] = _shim()

@@ -1,37 +1,88 @@
-"""A frame at the size its consumer wants, in its own layout: :class:`Scaler` holds the size and the target planes of
-``ops.image.rescale`` (one launch that resizes every sample plane by an exact area average) and returns a frame of the
-same class and parameters — an operator's wall, an encoder's ladder or an event log's thumbnail take it from there,
-with no RGB frame and no colour conversion on the way. Nothing here synchronises with the host, so
-``YolosSmall.annotate_image(..., scaler=...)`` captures as one graph: frame in, annotated frame out at another size.
+"""A frame at the size its consumer wants: :class:`Scaler` holds the size and the target planes and returns a frame at
+that size — an operator's wall, an encoder's ladder or an event log's thumbnail take it from there. Without a
+``format`` the frame keeps its own layout: ``ops.image.rescale`` (one launch that resizes every sample plane by an
+exact area average), a frame of the same class and parameters, no RGB frame and no colour conversion on the way. With
+a ``format`` the frame is written in that layout instead: ``ops.image.convert`` (one launch: the source read as the
+model reads it, PQ / HLG included, resized by the same area average, stored in the target's layout, depth, subsampling,
+order, matrix and range). Nothing here synchronises with the host, so ``YolosSmall.annotate_image(..., scaler=...)``
+captures as one graph: frame in, annotated frame out at another size and layout.
 
-Bilinear, bicubic and Lanczos resizing, changing layout, depth or subsampling while resizing, PQ / HLG surfaces,
-batches, sides above 8192 and resizing in place are not offered."""
+Bilinear, bicubic and Lanczos resizing, chroma sitings other than centred on the way out, dithering, PQ / HLG targets
+(and, without a ``format``, PQ / HLG surfaces), batches, sides above 8192 and resizing in place are not offered."""
 from __future__ import annotations
 
 from dataclasses import replace
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
 from ...ops import image as I
 
+#: the formats a :class:`Scaler` writes beside the 19 of ``surfaces.FORMATS``: packed pixels and 8-bit 4:2:0
+PACKED_FORMATS, YUV420_FORMATS = ("rgb", "bgr", "rgba", "bgra"), ("nv12", "nv21", "i420", "yv12")
+
 
 class Scaler:
-    def __init__(self, size: Tuple[int, int]):
-        """``size``: ``(rows, columns)`` of every frame :meth:`scale` returns, 1..8192 each."""
+    def __init__(self, size: Tuple[int, int], format: Optional[str] = None, matrix: Optional[str] = None,
+                 full_range: Optional[bool] = None):
+        """``size``: ``(rows, columns)`` of every frame :meth:`scale` returns, 1..8192 each. ``format``: None — the
+        frame's own layout — or the layout of every frame :meth:`scale` returns: ``rgb``, ``bgr``, ``rgba``, ``bgra``,
+        ``nv12``, ``nv21``, ``i420``, ``yv12`` or a name of ``surfaces.FORMATS``. ``matrix`` and ``full_range`` of a YUV
+        ``format``: by default the source's where it is YUV and SDR, else ``bt709`` and limited range."""
         try:
             H, W = (int(v) for v in size)
         except (TypeError, ValueError):
             raise ValueError(f"Scaler: size {size!r} is not (rows, columns)") from None
         if not (1 <= H <= I.RESCALE_MAX_SIDE and 1 <= W <= I.RESCALE_MAX_SIDE):
             raise ValueError(f"Scaler: size {size!r} is not (rows, columns) of 1..{I.RESCALE_MAX_SIDE}")
-        self.size = (H, W)
+        if format is not None:
+            from . import surfaces
+            if format not in PACKED_FORMATS + YUV420_FORMATS + tuple(surfaces.FORMATS):
+                raise ValueError(f"Scaler: format {format!r} is none of "
+                                 f"{PACKED_FORMATS + YUV420_FORMATS + tuple(sorted(surfaces.FORMATS))}")
+            if matrix is not None:
+                I.yuv_real_matrix(matrix)
+        self.size, self.format, self.matrix, self.full_range = (H, W), format, matrix, full_range
+
+    def _converted(self, frame):
+        """:meth:`target` with a ``format``: a contiguous frame of it at ``size``, cached under (device, format, matrix,
+        range, size). A 4:2:0 format takes an even number of rows, as the buffers of its decoders do."""
+        from . import surfaces
+        from .processor import Nv12, Packed, Yuv420p
+        H, W = self.size
+        fmt, device = self.format, I._chip_source(frame)[3]
+        yuv_sdr = not isinstance(frame, torch.Tensor) and hasattr(frame, "matrix") \
+            and getattr(frame, "transfer", "sdr") == "sdr"
+        matrix = self.matrix if self.matrix is not None else frame.matrix if yuv_sdr else "bt709"
+        full = bool(self.full_range if self.full_range is not None else frame.full_range if yuv_sdr else False)
+        if fmt in PACKED_FORMATS:
+            matrix, full = None, None
+        key = (str(device), "convert", fmt, matrix, full, H, W)
+
+        def buffer(n: int, fill: int = 0) -> torch.Tensor:
+            return I._scale_buffers.get(key, lambda: (torch.full((n,), fill, dtype=torch.uint8, device=device),))[0]
+        if fmt in PACKED_FORMATS:
+            C = len(fmt)
+            return Packed(buffer(H * W * C, 0xFF).view(H, W, C), fmt)
+        even = 2 * ((W + 1) // 2)       # a luma row's samples, rounded up to whole chroma pairs
+        if fmt in ("nv12", "nv21"):
+            return Nv12.from_buffer(buffer(even * (H + H // 2)), H, W, even, matrix, full, vu=fmt == "nv21")
+        if fmt in YUV420_FORMATS:
+            return Yuv420p.from_buffer(buffer(even * (H + H // 2)), H, W, even, order=fmt, matrix=matrix, full_range=full)
+        kind, _, depth = surfaces.FORMATS[fmt][:3]
+        row = 2 * even if kind == "packed" else even * (1 if depth == 8 else 2)
+        # luma rows, then at most twice as many bytes of chroma (4:4:4)
+        return surfaces.from_buffer(fmt, buffer(3 * row * H), H, W, row, matrix=matrix, full_range=full)
 
     def target(self, frame):
-        """The frame :meth:`scale` writes for ``frame``: its class and parameters, its layout and sample type at
-        ``size``, contiguous planes allocated once per (device, layout, size) and kept as ``ops.image``'s chip buffers
-        are — a later call of the same key overwrites them, and a captured graph keeps them alive. A planar target is
-        one allocation with U and V in the order they lie in ``frame``; the fourth byte of a packed pixel is 0xFF."""
+        """The frame :meth:`scale` writes for ``frame``. Without a ``format``: its class and parameters, its layout and
+        sample type at ``size``, contiguous planes allocated once per (device, layout, size) and kept as
+        ``ops.image``'s chip buffers are — a later call of the same key overwrites them, and a captured graph keeps
+        them alive. A planar target is one allocation with U and V in the order they lie in ``frame``; the fourth byte
+        of a packed pixel is 0xFF. With a ``format``: a ``Packed``, ``Nv12``, ``Yuv420p`` or ``surfaces`` frame of it
+        over one buffer, kept the same way per (device, format, matrix, range, size)."""
+        if self.format is not None:
+            return self._converted(frame)
         s = I.overlay_surface(frame)
         H, W = self.size
         if s.packed is not None:
@@ -64,6 +115,10 @@ class Scaler:
         return replace(frame, y=y, u=u, v=v)
 
     def scale(self, frame):
-        """``frame`` (anything ``ops.image.overlay_surface`` takes: SDR, one frame) resized to ``size``: a frame of the
-        same class and parameters (matrix, range, ``vu``, order, depth, ...) whose planes are :meth:`target`'s."""
+        """``frame`` resized to ``size``. Without a ``format``: anything ``ops.image.overlay_surface`` takes (SDR, one
+        frame), returned as a frame of the same class and parameters (matrix, range, ``vu``, order, depth, ...) whose
+        planes are :meth:`target`'s. With a ``format``: anything ``ops.image.chips`` reads (PQ / HLG too, one frame),
+        returned as :meth:`target`'s frame of that format."""
+        if self.format is not None:
+            return I.convert(frame, self.target(frame))
         return I.rescale(frame, self.target(frame))

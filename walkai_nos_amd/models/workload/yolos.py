@@ -501,7 +501,8 @@ class YolosSmall(nn.Module):
         place: a decoder writes the next frame over it before the next replay. With ``target=None`` a replay on an
         unchanged buffer therefore detects on the annotated frame, not on the one that was put there. With a ``scaler``
         (``scaler.Scaler``) the painted surface is resized after the drawing, one more launch inside the same graph, and
-        the dict gains ``"scaled"``: a frame of the surface's class and layout at the scaler's size."""
+        the dict gains ``"scaled"``: a frame of the surface's class and layout — or of the scaler's ``format`` — at the
+        scaler's size."""
         det = self.detect_image(frame, threshold) if tracker is None else self.track_image(frame, tracker, threshold)
         return self._painted(det, overlay.draw(det, frame if target is None else target), scaler)
 

@@ -188,7 +188,13 @@ def _L() -> ctypes.CDLL:
             # a surface and its size on either side of both rescale entries
             L.nos_rescale_packed.argtypes = [vp, vp, vp, i64, i32, i32] * 2 + [ctypes.c_char_p, vp]
             L.nos_rescale_yuv.argtypes = [src, i32, i32] * 2 + [vp]
+            # both convert entries behind their source: a packed target or a YUV one, its size and the colour rule
+            converted = [vp, vp, vp, i64, ctypes.c_char_p, src, i32, i32, ip, vp]
+            L.nos_convert_packed.argtypes = [vp, vp, vp, i64, ctypes.c_char_p, i32, i32] + converted
+            L.nos_convert_yuv.argtypes = [src, hdr, i32, i32] + converted
             L.nos_image_last_error.restype = ctypes.c_char_p
+            if L.nos_convert_max_side() != CONVERT_MAX_SIDE:
+                raise NativeUnavailable(f"{LIB} was built with another largest convert side than ops/image.py expects")
             if L.nos_rescale_max_side() != RESCALE_MAX_SIDE:
                 raise NativeUnavailable(f"{LIB} was built with another largest rescale side than ops/image.py expects")
             if (L.nos_overlay_tile_rows(), L.nos_overlay_tile_columns()) != OVERLAY_TILE:
@@ -2733,8 +2739,8 @@ def rescale(frame, target):
 
     One HIP launch (``rescale_k``: a workgroup per tile of whole storage units of the target and band of rows,
     ``csrc/image_scale.h``) on the GPU for sides of 1..:data:`RESCALE_MAX_SIDE`; past that, on the CPU and with the
-    ``torch`` backend :func:`rescale_reference`. Bilinear, bicubic and Lanczos resizing, changing layout, depth or
-    subsampling on the way, PQ / HLG surfaces, batches, and resizing in place are not offered."""
+    ``torch`` backend :func:`rescale_reference`. Bilinear, bicubic and Lanczos resizing, batches, and resizing in place
+    are not offered; changing layout, depth or subsampling on the way and PQ / HLG sources are :func:`convert`'s."""
     s, d = _rescale_check(frame, target)
     if not _use_hip(d.samples[0][0]) or max(s.h, s.w, d.h, d.w) > RESCALE_MAX_SIDE:
         return rescale_reference(frame, target)
@@ -2744,6 +2750,140 @@ def rescale(frame, target):
     # either end with its size; the order (packed pixels only) once, behind both
     rc = entry(*place, *pitch, s.h, s.w, *to_place, *to_pitch, d.h, d.w, *order, stream)
     _check(rc, "rescale")
+    return target
+
+
+# ---- a frame converted into a surface of another layout and size -------------------------------------------
+#: the largest side of either frame, and the largest source of a resizing call, on the HIP route of :func:`convert`
+#: (``csrc/image_convert.h``)
+CONVERT_MAX_SIDE, CONVERT_MAX_AREA = 8192, 1 << 24
+
+
+def convert_table(matrix: str = "bt601", full_range: bool = False, depth: int = 8) -> Tuple[int, ...]:
+    """The 12 integers :func:`convert` computes a YUV target's codes with: ``rint(inv(M) * 2^14)`` of
+    :func:`yuv_real_matrix` by rows (Y, U, V) x (R, G, B) — in each chroma row the entry of largest magnitude is then
+    replaced so that the row sums to zero, so grey gets exactly neutral chroma — then the three offsets. Every
+    coefficient is at most 187 953 in size (below 2^18) and the absolute sum of a row at most 263 174 (depth 12, full
+    range); with a block's sum of at most 4 x 255 per channel and the offset term ``4 (2048 << 14) + 4 2^13`` every
+    sum stays below 4.03e8 in size (int32)."""
+    m, off = yuv_real_matrix(matrix, full_range, depth)
+    t = np.rint(np.linalg.inv(m) * float(1 << 14)).astype(np.int64)
+    for row in (1, 2):
+        k = int(np.argmax(np.abs(t[row])))
+        t[row, k] -= t[row].sum()
+    return tuple(int(v) for v in t.reshape(-1)) + tuple(off)
+
+
+def _convert_check(frame, target) -> tuple:
+    """Both operands of :func:`convert` described and checked, ``ValueError`` before any launch: ``(h, w, packed, yuv,
+    rgb, d)`` — the frame as :func:`_chip_source` reads it, the target as :func:`overlay_surface` describes it; one
+    frame each, one device, storage that does not meet (the test of :func:`_rescale_check`)."""
+    who = "convert"
+    B, h, w, device, packed, yuv, rgb = _chip_source(frame)
+    if B != 1:
+        raise ValueError(f"{who}: one frame, not a batch of {B}")
+    try:
+        d = overlay_surface(target)
+    except ValueError as e:
+        raise ValueError(f"{who}: the target: {e}") from None
+    if device != d.device:
+        raise ValueError(f"{who}: the frame is on {device}, the target on {d.device}")
+    if packed is not None:
+        bounds = [_storage_bounds(packed[0])]
+    else:
+        bounds = [(yuv[0].plane[i].lo, yuv[0].plane[i].hi) for i in range((3, 2, 1)[yuv[0].layout])]
+    for t in ((d.packed[0],) if d.packed is not None else d.yuv[1]):
+        blo, bhi = _storage_bounds(t)
+        if any(alo < bhi and blo < ahi for alo, ahi in bounds):
+            raise ValueError(f"{who}: the frame's and the target's storage meet (converting in place is not offered)")
+    return h, w, packed, yuv, rgb, d
+
+
+def convert_reference(frame, target):
+    """The torch composition of :func:`convert`, with the same effect on ``target`` on any device and for any size,
+    without a host sync: ``frame.rgb()``, at another size ``Wy @ rgb @ Wx^T`` in float64 with :func:`chip_weights` —
+    exact, every term is an integer below 2^53 — and ``(sum + A // 2) // A`` in int64; then per sample plane the bytes,
+    or :func:`convert_table`'s rule on the sums of the blocks in int64, stored through the plane's strided view
+    (:func:`_plane_store`; a 16-bit word whole, as ``code << shift``). It is the definition."""
+    h, w, _, _, rgb, d = _convert_check(frame, target)
+    R = rgb()[0].to(torch.int64)                                      # [h, w, 3]
+    if (h, w) != (d.h, d.w):
+        A = h * w
+        total = chip_weights(h, d.h, d.device) @ R.permute(2, 0, 1).to(torch.float64) @ chip_weights(w, d.w, d.device).t()
+        R = torch.div(total.to(torch.int64) + A // 2, A, rounding_mode="floor").permute(1, 2, 0)
+    if d.packed is not None:
+        for view, c, _, _ in d.samples:
+            _plane_store(view, R[..., c].to(torch.int32), 0)
+        return target
+    matrix, full, depth = d.colour
+    t = convert_table(matrix, full, depth)
+    for view, c, hs, vs in d.samples:
+        ch, cw = view.shape
+        # the blocks clipped to the frame: the sum of each, and how many pixels it holds, 1 << k
+        S = torch.nn.functional.pad(R, (0, 0, 0, (cw << hs) - d.w, 0, (ch << vs) - d.h))
+        S = S.reshape(ch, 1 << vs, cw, 1 << hs, 3).sum((1, 3))
+        ky = torch.full((ch,), vs, dtype=torch.int64, device=d.device)
+        kx = torch.full((cw,), hs, dtype=torch.int64, device=d.device)
+        if (ch << vs) != d.h:
+            ky[-1] = 0
+        if (cw << hs) != d.w:
+            kx[-1] = 0
+        k = ky[:, None] + kx[None, :]
+        code = (t[3 * c] * S[..., 0] + t[3 * c + 1] * S[..., 1] + t[3 * c + 2] * S[..., 2]
+                + ((t[9 + c] << 14) + (1 << 13) << k)) >> (14 + k)
+        _plane_store(view, code.clamp(0, (1 << depth) - 1).to(torch.int32), d.shift)
+    return target
+
+
+def convert(frame, target):
+    """``frame`` converted into ``target``, a second surface of any other layout, depth, subsampling, component order,
+    matrix, range and size, with no host synchronisation and no RGB frame; returns ``target``. ``frame``: anything
+    :func:`chips` reads (a uint8 RGB tensor, ``Packed`` or any YUV frame; nearest or bilinear chroma at any siting;
+    transfer ``sdr``, ``pq`` or ``hlg``), exactly one frame. ``target``: anything :func:`overlay_surface` takes — SDR,
+    one frame, writable — on the same device; the two storages do not meet. Anything else is a ``ValueError`` before
+    any launch. The rule, in exact integers:
+
+    1. ``R [H, W, 3]`` uint8 is the exact area average of ``frame.rgb()`` stretched to the target's ``H x W``: per
+       channel ``(sum Wy Wx v + A // 2) // A`` with :func:`chip_weights` and ``A = h w`` — rule 4 of :func:`chips` on
+       the whole frame. At equal sizes ``R`` is ``frame.rgb()``.
+    2. A packed target stores ``R``'s bytes in its order; the fourth byte of RGBA / BGRA is not written.
+    3. A YUV target computes codes with ``t = convert_table(matrix, full_range, depth)`` of the target. Luma of pixel
+       ``(y, x)`` is ``clip((t[0:3] . R[y][x] + (t[9] << 14) + 2^13) >> 14, 0, 2^depth - 1)``. A chroma sample ``(cy,
+       cx)`` covers the luma pixels of its block ``[cy << vs, (cy + 1) << vs) x [cx << hs, (cx + 1) << hs)`` clipped to
+       the frame, ``n = 2^k`` pixels with ``n`` in {1, 2, 4}; with ``S`` the sum of ``R`` over the block its code is
+       ``clip((t_c . S + n (off_c << 14) + n 2^13) >> (14 + k), 0, 2^depth - 1)``, an arithmetic shift and one
+       rounding. This is the block's mean, that is centred siting: chroma co-sited with a luma column or row on the
+       way out is not offered. :func:`convert_table` states the bound that keeps every sum in int32 at depth 12.
+    4. A sample is stored as the byte, or as the whole 16-bit word ``code << shift``.
+    5. Every sample of every plane of the target is written by every call, and nothing else: not the pitch padding,
+       not the parent of a crop, not the fourth byte, no byte of the source.
+
+    One HIP launch (``convert_k``: a workgroup per tile of 128 columns x a band of rows of the target,
+    ``csrc/image_convert.h``) on the GPU for sides of 1..:data:`CONVERT_MAX_SIDE` and, where the sizes differ, a frame
+    of at most :data:`CONVERT_MAX_AREA` pixels; past that, on the CPU and with the ``torch`` backend
+    :func:`convert_reference`. The kernel beat the reference in every pair measured (``tools/kbench.py --only image
+    --rows convert``: by 7.5 to 77 times on the whole GPU, by 3.8 to 72 on a 32-CU slice; the README holds the rows), so
+    no pair or size inside the limits stays on the reference. Not offered: chroma sitings other than centred on the way
+    out, dithering, PQ / HLG targets, batches, and converting in place."""
+    h, w, packed, yuv, _, d = _convert_check(frame, target)
+    same = (h, w) == (d.h, d.w)
+    if not _use_hip(d.samples[0][0]) or max(h, w, d.h, d.w) > CONVERT_MAX_SIDE or (not same and h * w > CONVERT_MAX_AREA):
+        return convert_reference(frame, target)
+    if d.packed is not None:
+        (to, lo, hi), (to_pitch,), (to_order,) = _surface_args(d.packed, None)
+        end = (to, lo, hi, to_pitch, to_order, None, d.h, d.w, None)
+    else:
+        table = (ctypes.c_int * 12)(*convert_table(*d.colour))
+        end = (None, None, None, 0, None, ctypes.byref(yuv_src(*d.yuv, ())), d.h, d.w, table)
+    stream = torch.cuda.current_stream().cuda_stream
+    if packed is not None:
+        place, pitch, order = _surface_args(packed, None)
+        rc = _L().nos_convert_packed(*place, *pitch, *order, h, w, *end, stream)
+    else:
+        src, hdr = yuv
+        tables = None if hdr is None else ctypes.byref(yuv_hdr(*_hdr_device_tables(*hdr, d.device)))
+        rc = _L().nos_convert_yuv(ctypes.byref(src), tables, h, w, *end, stream)
+    _check(rc, "convert")
     return target
 
 
